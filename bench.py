@@ -2,7 +2,12 @@
 """Headline benchmark: registration pairs/sec on synthetic 3DMatch_test-like clouds (BASELINE.json
 configs[1]: voxel 0.0625 m, ~5k points per cloud, batch-of-pairs = 32 per GPU).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, higher_is_better,
+dtype, ms_per_step, the config it ran).  --full adds everything else listed below, measured after the headline region.
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (see dump_outputs); the
+inputs are seeded, so two builds can be compared output for output.
 
 N > 1 runs one rank per GPU over RCCL.  Started under torch.distributed.run (RANK / WORLD_SIZE in the environment)
 this process IS a rank; started bare, it stays a CPU-only parent that spawns the N ranks as child processes before
@@ -12,11 +17,13 @@ One *step* = the hot path A1-A10 over one batch of 32 pai
 in HBM: PointTransformer forward -> thresholded 1-NN -> fused gather + Kabsch -> RE/TE (+ the all-gather
 of per-pair metric rows when N > 1, the path's only collective).  Rank 0 prints ONE JSON line.
 
-Extra objects on that line:
+Extra objects on that line with --full:
+  output_checksum -- sums of the last timed step's RE / TE / correspondence counts, checked bit-equal to the first warm-up step's.
   roofline     -- the GEMM kernel (all epilogue instantiations pooled; per-instantiation rows in "by_kernel" so
                   they can be matched against profiles/*kernel_stats*): algorithmic fp32 flops (true, unpadded
                   token counts) / the time during which a GEMM launch was running, measured live with HIP events
-                  on the launch streams inside the timed region (scream_trace_*).  Consecutive steps run WHOLE on two
+                  on the launch streams over K more steps timed like the headline's (scream_trace_*; the headline
+                  region itself runs without the events).  Consecutive steps run WHOLE on two
                   alternating HIP streams (config.steps_in_flight = 2; round 3 -- rounds 1-2 split every step into two
                   concurrent lanes, --lanes 2), so launches of two steps overlap: that time is the union of the launch intervals
                   ("busy_ms_per_step"; "summed_launch_ms_per_step" and the per-launch avg_ms rows count overlapped
@@ -25,7 +32,7 @@ Extra objects on that line:
                   kernels on the fp16 matrix cores with THREE MFMAs per fp32 product -> 2500 / 3 = 833.3 TFLOP/s of
                   fp32-equivalent work; SCREAM_GEMM=x3 on the bf16 matrix cores with six -> 2500 / 6 = 416.7;
                   SCREAM_GEMM=f32 runs gemm_f32_kernel against the 157.3 TFLOP/s fp32 matrix peak.
-  sustained_value -- pairs/s over >= 3 s of back-to-back steps right after the timed region (the power governor needs a few
+  sustained_value -- pairs/s over >= 3 s of back-to-back steps right after the timed regions (the power governor needs a few
                   hundred ms to settle; `value` is the K steps the driver asked for).
   variant_registered_pred -- the same step re-timed (outside the headline region) with src_pred replaced, after the
                   forward, by GT-registered src + 1 cm noise, so that the search/gather/Kabsch stages see realistic
@@ -150,6 +157,44 @@ def cpu_baseline(items, sd, max_pairs, budget_s=25.0):
                       % (done, len(items), cores, t_total)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, re, te, lane_outs, lane_parts):
+    """--dump-outputs: what the last timed step returned to its caller, this rank's pairs in order.  Per pair: T_pred [B,4,4],
+    n_corr, re_deg, te; per true source row (padding rows dropped): src_pred [rows,3] (the forward's output) and the
+    thresholded 1-NN's nn_idx, nn_dmin, nn_valid.  Floats stay float32, integers and flags become float64 (exact).  If the
+    per-row arrays would take the files past 64 MB, a fixed seeded sample of rows is written, with its row numbers (rows.npy)."""
+    import torch
+    rows = []
+    for ln, o in zip(lane_parts, lane_outs):
+        b = ln.batch
+        rows.append(torch.cat([torch.arange(int(b.cloud_row0_host[k]), int(b.cloud_row0_host[k]) + b.src_len[k]) for k in range(b.n_pairs)]))
+
+    def per_row(key):
+        return torch.cat([o[key].detach().cpu()[r] for r, o in zip(rows, lane_outs)]).numpy()
+
+    def f64(a):
+        return np.asarray(a).astype(np.float64)
+
+    per_pair = {"T_pred": torch.cat([o["T"].detach().cpu() for o in lane_outs]).float().numpy(),
+                "n_corr": f64(torch.cat([o["n_corr"].detach().cpu() for o in lane_outs]).numpy()),
+                "re_deg": re.detach().cpu().float().numpy(), "te": te.detach().cpu().float().numpy()}
+    row_arrays = {"src_pred": per_row("src_pred").astype(np.float32), "nn_idx": f64(per_row("idx")),
+                  "nn_dmin": per_row("dmin").astype(np.float32), "nn_valid": f64(per_row("valid"))}
+    n_rows = row_arrays["src_pred"].shape[0]
+    row_bytes = sum(a.nbytes for a in row_arrays.values()) / max(n_rows, 1)
+    fixed = sum(a.nbytes for a in per_pair.values())
+    keep = int((DUMP_LIMIT_BYTES - fixed - (1 << 20)) // (row_bytes + 8))
+    if keep < n_rows:
+        sample = np.sort(np.random.default_rng(0).choice(n_rows, size=keep, replace=False))
+        row_arrays = {k: v[sample] for k, v in row_arrays.items()}
+        row_arrays["rows"] = sample.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in {**per_pair, **row_arrays}.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def _free_port():
     import socket
     with socket.socket() as so:
@@ -231,6 +276,12 @@ def main():
     ap.add_argument("--lanes", type=int, default=None,
                     help="split every step's pairs into this many concurrent sub-batches that start together (scream_amd/lanes.py; "
                          "rounds 1-2's default was 2); --lanes 1 = one step at a time on one stream")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline region, also measure and check everything else on the line (output checksum, traced roofline "
+                         "region, sustained rate, registered-prediction variant, power, per-kernel roofs, HBM traffic record, CPU "
+                         "baseline); the --no-* options below drop parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sustain", dest="sustain", action="store_false", help="skip the >= 3 s sustained-rate leg")
     ap.add_argument("--no-secondary", dest="secondary", action="store_false",
@@ -245,6 +296,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher rehearsal without a GPU: every rank joins a gloo group, all-gathers its rank and rank 0 prints them")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:  # bare `python bench.py --gpus N`: be the launcher
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -312,6 +365,9 @@ def main():
             self.s = torch.tensor([it[4] for it in its], dtype=torch.float32, device=dev)
             self.c = torch.stack([it[5] for it in its]).to(dev)
             self.T_gt = torch.stack([gt_pose_metric(it[2], it[3], it[4], it[5]) for it in its]).to(dev)
+            self.reg_pred = None
+            if not args.full:
+                return
             # with random weights almost nothing passes the distance threshold, so A8/A9 see K ~ 0; the
             # "registered prediction" variant swaps in GT-registered src + 1 cm noise after the forward (K ~ overlap * N)
             reg = torch.zeros(self.batch.rows_src, 3)
@@ -344,7 +400,7 @@ def main():
             src_pred = ln.reg_pred
         T, n_corr, idx, dmin, valid = register_batch(ln.batch, src_pred, ln.s, ln.c, dis_thresh)  # A7-A9
         re, te = ops.transformation_error_batched(T, ln.T_gt)                                 # A10
-        return re, te, n_corr
+        return re, te, n_corr, {"src_pred": src_pred, "T": T, "n_corr": n_corr, "idx": idx, "dmin": dmin, "valid": valid}
 
     def step(trace=None, registered=False):
         if alt_streams:  # the whole step on the next stream; nothing joins until fence()
@@ -361,43 +417,79 @@ def main():
             rows = torch.zeros(B, sdist.ROW_WIDTH, device=dev)
             rows[:, 0], rows[:, 4], rows[:, 5] = pair_ids, re, te
             tdist.all_gather(gathered[slot], rows.to(coll_dev))
-        return re, te, n_corr
+        return re, te, n_corr, [o[3] for o in outs]
 
     def fence():
         if world > 1:
             tdist.barrier()
         torch.cuda.synchronize()
 
+    def headline_line(elapsed):
+        """The result line of a plain run: the K timed steps and the configuration they ran."""
+        return {
+            "metric": "registration pairs/sec", "value": round(B * world * args.steps / elapsed, 3), "unit": "pairs/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f16 (autocast mirror; not the fp32 path)" if net.gemm_backend == "h1" else "f32", "data": "synthetic",
+            "config": {"workload": {"3dmatch": "BASELINE configs[1]: synthetic 3DMatch_test-like pairs, voxel 0.0625 m, ~5k points/cloud",
+                                    "kitti": "BASELINE configs[3]: synthetic KITTI_test-like pairs, voxel 0.7 m, ~13-16k points/cloud",
+                                    "uniform64k": "BASELINE configs[4]: 65 536 uniform points per cloud"}[args.workload]
+                                   + ", batch-of-pairs=%d per GPU, A1-A10 per pair (forward 6+6 layers d_model 256, 1-NN thresh %g, "
+                                     "Kabsch, RE/TE), random-init weights seed 0" % (B, dis_thresh),
+                       "pairs_per_step_per_gpu": B, "lanes": len(lane_parts), "steps_in_flight": max(1, args.alternate), "mean_src_points": round(float(np.mean(src_len)), 1),
+                       "mean_tgt_points": round(float(np.mean(tgt_len)), 1), "parallelism": "dp%d (pairs sharded, metric-row all-gather)" % world,
+                       "rccl_ranks": tdist.get_world_size() if world > 1 else 1, "collective_backend": backend if world > 1 else None,
+                       "gemm_backend": net.gemm_backend},
+        }
+
     first = None
     for _ in range(args.warmup):
         o = step()
-        if first is None:
+        if args.full and first is None:
             if alt_streams:
                 torch.cuda.synchronize()  # the step ran on a side stream
-            first = tuple(t.clone() for t in o)
-    cap = 200 * len(lane_parts) * max(args.steps, 1)  # ~135 records per forward
-    trace = lib.scream_trace_create(cap)
-    assert trace, "scream_trace_create failed"
+            first = tuple(t.clone() for t in o[:3])
+    # ---- the headline region: K steps, nothing else -------------------------------------------------------------
     fence()
     t0 = time.perf_counter()
     last = None
     for _ in range(args.steps):
-        last = step(trace)
+        last = step()
     fence()
     elapsed = time.perf_counter() - t0
-    # the timed steps did the work: every step's RE / TE / correspondence counts -- functions of the whole forward, search
-    # and solve -- are finite and, the path being deterministic, bit-identical to the first warm-up step's
-    checksum = None
-    if last is not None:
-        assert all(bool(torch.isfinite(t.float()).all()) for t in last), "non-finite outputs in the timed region"
-        if first is not None:
-            assert all(torch.equal(a, b) for a, b in zip(first, last)), "timed step differs from the first warm-up step"
-        checksum = {"sum_re_deg": round(float(last[0].double().sum().item()), 6), "sum_te": round(float(last[1].double().sum().item()), 6),
-                    "sum_correspondences": int(last[2].sum().item()), "equal_to_first_warmup_step": first is not None}
     if world > 1:
         t = torch.tensor([elapsed], device=coll_dev, dtype=torch.float64)
         tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[0], last[1], last[3], lane_parts)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline_line(elapsed)), flush=True)
+        if world > 1:
+            tdist.barrier()
+            tdist.destroy_process_group()
+        return
+    # the timed steps did the work: every step's RE / TE / correspondence counts -- functions of the whole forward, search
+    # and solve -- are finite and, the path being deterministic, bit-identical to the first warm-up step's
+    last = last[:3]
+    assert all(bool(torch.isfinite(t.float()).all()) for t in last), "non-finite outputs in the timed region"
+    if first is not None:
+        assert all(torch.equal(a, b) for a, b in zip(first, last)), "timed step differs from the first warm-up step"
+    checksum = {"sum_re_deg": round(float(last[0].double().sum().item()), 6), "sum_te": round(float(last[1].double().sum().item()), 6),
+                "sum_correspondences": int(last[2].sum().item()), "equal_to_first_warmup_step": first is not None}
+
+    # ---- the same K steps again with HIP events around every launch (scream_trace_*): the per-kernel times of the roofline.
+    # A region of its own, so that the events never sit in the headline's
+    cap = 200 * len(lane_parts) * args.steps  # ~135 records per forward
+    trace = lib.scream_trace_create(cap)
+    assert trace, "scream_trace_create failed"
+    fence()
+    t_tr = time.perf_counter()
+    for _ in range(args.steps):
+        step(trace)
+    fence()
+    traced_elapsed = time.perf_counter() - t_tr
 
     # ---- sustained rate: >= 3 s of back-to-back steps (same step, no trace), the same count on every rank -------
     n_sus = max(args.steps, int(np.ceil(3.0 / max(elapsed / max(args.steps, 1), 1e-4)))) if args.sustain else 0
@@ -442,7 +534,7 @@ def main():
     t1 = time.perf_counter()
     n_run = 0
     while n_run < n_var or (sampling[0] and world == 1 and time.perf_counter() - t1 < 1.0):  # >= 1 s so rocm-smi sees it
-        re_v, te_v, k_v = step(None, registered=True)
+        re_v, te_v, k_v, _ = step(None, registered=True)
         n_run += 1
     fence()
     var_elapsed = time.perf_counter() - t1
@@ -534,7 +626,7 @@ def main():
     by_kernel = []
     for k_, v in sorted(by.items(), key=lambda kv: (kv[0] >= 100, kv[0])):
         row = {"kernel": GEMM_NAMES.get(k_, str(k_)), "launches": v["launches"],
-               "avg_ms": round(v["ms"] / v["launches"], 4), "share_of_step": round(v["ms"] / (elapsed * 1e3), 4)}
+               "avg_ms": round(v["ms"] / v["launches"], 4), "share_of_step": round(v["ms"] / (traced_elapsed * 1e3), 4)}
         if k_ < 100:
             row["tflops_algorithmic"] = round(v["padded_flops"] * pad_eff / (v["ms"] * 1e-3) / 1e12, 2)
         by_kernel.append(row)
@@ -611,23 +703,10 @@ def main():
                   ("gemm_f32_kernel (v_mfma_f32_32x32x2_f32; all epilogue instantiations; the fused K^T V epilogue's own "
                    "MFMAs are not counted as algorithmic flops)")
     if rank == 0:
-        total_pairs = B * world * args.steps
-        out = {
-            "metric": "registration pairs/sec", "value": round(total_pairs / elapsed, 3), "unit": "pairs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-            "sustained_value": None if sustained is None else sustained[0],
-            "sustained": None if sustained is None else {"steps": sustained[1], "seconds": sustained[2]},
-            "vs_baseline": None, "dtype": "f16 (autocast mirror; not the fp32 path)" if gb == "h1" else "f32", "data": "synthetic",
-            "config": {"workload": {"3dmatch": "BASELINE configs[1]: synthetic 3DMatch_test-like pairs, voxel 0.0625 m, ~5k points/cloud",
-                                    "kitti": "BASELINE configs[3]: synthetic KITTI_test-like pairs, voxel 0.7 m, ~13-16k points/cloud",
-                                    "uniform64k": "BASELINE configs[4]: 65 536 uniform points per cloud"}[args.workload]
-                                   + ", batch-of-pairs=%d per GPU, A1-A10 per pair (forward 6+6 layers d_model 256, 1-NN thresh %g, "
-                                     "Kabsch, RE/TE), random-init weights seed 0" % (B, dis_thresh),
-                       "pairs_per_step_per_gpu": B, "lanes": len(lane_parts), "steps_in_flight": max(1, args.alternate), "mean_src_points": round(float(np.mean(src_len)), 1),
-                       "mean_tgt_points": round(float(np.mean(tgt_len)), 1), "parallelism": "dp%d (pairs sharded, metric-row all-gather)" % world,
-                       "rccl_ranks": tdist.get_world_size() if world > 1 else 1, "collective_backend": backend if world > 1 else None,
-                       "gemm_backend": net.gemm_backend},
+        out = headline_line(elapsed)
+        out["sustained_value"] = None if sustained is None else sustained[0]
+        out["sustained"] = None if sustained is None else {"steps": sustained[1], "seconds": sustained[2]}
+        out.update({
             "roofline": {"bound": "mfma", "kernel": kernel_desc,
                          "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
                          "frac": round(achieved / peak, 4), "traffic": traffic, "secondary": secondary,
@@ -640,7 +719,7 @@ def main():
                          "algorithmic_gflop_per_step": round(algo_flops_step / 1e9, 1),
                          "row_padding_efficiency": round(pad_eff, 4), "by_kernel": by_kernel,
                          "by_gemm_shape": by_gemm_shape},
-        }
+        })
         out["output_checksum"] = checksum
         out["variant_registered_pred"] = variant
         out["power"] = power

@@ -12,8 +12,9 @@ Weights are not stored: they are regenerated from a numpy seed by
 scream_amd.synthetic.make_state_dict (PCG64, machine independent) and loaded into the
 reference model with load_state_dict, so a fixture is (seed, inputs, expected outputs).
 
-Usage:  python oracle/make_golden.py   (rewrites tests/golden/)
+Usage:  python oracle/make_golden.py   (rewrites tests/golden/; --reference-only: just reference.npz)
 """
+import hashlib
 import os
 import pickle
 import sys
@@ -321,8 +322,50 @@ def dataset_items(rng):
     np.savez(os.path.join(OUT, "dataset_items.npz"), **rec)
 
 
+def tensor_digest(t):
+    """sha256 of a tensor's contiguous bytes: equal digests = bit-identical tensors (a fixture of a full state dict would not fit)."""
+    return hashlib.sha256(t.detach().contiguous().numpy().tobytes()).hexdigest()
+
+
+def reference_records():
+    """tests/golden/reference.npz: what tests/test_oracle_live.py checks against -- the reference model's seeded initialisation
+    (names and digests of its state dicts), its full-size forward and in-model registration, and two geometry helpers."""
+    ref_pointnet, _, ref_utils, _ = import_reference()
+    rec = {}
+    # the full-size model of seed 0: digests of its weights, its forward and transform on seeded clouds
+    torch.manual_seed(0)
+    net = ref_pointnet.PointTransformer(d_model=256).eval()
+    sd = net.state_dict()
+    rec["full_keys"] = np.array(list(sd.keys()))
+    rec["full_digests"] = np.array([tensor_digest(v) for v in sd.values()])
+    g = torch.Generator().manual_seed(1)
+    src, tgt = torch.rand(1, 700, 3, generator=g) - 0.5, torch.rand(1, 900, 3, generator=g) - 0.5
+    center = torch.rand(1, 1, 3, generator=g) * 0.2
+    with torch.no_grad():
+        want, _, tr = net(src, tgt, center, 0.4, False, True, None)
+    rec.update(full_src=src.numpy(), full_tgt=tgt.numpy(), full_center=center.numpy(), full_src_pred=want.numpy(), full_transform=tr.numpy())
+    # the 2 + 2 layer model of seed 123: the initialisation the product must reproduce
+    torch.manual_seed(123)
+    sd = ref_pointnet.PointTransformer(d_model=256, self_layer_num=2, cross_layer_num=2).state_dict()
+    rec["small_keys"] = np.array(list(sd.keys()))
+    rec["small_digests"] = np.array([tensor_digest(v) for v in sd.values()])
+    # utils.rigid_transform_3d (weighted, thresholded) and utils.square_distance; the distance matrices by digest and a sample
+    rng = np.random.default_rng(0)
+    A = torch.from_numpy(rng.normal(size=(3, 400, 3)).astype(np.float32))
+    B = torch.from_numpy(rng.normal(size=(3, 400, 3)).astype(np.float32))
+    w = torch.from_numpy(rng.uniform(size=(3, 400)).astype(np.float32))
+    d = ref_utils.square_distance(A, B)
+    pick = np.random.default_rng(1).choice(d.numel(), size=4096, replace=False)
+    rec.update(geo_A=A.numpy(), geo_B=B.numpy(), geo_w=w.numpy(), geo_rigid=ref_utils.rigid_transform_3d(A, B, w.clone(), 0.3).numpy(),
+               geo_sqdist_digest=np.array(tensor_digest(d)), geo_sqdist_pick=pick, geo_sqdist_sample=d.reshape(-1)[pick].numpy())
+    np.savez_compressed(os.path.join(OUT, "reference.npz"), **rec)
+
+
 if __name__ == "__main__":
     if "--dataset-items-only" in sys.argv:  # adds tests/golden/dataset_items.npz without regenerating the other fixtures
         dataset_items(np.random.default_rng(20261004))
+    elif "--reference-only" in sys.argv:  # adds tests/golden/reference.npz without regenerating the other fixtures
+        reference_records()
     else:
         main()
+        reference_records()

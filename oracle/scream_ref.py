@@ -10,7 +10,7 @@ Parity status: PINNED.  ``oracle/make_golden.py`` imports the reference's own
 code in the build container (never on the GPU box) and writes
 ``tests/golden/*.npz``; ``tests/test_oracle_golden.py`` checks every function
 here against those vectors, and ``tests/test_oracle_live.py`` re-checks against
-the live reference whenever ``/root/reference`` is present.
+the reference's full-size model (``tests/golden/reference.npz``).
 
 Every function cites the reference file:line it restates (paths relative to the
 reference checkout).

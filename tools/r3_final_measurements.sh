@@ -4,8 +4,8 @@ set -o pipefail
 export SCREAM_NO_BUILD=1; cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; O=gpurun_out/r3final; mkdir -p $O
 timeout -k 10 700 python -m pytest tests -m gpu -x -q > $O/gpu_tests.txt 2>&1; rc=$?; tail -3 $O/gpu_tests.txt
 [ $rc -eq 0 ] || exit 1
-timeout -k 10 300 python bench.py --steps 40 --warmup 6 > $O/bench.json 2> $O/bench.err || exit 1
-timeout -k 10 300 python bench.py --steps 40 --warmup 6 --lanes 1 --no-cpu-baseline > $O/bench_l1.json 2> $O/bench_l1.err || exit 1
+timeout -k 10 300 python bench.py --full --steps 40 --warmup 6 > $O/bench.json 2> $O/bench.err || exit 1
+timeout -k 10 300 python bench.py --full --steps 40 --warmup 6 --lanes 1 --no-cpu-baseline > $O/bench_l1.json 2> $O/bench_l1.err || exit 1
 for M in "lanes1:--lanes 1" "default:"; do
   T=${M%%:*}; A=${M#*:}
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$T -- python3 bench.py --steps 7 --warmup 3 --gen-procs 1 --no-cpu-baseline --no-power --no-sustain $A > $O/bench_under_rocprof_$T.json 2> $O/rocprof_$T.err || exit 1
@@ -19,10 +19,10 @@ timeout -k 10 400 python tools/eval_e2e.py 4096 --workers 0,4,8 > $O/eval_e2e.tx
 cat $O/eval_e2e.txt
 for wl in kitti uniform64k; do
   P=32; [ $wl = uniform64k ] && P=16
-  timeout -k 10 300 python bench.py --workload $wl --pairs $P --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_$wl.json 2> $O/bench_$wl.err || exit 1
+  timeout -k 10 300 python bench.py --full --workload $wl --pairs $P --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_$wl.json 2> $O/bench_$wl.err || exit 1
 done
-for gb in x3 f32; do SCREAM_GEMM=$gb timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_$gb.json 2> $O/bench_$gb.err || exit 1; done
-SCREAM_BENCH_BACKEND=gloo SCREAM_BENCH_SINGLE_DEVICE=1 timeout -k 10 300 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_2rank.json 2> $O/bench_2rank.err || exit 1
+for gb in x3 f32; do SCREAM_GEMM=$gb timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_$gb.json 2> $O/bench_$gb.err || exit 1; done
+SCREAM_BENCH_BACKEND=gloo SCREAM_BENCH_SINGLE_DEVICE=1 timeout -k 10 300 python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_2rank.json 2> $O/bench_2rank.err || exit 1
 python - <<'PY'
 import json
 O="gpurun_out/r3final/"

@@ -3,8 +3,8 @@ set -o pipefail
 export SCREAM_NO_BUILD=1; cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; O=gpurun_out/$1; mkdir -p $O
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/gpu_tests.txt 2>&1; rc=$?; tail -5 $O/gpu_tests.txt
 [ $rc -eq 0 ] || exit 1
-env $2 timeout -k 10 300 python bench.py --steps 40 --warmup 6 > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
-env $2 timeout -k 10 300 python bench.py --steps 40 --warmup 6 --lanes 1 --no-cpu-baseline > $O/bench_l1.json 2> $O/bench_l1.err || exit 1
+env $2 timeout -k 10 300 python bench.py --full --steps 40 --warmup 6 > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+env $2 timeout -k 10 300 python bench.py --full --steps 40 --warmup 6 --lanes 1 --no-cpu-baseline > $O/bench_l1.json 2> $O/bench_l1.err || exit 1
 python - <<PY
 import json
 O="gpurun_out/$1/"

@@ -3,7 +3,7 @@ set -o pipefail
 export SCREAM_NO_BUILD=1; cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp; O=gpurun_out/r5grid; mkdir -p $O
 for i in 1 2; do for g in ${GRIDS:-256 240 224 192}; do
   if [ $g = 256 ]; then L=""; else L="SCREAM_LIB=tools/_ab/lib_g$g.so"; fi
-  env $L timeout -k 10 400 python bench.py --steps 40 --warmup 6 --no-cpu-baseline --no-secondary > $O/b_${g}_$i.json 2> $O/b_${g}_$i.err || { tail -5 $O/b_${g}_$i.err; exit 1; }
+  env $L timeout -k 10 400 python bench.py --full --steps 40 --warmup 6 --no-cpu-baseline --no-secondary > $O/b_${g}_$i.json 2> $O/b_${g}_$i.err || { tail -5 $O/b_${g}_$i.err; exit 1; }
 done; done
 python - <<PY
 import json

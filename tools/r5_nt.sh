@@ -11,7 +11,7 @@ done
 unset SCREAM_LIB
 for i in 1 2; do for v in $VARIANTS; do
   if [ $v = base ]; then L=""; else L="SCREAM_LIB=tools/_ab/lib_$v.so"; fi
-  env $L timeout -k 10 400 python bench.py --steps 40 --warmup 6 --no-cpu-baseline --no-secondary > $O/b_${v}_$i.json 2> $O/b_${v}_$i.err || { tail -5 $O/b_${v}_$i.err; exit 1; }
+  env $L timeout -k 10 400 python bench.py --full --steps 40 --warmup 6 --no-cpu-baseline --no-secondary > $O/b_${v}_$i.json 2> $O/b_${v}_$i.err || { tail -5 $O/b_${v}_$i.err; exit 1; }
 done; done
 python - <<PY
 import json
