@@ -140,7 +140,8 @@ int scream_gemm_qkv_split_f32(const float* A, int64_t lda, const void* W_packed,
  * layer k 0-3 | v 0-3 | k 4-7 | v 4-7; n_q = 256 with N = 768, or n_q = 0 with N = 512 L) is packed once by scream_pack_proj
  * into scream_proj_image_bytes(N, split) bytes: [N / 32 stages][split planes][16 fragments][64 lanes][8] fp16, in the order the
  * kernel consumes them (query chunks 0 .. 7, then per layer and head K_h, V_h).  M % 128 == 0; exponents as for
- * scream_gemm_qkv_split_f32 (a_exp, w_exp of the product; k_exp, v_exp of K' and V in the reduction). */
+ * scream_gemm_qkv_split_f32 (a_exp, w_exp of the product; k_exp, v_exp of K' and V in the reduction), and SCREAM_EINVAL unless
+ * a_exp + w_exp, v_exp - a_exp - w_exp and k_exp + v_exp lie in [-126, 126]. */
 int64_t scream_proj_image_bytes(int32_t N, int32_t split);
 int scream_pack_proj(const float* W, int32_t N, int32_t n_q, int32_t split, int32_t w_exp, void* proj_image, void* stream);
 int scream_proj_qkv_f32(const float* x, const void* proj_image, float* Q, int64_t M, int32_t N, int32_t n_q,

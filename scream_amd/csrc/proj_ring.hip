@@ -455,6 +455,11 @@ extern "C" int scream_proj_qkv_f32(const float* x, const void* proj_image, float
     SCREAM_REQUIRE(M >= 0 && M % SCREAM_ROW_TILE == 0 && row_base >= 0 && row_base % SCREAM_ROW_TILE == 0, SCREAM_EUNSUPPORTED);
     SCREAM_REQUIRE(n_q == 0 || Q, SCREAM_EINVAL);
     SCREAM_REQUIRE(a_exp >= -60 && a_exp <= 60 && w_exp >= -60 && w_exp <= 60 && k_exp >= -40 && k_exp <= 40 && v_exp >= -40 && v_exp <= 40, SCREAM_EINVAL);
+    // the factors below combine them, and each must stay a normal fp32 power of two (exp2i), elu1s's c log2(e) included: with the
+    // ranges above only v_exp - a_exp - w_exp can leave [-126, 126] (it reaches +-160); the other two sums (at most 120 and 80 today)
+    // are checked as well so that widening a range above cannot let them through silently
+    const auto in126 = [](int e) { return e >= -126 && e <= 126; };
+    SCREAM_REQUIRE(in126(a_exp + w_exp) && in126(v_exp - a_exp - w_exp) && in126(k_exp + v_exp), SCREAM_EINVAL);
     SCREAM_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(proj_image) | reinterpret_cast<uintptr_t>(Q) |
                      reinterpret_cast<uintptr_t>(kv_partial)) & 15) == 0, SCREAM_EINVAL);
     if (M == 0) return 0;

@@ -10,8 +10,13 @@
 //              |x| 2^e <= 2^15 holds for EVERY value the operand can take (scream_amd/scales.py derives the bounds from the
 //              weights: LayerNorm outputs are bounded by their gamma / beta, a projection of one by the norms of its rows, an
 //              attention output by its values).  Nothing can overflow, so there is no run-time flag; values below
-//              2^-3 / 2^e lose relative (not absolute) precision: 2^-25 / 2^e against a bound of 2^15 / 2^e, i.e. 2^-40 of
-//              the operand's range.  Measured against float64 with the hardware's own accumulation
+//              2^-3 / 2^e lose relative precision: 2^-25 / 2^e against a bound of 2^15 / 2^e, i.e. 2^-40 of the operand's
+//              range.  Absolute, so harmless for a GEMM operand -- not for the linear-attention feature maps Q' and K', which the
+//              reference also DIVIDES by: a head of them far below the bound keeps an exact fp32 denominator over a numerator of
+//              subnormal / zero planes.  Q' therefore takes a data-dependent exponent per row and head in the layer tail
+//              (tail_split.hip: apply_qscale; e_q is its floor).  K' in the K^T V epilogues (proj_ring.hip: ride_k,
+//              gemm_epilogue.h) still uses the static e_k alone: open, pinned by tests/test_gpu_attention_range.py.
+//              Measured against float64 with the hardware's own accumulation
 //              (tools/ubench/split_acc.py, profiles/r03_split_acc.txt): same normwise error as SplitBf3.
 //              The accumulators are in units of 2^(ea + ew); the kernels fold that exact factor into what follows (a
 //              LayerNorm of c z with eps c^2 equals the LayerNorm of z bit for bit), never into an extra rounding.

@@ -134,8 +134,8 @@ struct HeadOps {   // the per-cloud operands of one head's apply, as loaded (Q' 
 // SplitH2: the exact power-of-two factors of the kernel (all 1 / unused for SplitBf3)
 struct TailScales {
     float s_att;  // 2^e_att, folded into Z
-    float s_q;    // fp16 x 2 apply: 2^e_q, the scale of Q' = elu(q) + 1 <= 1 + the bound of q as an operand
-    float s_attq; // 2^(e_att - e_q): with the head's 2^-e_h what takes the apply's accumulator to the scaled attention output
+    int e_q;      // fp16 x 2 apply: the weight-derived exponent of Q' = elu(q) + 1 <= 1 + the bound of q -- the floor of the row scale t
+    int e_att;    // 2^(e_att - t - e_h) takes the apply's accumulator to the scaled attention output
     float c1;     // 2^(e_wm + e_att): unit of the merge accumulators
     float eps1;   // 1e-5 c1^2
     float s_m1;   // 2^e_m1, folded into gamma1 / beta1
@@ -298,14 +298,37 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
     V apA[2][NP], apB[2][NP];  // planes of att_h^T, the B operand of the merge GEMM: heads of even / odd index
     f32x16 aT;              // att_h^T tile of the head being applied
     bf16x8 qp[2][3];        // bf16 x 3 apply (SplitBf3 kernels; the fp16 kernels with T_APPLY_H2 = 0)
-    f16x8 qph[2][2];        // fp16 x 2 apply: the planes of Q' 2^e_q
+    f16x8 qph[2][2];        // fp16 x 2 apply: the planes of Q' 2^t
     float Zs = 0.f;
+    int tq = 0;             // fp16 x 2 apply: exponent t of the row and head being applied (apply_qscale)
 
     // ---- apply of one head (models/transformer.py:41-42), in pieces that ride inside the groups of another stage ----
+    // fp16 x 2: Q' is scaled PER ROW AND HEAD.  The weight-derived e_q bounds Q' from above only, and the reference divides by Q'
+    // (att = Q'.KV / (Q'.Ksum + 1e-6)): a head whose 32 Q' of a row all sit far below the bound (a head-wide negative q) had
+    // subnormal or zero planes while its denominator, formed from the fp32 Q', stayed exact -- attention 0 instead of ~|V|.  So
+    // t puts the largest Q' of the row's head into [2^14, 2^15) (kv_finalize_image's rule for e_h), never below e_q: 2^t is an
+    // exact power of two, and a row whose planes were normal under 2^e_q gives the old bits.  Two caps keep both factors finite
+    // normal floats (a larger t would make 2^t inf -- NaN planes -- or wrap its bits):
+    //   * t <= 127, 2^t itself.  Every fp32-normal Q' (>= 2^-126) times 2^127 is >= 2: its first plane is normal and its second
+    //     rounds to a step of 2^-24, 2^-25 of the value -- finer than the fp32 input's own rounding.  Only an fp32-subnormal Q'
+    //     (q < -87) loses bits, and the input has fewer than the planes keep.  Q' == 0 gives zero planes.
+    //   * t <= e_att - e_h + 126, 2^(e_att - t - e_h) folded into Z (>= 46 for every exponent tail_scales accepts): a row at this
+    //     cap has max Q' < 2^(14 - t), and with |KV| <= 2^(15 - e_h) its |Q'.KV S| / 1e-6 is below 2^(-72 - e_att) S -- under
+    //     2^-67 of the attention bound 2^(15 - e_att) for any S < 2^20: nothing next to the eps term, whatever its planes keep.
+    auto apply_qscale = [&](const f32x4 (&qb)[4]) {
+        float m = 0.f;  // Q' > 0 (elu + 1)
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) m = fmaxf(m, qb[a][k]);
+        m = fmaxf(m, __shfl_xor(m, 32));
+        const int hb = (int)(__float_as_uint(op.sc[0]) >> 23);  // 127 - e_h
+        tq = min(max(14 - ((int)(__float_as_uint(m) >> 23) - 127), sc.e_q), min(127, sc.e_att + hb - 1));
+    };
     auto apply_qsplit = [&](f32x4 (&qb)[4], int tile_tag, int s2) {  // 16-deep step s2 of Q' into its planes
         f32x4 lo = qb[2 * s2], hi = qb[2 * s2 + 1];
         if (T_ABLATE & 16) lo = hi = f32x4{(float)lane, 1.0f, 0.5f, (float)tile_tag};
-        if (APPLY_H2) split8s<SplitH2>(lo, hi, sc.s_q, qph[s2]);
+        if (APPLY_H2) split8s<SplitH2>(lo, hi, __uint_as_float((uint32_t)(tq + 127) << 23), qph[s2]);
         else split8<SplitBf3>(lo, hi, qp[s2]);
     };
     auto apply_mfma = [&](int s2) {
@@ -330,8 +353,8 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
         zp += __shfl_xor(zp, 32);
         Zs = 1.0f / (zp + 1e-6f);
         // exact powers of two: (aT * (Z 2^e)) * S == ((aT * Z) * S) 2^e bit for bit; the fp16 x 2 apply's accumulator is in units of
-        // 2^(e_h + e_q), so its Z also carries 2^-(e_h + e_q)
-        if (APPLY_H2) Zs *= sc.s_attq * op.sc[0];
+        // 2^(e_h + t), so its Z also carries 2^-(e_h + t)
+        if (APPLY_H2) Zs *= __uint_as_float((uint32_t)(sc.e_att - tq + (int)(__float_as_uint(op.sc[0]) >> 23)) << 23);
         else if (SP::SCALED) Zs *= sc.s_att;
     };
     auto apply_split_pair = [&](int k, V (&ap)[2][NP], float S) {  // elements 2k, 2k+1: (aT * Z) * S, then the operand split
@@ -345,6 +368,7 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
     };
     // the pieces of one apply as they ride in group g of a 16-group stage: operands consumed in groups 0-3
     auto apply_ride = [&](f32x4 (&qb)[4], int g, V (&ap)[2][NP], float S, int tile_tag) {
+        if (g == 0 && APPLY_H2) apply_qscale(qb);
         if (g == 0) apply_qsplit(qb, tile_tag, 0);
         if (g == 1) apply_qsplit(qb, tile_tag, 1);
         if (g == 1) apply_mfma(0);
@@ -1236,8 +1260,8 @@ bool tail_scales(const scream_tail_exps_t* ex, TailScales* sc) {
     if (e1 < -44 || e1 > 44 || e2 < -44 || e2 > 44 || eh < -100 || eh > 100) return false;  // c^2 and c^2 * var stay finite in fp32
     if (ex->e_q < -40 || ex->e_q > 40) return false;
     sc->s_att = exp2i(ex->e_att);
-    sc->s_q = exp2i(ex->e_q);
-    sc->s_attq = exp2i(ex->e_att - ex->e_q);
+    sc->e_q = ex->e_q;
+    sc->e_att = ex->e_att;
     sc->c1 = exp2i(e1);
     sc->eps1 = 1e-5f * exp2i(2 * e1);
     sc->s_m1 = exp2i(ex->e_m1);
@@ -1330,7 +1354,7 @@ extern "C" int scream_layer_tail_f32(const float* Q, const void* kv_image, const
     SCREAM_REQUIRE(x != y, SCREAM_EINVAL);  // the residual of a row is read twice, long after its neighbours were written
     // q_next (the image then has its eight query stages): fp16 splits only; it may be Q itself, never x or y
     SCREAM_REQUIRE(!q_next || (split != SCREAM_SPLIT_BF3 && q_next != x && q_next != y), SCREAM_EINVAL);
-    TailScales sc{1.f, 1.f, 1.f, 1.f, 1e-5f, 1.f, 1.f, 1.f, 1e-5f, 1.f, 1.f, 1.f, 1.f};
+    TailScales sc{1.f, 0, 0, 1.f, 1e-5f, 1.f, 1.f, 1.f, 1e-5f, 1.f, 1.f, 1.f, 1.f};
     if (split != SCREAM_SPLIT_BF3) SCREAM_REQUIRE(tail_scales(exps, &sc), SCREAM_EINVAL);
     const int64_t tiles = M / SCREAM_ROW_TILE;
     if (tiles == 0) return 0;

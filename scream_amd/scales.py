@@ -17,8 +17,13 @@ The bound fixes the exponent: e = floor(log2(2^15 / bound)).  On the HIGH side i
 gives headroom away: safe); on the LOW side it is NOT clamped -- a bound above 2^(15 - E_MIN) = 2^39 has no exponent in range
 that keeps the contract, so exp_for raises ScaleRangeError and the model routes such weights to the scale-free bf16 x 3 split
 (gemm_backend "x3"; scream_amd/model.py).  Values below 2^-3 / 2^e lose relative precision (the second fp16 plane goes
-subnormal), i.e. operand values more than 2^18 below their bound -- 2^-40 of the operand's range in absolute terms.  Weight
-matrices take e from their largest |element|.
+subnormal), i.e. operand values more than 2^18 below their bound -- 2^-40 of the operand's range in absolute terms.  That is
+harmless for a GEMM operand but NOT for the feature maps of linear attention: the reference divides by Q' and K'
+(att = Q'.KV / (Q'.Ksum + 1e-6)), so a head whose Q' or K' are all far below their bound would lose its whole numerator while
+the fp32 denominator stays exact.  e_q is therefore only the FLOOR of Q's scale: the layer tail scales Q' per (row, head) by the
+power of two that puts the row's largest Q' of the head into [2^14, 2^15) (csrc/tail_split.hip: apply_qscale).  K' in the K^T V
+epilogues still uses e_k alone (open: tests/test_gpu_attention_range.py pins it).  Weight matrices take e from their largest
+|element|.
 """
 from __future__ import annotations
 
