@@ -480,6 +480,41 @@ int scream_grad3(const float* w, const float* s, const float* center, const int3
 int scream_pe_embed(const float* xyz, const int32_t* tile_cloud, const float* center, const float* dim_t,
                     const float* emb_w, const float* emb_b, float* z, int64_t rows, void* stream);
 
+/* ---- Depth renderer of the training-time GAN loss (models/render.py:8-73, RegistrationRender; csrc/render.hip).
+ * For pair p and view v (rot [n_views, 9], row-major fp32 3x3 matrices R_v), every point of the pair's source cloud (packed
+ * rows s_row0[p] .. + s_len[p] of src) and target cloud (t_row0 / t_len of tgt) is rotated, X = R_v x; then
+ *   dmin, dmax = min / max of X_z over BOTH clouds (on the device; no host synchronisation),
+ *   pv_k = 1 - (X_k,z - dmin) / (dmax - dmin),
+ *   c_p = ((j - w/2 + 0.5) / (w/2), (i - w/2 + 0.5) / (w/2)) for pixel p = i w + j (row i, column j),
+ *   g_kp = exp(-rho^2 / 2 |X_k,xy - c_p|^2)  (rho^2 multiplies: exp(-288 d^2) at rho = 24; evaluated as one exp2),
+ *   img[p] = max_k pv_k g_kp over the side's own points (channel 0: source, channel 1: target),
+ * and writes imgs [n_pairs, n_views, 2, w, w] = (img - 0.5) / 0.5 with argmax [n_pairs, n_views, 2, w, w] (int32, the index of the
+ * selected point inside its cloud).  Rules the reference leaves open:
+ *   ties: the lowest point index within the side wins (torch on the CPU; torch on the GPU promises nothing);
+ *   zero pixels: where the maximum is exactly 0 the argmax is -1 and the pixel passes no gradient (its points' g underflowed);
+ *   flat views: dmax == dmin is 0 / 0 in the reference -- every pixel of both images of that view is NaN, argmax -1, no fault;
+ *   empty clouds: rejected by the Python layer (scream_amd/render.py), as PackedBatch does.
+ * Results are bitwise the same however many pairs share the call (the point ranges are split over blocks and merged with an
+ * integer atomicMax of (value, ~index) keys, which does not depend on the order).  w % 64 == 0 (the reference renders 64 x 64
+ * chunks), n_views >= 1, rho finite, n_pairs * n_views * 2 <= 65535.  max_s_len / max_t_len (host) bound the cloud lengths and
+ * size the grid; src_rows_total is the row count of src (it sizes the backward's part of the workspace).
+ * workspace: scream_render_workspace_bytes(n_pairs, n_views, w, src_rows_total) bytes, 16-byte aligned; it begins with the depth
+ * ranges, which scream_render_depth_bwd reads: hand the backward the forward's workspace, untouched. */
+int64_t scream_render_workspace_bytes(int32_t n_pairs, int32_t n_views, int32_t w, int64_t src_rows_total);
+int scream_render_depth(const float* src, const int32_t* s_row0, const int32_t* s_len, const float* tgt,
+                        const int32_t* t_row0, const int32_t* t_len, int32_t n_pairs, int32_t max_s_len, int32_t max_t_len,
+                        int64_t src_rows_total, const float* rot, int32_t n_views, int32_t w, float rho, float* imgs,
+                        int32_t* argmax, void* workspace, int64_t workspace_bytes, void* stream);
+/* Backward of the source images: dsrc[row] = sum over views (ascending) of R_v^T sum over the pixels p of the view's source image
+ * whose argmax is that point (raster order) of dimgs[p] do_p/dX, with do/dX_x = -2 rho^2 pv g (X_x - c_x) (same for y) and
+ * do/dX_z = -2 g / (dmax - dmin) (dmin, dmax constants, as the reference's .item() makes them).  The target channel of dimgs is
+ * not read (no caller differentiates the target).  Fixed-order sums, no float atomics: two identical calls give identical bits.
+ * Rows of src outside every source cloud are not written.  argmax and workspace: those of the scream_render_depth call. */
+int scream_render_depth_bwd(const float* src, const int32_t* s_row0, const int32_t* s_len, int32_t n_pairs, int32_t max_s_len,
+                            int64_t src_rows_total, const float* rot, int32_t n_views, int32_t w, float rho,
+                            const float* dimgs, const int32_t* argmax, void* workspace, int64_t workspace_bytes, float* dsrc,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@ SOURCES = {
     "nn_search.hip": ["-ffp-contract=off"],
     "kabsch.hip": ["-ffp-contract=off"],
     "icp_grid.hip": ["-ffp-contract=off"],
+    "render.hip": ["-ffp-contract=off"],
 }
 # SCREAM_HIPCC_EXTRA="file.hip:-flag,-flag;file2.hip:-flag": extra compiler flags per source (experiments; empty in the product)
 EXTRA_DEFINES = {}

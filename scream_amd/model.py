@@ -17,6 +17,7 @@ from torch import nn
 
 from . import _lib, ops, scales
 from .packing import PackedBatch
+from .render import RegistrationRender
 
 D_MODEL = 256
 NHEAD = 8
@@ -81,8 +82,8 @@ class PointTransformer(nn.Module):
             self.cross.append(_CrossParams(d_model))
         self.coor_mlp = nn.Sequential(nn.Conv1d(d_model, d_model, 1), nn.ReLU(), nn.Conv1d(d_model, d_model, 1),
                                       nn.ReLU(), nn.Conv1d(d_model, 3, 1))
-        # models/pointnet.py:36 builds a RegistrationRender here; it owns no parameters or buffers and is
-        # only used when get_imgs=True (training-time GAN loss) -- out of scope, see DESIGN.md.
+        # models/pointnet.py:36: the depth renderer of get_imgs=True (training-time GAN loss); no parameters, no buffers
+        self.generator = RegistrationRender(rho=24, w=64)
         self._packs = {}  # gemm backend -> _Pack: the weights in that backend's kernel layout (built on first use)
         self._ws = None
 
@@ -376,34 +377,32 @@ class PointTransformer(nn.Module):
     def _forward_train(self, src, tgt, src_center, s, get_imgs, get_transform, filter):
         assert src.shape[0] == 1, "batch size must 1"
         assert tgt.shape[0] == 1, "batch size must 1"
-        if get_imgs:
-            raise NotImplementedError("get_imgs=True (depth renderer for the training-time GAN loss, models/render.py) is out of scope")
         center = None if src_center is None else src_center.reshape(3)
         batch = PackedBatch.from_pairs([src[0].detach()], [tgt[0].detach()], [None if center is None else center.detach()])
         src_ = self.forward_packed_train(batch)[: src.shape[1]].unsqueeze(0)
+        # pointnet.py:62-65: the predicted source (normalised frame) and the raw target; differentiable in src_
+        imgs = self.generator(src_[0], tgt[0].detach()) if get_imgs else None
         transform = None
         if get_transform:
             from .geometry import register_from_prediction
             with torch.no_grad():
                 ref = tgt[0] if filter is None else filter[0]
                 transform = register_from_prediction(src[0], src_[0].detach(), ref, float(s), 0.075)
-        return src_, None, transform
+        return src_, imgs, transform
 
     def _forward_infer(self, src, tgt, src_center=None, s=1, get_imgs=False, get_transform=False, filter=None):
         assert src.shape[0] == 1, "batch size must 1"
         assert tgt.shape[0] == 1, "batch size must 1"
-        if get_imgs:
-            raise NotImplementedError("get_imgs=True (depth renderer for the training-time GAN loss, "
-                                      "models/render.py) is out of scope; every evaluate_* call passes False")
         center = None if src_center is None else src_center.reshape(3)
         batch = PackedBatch.from_pairs([src[0]], [tgt[0]], [center])
         src_ = self.forward_packed(batch)[: src.shape[1]].unsqueeze(0).clone()
+        imgs = self.generator(src_[0], tgt[0]) if get_imgs else None  # pointnet.py:62-65
         transform = None
         if get_transform:  # pointnet.py:66-74: NN against `filter` at 0.075, Kabsch in the normalised frame
             from .geometry import register_from_prediction
             ref = tgt[0] if filter is None else filter[0]
             transform = register_from_prediction(src[0], src_[0], ref, float(s), 0.075)
-        return src_, None, transform
+        return src_, imgs, transform
 
     def loss(self, src_pred, src_pcd, rot_gt, trans_gt):
         """models/pointnet.py:93-99 (L1 point loss; metric bookkeeping, not a hot-path kernel)."""
@@ -432,6 +431,7 @@ class DEMTransformer(PointTransformer):
             self.cross.append(_CrossParams(d_model))
         self.coor_mlp = nn.Sequential(nn.Conv1d(d_model, d_model, 1), nn.ReLU(), nn.Conv1d(d_model, d_model, 1),
                                       nn.ReLU(), nn.Conv1d(d_model, 3, 1))
+        self.generator = RegistrationRender(rho=24, w=64, view="single")  # models/pointnet.py:133
         self._packs = {}
         self._ws = None
 
@@ -448,12 +448,11 @@ class DEMTransformer(PointTransformer):
     def forward(self, dsm, dem_coarse, get_imgs=False):
         assert dsm.shape[0] == 1, "batch size must 1"
         assert dem_coarse.shape[0] == 1, "batch size must 1"
-        if get_imgs:
-            raise NotImplementedError("get_imgs=True (depth renderer, models/render.py) is out of scope")
         zero = torch.zeros(3, device=dsm.device)  # both clouds embed their raw coordinates (pointnet.py:138-139)
         batch = PackedBatch.from_pairs([dsm[0]], [dem_coarse[0]], [zero])
         dem_ = self.forward_packed(batch)[: dsm.shape[1]].unsqueeze(0).clone()
-        return dem_, None
+        imgs = self.generator(dem_[0], dem_coarse[0]) if get_imgs else None  # pointnet.py:156-159
+        return dem_, imgs
 
     def forward_batch(self, dsms, dems, centers=None):
         zero = torch.zeros(3, device=dsms[0].device)

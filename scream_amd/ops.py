@@ -360,6 +360,44 @@ def nn_search(query: torch.Tensor, ref: torch.Tensor, q_row0, q_len, r_row0, r_l
     return idx, dmin, valid
 
 
+def render_workspace(n_pairs: int, n_views: int, w: int, src_rows_total: int, device) -> torch.Tensor:
+    """Scratch of render_depth; render_depth_bwd needs the forward's, untouched (it begins with the depth ranges)."""
+    need = _lib.load().scream_render_workspace_bytes(n_pairs, n_views, w, src_rows_total)
+    if need < 0:
+        raise _lib.ScreamHipError("scream_render_workspace_bytes(%d, %d, %d, %d): invalid argument" % (n_pairs, n_views, w, src_rows_total))
+    return torch.empty(max(need, 16), device=device, dtype=torch.uint8)
+
+
+def render_depth(src: torch.Tensor, s_row0, s_len, tgt: torch.Tensor, t_row0, t_len, max_s_len: int, max_t_len: int,
+                 rot: torch.Tensor, w: int, rho: float, workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Packed depth renderer (scream_render_depth): src / tgt packed [rows,3], per-pair row0 / len int32 device arrays, rot
+    [V,3,3] fp32 on the device.  Returns (imgs [B,V,2,w,w] fp32, argmax [B,V,2,w,w] int32)."""
+    n_pairs, V = s_row0.shape[0], rot.shape[0]
+    dev = src.device
+    if workspace is None:
+        workspace = render_workspace(n_pairs, V, w, src.shape[0], dev)
+    imgs = torch.empty(n_pairs, V, 2, w, w, device=dev, dtype=torch.float32)
+    argmax = torch.empty(n_pairs, V, 2, w, w, device=dev, dtype=torch.int32)
+    check(_lib.load().scream_render_depth(_p(src), _p(s_row0, torch.int32), _p(s_len, torch.int32), _p(tgt), _p(t_row0, torch.int32),
+                                          _p(t_len, torch.int32), n_pairs, int(max_s_len), int(max_t_len), src.shape[0],
+                                          _p(rot.reshape(V, 9)), V, int(w), float(rho), _p(imgs), _p(argmax, torch.int32),
+                                          _p(workspace, torch.uint8), workspace.numel(), _stream()), "scream_render_depth")
+    return imgs, argmax
+
+
+def render_depth_bwd(dimgs: torch.Tensor, argmax: torch.Tensor, src: torch.Tensor, s_row0, s_len, max_s_len: int,
+                     rot: torch.Tensor, w: int, rho: float, workspace: torch.Tensor) -> torch.Tensor:
+    """Gradient of the source images with respect to the packed source rows (scream_render_depth_bwd); argmax and workspace are
+    those of the render_depth call.  Returns dsrc [rows,3] (zero on rows outside every source cloud)."""
+    n_pairs, V = s_row0.shape[0], rot.shape[0]
+    dsrc = torch.zeros(src.shape[0], 3, device=src.device, dtype=torch.float32)
+    check(_lib.load().scream_render_depth_bwd(_p(src), _p(s_row0, torch.int32), _p(s_len, torch.int32), n_pairs, int(max_s_len),
+                                              src.shape[0], _p(rot.reshape(V, 9)), V, int(w), float(rho), _p(dimgs),
+                                              _p(argmax, torch.int32), _p(workspace, torch.uint8), workspace.numel(), _p(dsrc),
+                                              _stream()), "scream_render_depth_bwd")
+    return dsrc
+
+
 def kabsch_corr(src, ref, src_row0, src_len, ref_row0, idx, valid, s, c) -> Tuple[torch.Tensor, torch.Tensor]:
     """Returns (T [n_pairs,4,4], n_corr int32 [n_pairs])."""
     n_pairs = s.shape[0]
