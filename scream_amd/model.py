@@ -359,9 +359,10 @@ class PointTransformer(nn.Module):
         return getattr(self, "_grad_train", False) and torch.is_grad_enabled()
 
     def forward_packed_train(self, batch: PackedBatch) -> torch.Tensor:
-        """forward_packed's packed src_pred [rows_src, 3] with a grad_fn: its backward writes the gradient of every parameter."""
-        if type(self) is not PointTransformer:
-            raise NotImplementedError("training is implemented for PointTransformer only")
+        """forward_packed's packed src_pred [rows_src, 3] (DEMTransformer: dem_pred) with a grad_fn: its backward writes the
+        gradient of every parameter."""
+        if type(self) not in (PointTransformer, DEMTransformer):
+            raise NotImplementedError("training is implemented for PointTransformer and DEMTransformer only")
         from . import train as _train
         return _train.apply(self, batch)
 
@@ -444,8 +445,26 @@ class DEMTransformer(PointTransformer):
     def _stem_tgt_modules(self) -> Optional[List[_MHAParams]]:
         return list(self.stem_dem)
 
-    @torch.no_grad()
     def forward(self, dsm, dem_coarse, get_imgs=False):
+        """models/pointnet.py:134-160.  Inference unless train() was called and grad mode is on: then dem_ (and imgs) carry
+        a grad_fn (train_open_gf.py's loop).  Batched training: forward_packed_train(PackedBatch.from_pairs(dsms, dem_coarses,
+        [zeros(3)] * B))."""
+        if self._trains():
+            return self._forward_train(dsm, dem_coarse, get_imgs)
+        with torch.no_grad():
+            return self._forward_infer(dsm, dem_coarse, get_imgs)
+
+    def _forward_train(self, dsm, dem_coarse, get_imgs=False):
+        assert dsm.shape[0] == 1, "batch size must 1"
+        assert dem_coarse.shape[0] == 1, "batch size must 1"
+        zero = torch.zeros(3, device=dsm.device)  # both clouds embed their raw coordinates (pointnet.py:138-139)
+        batch = PackedBatch.from_pairs([dsm[0].detach()], [dem_coarse[0].detach()], [zero])
+        dem_ = self.forward_packed_train(batch)[: dsm.shape[1]].unsqueeze(0)
+        # pointnet.py:156-159: differentiable in dem_; the coarse DEM is data
+        imgs = self.generator(dem_[0], dem_coarse[0].detach()) if get_imgs else None
+        return dem_, imgs
+
+    def _forward_infer(self, dsm, dem_coarse, get_imgs=False):
         assert dsm.shape[0] == 1, "batch size must 1"
         assert dem_coarse.shape[0] == 1, "batch size must 1"
         zero = torch.zeros(3, device=dsm.device)  # both clouds embed their raw coordinates (pointnet.py:138-139)

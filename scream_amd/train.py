@@ -1,12 +1,16 @@
-"""Training of PointTransformer: an fp32 forward that keeps its activations, and the backward pass on the HIP kernels of
-csrc/backward.hip, wired into torch.autograd.
+"""Training of PointTransformer and DEMTransformer: an fp32 forward that keeps its activations, and the backward pass on the
+HIP kernels of csrc/backward.hip, wired into torch.autograd.
 
 The forward is the unfused fp32 chain of the existing kernels (scream_pe_embed + scream_ln_fwd, scream_gemm_f32 with the
-elu + 1 / relu / bias + relu epilogues, scream_kv_reduce, scream_attn_apply, scream_ln_fwd, scream_coor_head).  The stem runs
-once over ALL packed rows (source and target clouds share its weights, models/pointnet.py:50-52), so its weight gradients are
-single sums over both applications.  The backward runs the chain in reverse: data gradients dX = dY W are scream_gemm_f32 on
-transposed weights (scream_transpose_f32), weight gradients scream_gemm_wgrad_f32, LayerNorm scream_ln_bwd, the linear attention
-scream_attn_bwd.  Every reduction is a fixed-order sum, so two identical calls give bitwise identical gradients.
+elu + 1 / relu / bias + relu epilogues, scream_kv_reduce, scream_attn_apply, scream_ln_fwd, scream_coor_head).  The layers
+come from the model's own layer lists (_layer_prefixes).  PointTransformer's stem runs once over ALL packed rows (source and
+target clouds share its weights, models/pointnet.py:50-52), so its weight gradients are single sums over both applications.
+DEMTransformer's stem runs twice per layer (models/pointnet.py:143-145): stem_dsm.i on the source rows [0, rows_src) and
+clouds [0, B), stem_dem.i on the target rows [rows_src, rows_total) and clouds [B, 2B); each side's weights get their
+gradients from their own rows only (stem_dem's reach it through the cross layers' key/value path).  The backward runs the
+chain in reverse: data gradients dX = dY W are scream_gemm_f32 on transposed weights (scream_transpose_f32), weight
+gradients scream_gemm_wgrad_f32, LayerNorm scream_ln_bwd, the linear attention scream_attn_bwd.  Every reduction is a
+fixed-order sum, so two identical calls give bitwise identical gradients.
 
 Memory budget: per packed row and block application the forward keeps x (1 KB), Q'|K'|V (3 KB), the attention output (1 KB),
 the merge output (1 KB), the LayerNorm1 output (1 KB), the FFN hidden layer (4 KB), the FFN output (1 KB) and the LayerNorm
@@ -16,7 +20,7 @@ A 5 k + 5 k point pair at 6 + 6 layers (stem on 10 k rows, cross stage on 5 k ro
 """
 from __future__ import annotations
 
-from typing import Dict, List
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -52,9 +56,9 @@ def wgrad(dY: torch.Tensor, X: torch.Tensor, dW: torch.Tensor, colsum: torch.Ten
     return dW
 
 
-def ln_fwd(a: torch.Tensor, b, gamma, beta):
+def ln_fwd(a: torch.Tensor, b, gamma, beta, out: torch.Tensor = None):
     rows = a.shape[0]
-    y = torch.empty(rows, D_MODEL, device=a.device, dtype=torch.float32)
+    y = torch.empty(rows, D_MODEL, device=a.device, dtype=torch.float32) if out is None else out
     mean = torch.empty(rows, device=a.device, dtype=torch.float32)
     rstd = torch.empty(rows, device=a.device, dtype=torch.float32)
     check(_lib.load().scream_ln_fwd(_p(a), _p(b), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), rows, _stream()), "scream_ln_fwd")
@@ -111,9 +115,11 @@ def _cat(*ws) -> torch.Tensor:
     return torch.cat([w for w in ws], dim=0).contiguous()
 
 
-def _block_fwd(P, prefix: str, x: torch.Tensor, t, batch: PackedBatch, r0: int, cb: int, n: int) -> (torch.Tensor, _Layer):
+def _block_fwd(P, prefix: str, x: torch.Tensor, t, batch: PackedBatch, r0: int, cb: int, n: int,
+               out: torch.Tensor = None) -> (torch.Tensor, _Layer):
     """One block (models/transformer.py:74-90) on rows [r0, r0 + x.shape[0]) whose clouds are [cb, cb + n).  t: the target
-    features (rows batch.rows_src ..) of a cross layer, None for a self layer."""
+    features (rows batch.rows_src ..) of a cross layer, None for a self layer.  out: where the block output goes (default:
+    a new tensor)."""
     w = lambda s: _w(P, prefix + s)
     L = _Layer()
     L.cross, L.prefix, L.r0, L.rows, L.cb, L.n, L.x, L.t = t is not None, prefix, r0, x.shape[0], cb, n, x, t
@@ -135,7 +141,7 @@ def _block_fwd(P, prefix: str, x: torch.Tensor, t, batch: PackedBatch, r0: int, 
     L.m1, *L.s1 = ln_fwd(L.msg, x, w("norm1.weight"), w("norm1.bias"))
     L.hid = gemm_f32(L.m1, w("mlp.0.weight").contiguous(), EPI_RELU)
     L.ffn = gemm_f32(L.hid, w("mlp.2.weight").contiguous())
-    y, *L.s2 = ln_fwd(L.ffn, x, w("norm2.weight"), w("norm2.bias"))
+    y, *L.s2 = ln_fwd(L.ffn, x, w("norm2.weight"), w("norm2.bias"), out)
     return y, L
 
 
@@ -184,9 +190,24 @@ def _block_bwd(P, G, L: _Layer, dy: torch.Tensor, batch: PackedBatch, dt) -> Non
     add_(dy, dffn)
 
 
-def _layer_prefixes(net) -> List[str]:
-    pre = ["stem.%d." % i for i in range(net.self_layer_num)]
-    return pre + [("cross.%d." % j) if j % 2 == 0 else ("cross.%d.layer." % j) for j in range(2 * net.cross_layer_num)]
+def _layer_prefixes(net) -> Tuple[List[str], Optional[List[str]], List[str]]:
+    """(stem, stem_tgt, cross): the state_dict prefixes of the model's layer lists (PointTransformer._layer_modules /
+    _stem_tgt_modules).  stem_tgt is None when one stem serves both clouds (PointTransformer); for DEMTransformer stem holds
+    stem_dsm.i (source side) and stem_tgt stem_dem.i (target side)."""
+    names = {id(m): n + "." for n, m in net.named_modules()}
+    mods, tgt = net._layer_modules(), net._stem_tgt_modules()
+    ns = net.self_layer_num
+    return ([names[id(m)] for m in mods[:ns]], None if tgt is None else [names[id(m)] for m in tgt],
+            [names[id(m)] for m in mods[ns:]])
+
+
+def _stem_passes(net, batch: PackedBatch) -> List[List[Tuple[str, int, int, int, int]]]:
+    """Per stem layer, the block applications (prefix, first row, rows, first cloud, clouds) -- csrc/forward.hip's stem split."""
+    stem, stem_tgt, _ = _layer_prefixes(net)
+    rs, rt, B = batch.rows_src, batch.rows_total, batch.n_pairs
+    if stem_tgt is None:  # pointnet.py:50-52: both clouds of every pair in one pass (shared weights)
+        return [[(p, 0, rt, 0, 2 * B)] for p in stem]
+    return [[(p, 0, rs, 0, B), (q, rs, rt - rs, B, B)] for p, q in zip(stem, stem_tgt)]  # pointnet.py:143-145
 
 
 def forward_saving(net, batch: PackedBatch):
@@ -202,21 +223,23 @@ def forward_saving(net, batch: PackedBatch):
                                       _p(_w(P, "embedding.bias")), _p(z0), rt, _stream()), "scream_pe_embed")
     f, *s0 = ln_fwd(z0, None, _w(P, "pre_norm.weight"), _w(P, "pre_norm.bias"))
     layers = []
-    prefixes = _layer_prefixes(net)
-    ns = net.self_layer_num
-    for i in range(ns):  # stem: both clouds of every pair in one pass (shared weights)
-        f, L = _block_fwd(P, prefixes[i], f, None, batch, 0, 0, 2 * B)
-        layers.append(L)
+    for passes in _stem_passes(net, batch):
+        y = torch.empty(rt, D_MODEL, device=dev, dtype=torch.float32)  # every application writes its own rows
+        for prefix, r0, rows, cb, n in passes:
+            _, L = _block_fwd(P, prefix, f[r0:r0 + rows], None, batch, r0, cb, n, out=y[r0:r0 + rows])
+            layers.append(L)
+        f = y
+    n_stem = len(layers)
     tf = f[rs:]
     sf = f[:rs]
-    for j in range(2 * net.cross_layer_num):
-        sf, L = _block_fwd(P, prefixes[ns + j], sf, tf if j % 2 else None, batch, 0, 0, B)
+    for j, prefix in enumerate(_layer_prefixes(net)[2]):
+        sf, L = _block_fwd(P, prefix, sf, tf if j % 2 else None, batch, 0, 0, B)
         layers.append(L)
     c = lambda k: _w(P, "coor_mlp.%d" % k + ".weight")[:, :, 0].contiguous()
     h1 = gemm_f32(sf, c(0), EPI_BIAS_RELU, bias=_w(P, "coor_mlp.0.bias"))
     h2 = gemm_f32(h1, c(2), EPI_BIAS_RELU, bias=_w(P, "coor_mlp.2.bias"))
     out = ops.coor_head(h2, c(4), _w(P, "coor_mlp.4.bias"))
-    return out, dict(z0=z0, s0=s0, layers=layers, sf=sf, h1=h1, h2=h2)
+    return out, dict(z0=z0, s0=s0, layers=layers, n_stem=n_stem, sf=sf, h1=h1, h2=h2)
 
 
 def backward(net, batch: PackedBatch, saved, dout: torch.Tensor) -> List[torch.Tensor]:
@@ -239,12 +262,11 @@ def backward(net, batch: PackedBatch, saved, dout: torch.Tensor) -> List[torch.T
     dF = torch.zeros(rt, D_MODEL, device=dev, dtype=torch.float32)  # gradient of the features of all rows
     gemm_f32(dh1, transpose(c(0)), out=dF[:rs])
     del dh1, dh2
-    layers = saved["layers"]
-    ns = net.self_layer_num
-    for L in reversed(layers[ns:]):  # cross stage: source rows; the target features collect every cross layer's gradient
+    layers, n_stem = saved["layers"], saved["n_stem"]
+    for L in reversed(layers[n_stem:]):  # cross stage: source rows; the target features collect every cross layer's gradient
         _block_bwd(P, G, L, dF[:rs], batch, dF[rs:])
-    for L in reversed(layers[:ns]):
-        _block_bwd(P, G, L, dF, batch, None)
+    for L in reversed(layers[:n_stem]):  # stem: each application on its own rows (all rows for one shared stem)
+        _block_bwd(P, G, L, dF[L.r0:L.r0 + L.rows], batch, None)
     # pre_norm and the embedding (models/pointnet.py:45-48); the position embedding has no parameters
     dz0 = torch.empty(rt, D_MODEL, device=dev, dtype=torch.float32)
     z0, (m0, r0) = saved["z0"], saved["s0"]
@@ -254,8 +276,8 @@ def backward(net, batch: PackedBatch, saved, dout: torch.Tensor) -> List[torch.T
 
 
 class PointTransformerFn(torch.autograd.Function):
-    """src_pred (packed [rows_src, 3]) = PointTransformer(batch) with the HIP backward.  The parameters are inputs so that
-    autograd routes their gradients into param.grad."""
+    """src_pred (packed [rows_src, 3]) = PointTransformer(batch) (DEMTransformer: dem_pred) with the HIP backward.  The
+    parameters are inputs so that autograd routes their gradients into param.grad."""
 
     @staticmethod
     def forward(ctx, net, batch, *params):
@@ -266,7 +288,7 @@ class PointTransformerFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         if ctx.saved is None:
-            raise RuntimeError("PointTransformer's training graph was already freed by an earlier backward")
+            raise RuntimeError("the model's training graph was already freed by an earlier backward")
         grads = backward(ctx.net, ctx.batch, ctx.saved, dout)
         ctx.saved = None
         return (None, None) + tuple(grads)

@@ -1,0 +1,338 @@
+"""DEMTransformer training (scream_amd/train.py with separate stems, csrc/backward.hip) against float64: the gradients of every
+parameter against the CPU oracle under torch autograd, the per-side stem rule, the self-attention kernels on the target side,
+batching, determinism, the reference's train_open_gf.py loop, the renderer's images in training and the untouched inference
+path.  Needs an MI355X: run with `pytest -m gpu`."""
+
+import numpy as np
+import pytest
+import torch
+
+import render_ref as RR
+from oracle import scream_ref as O
+from scream_amd import _lib, ops, train
+from scream_amd.evaluate_open_gf import SyntheticDEM
+from scream_amd.packing import PackedBatch
+from scream_amd.render import rotation_matrix, view_eulers
+from scream_amd.synthetic import make_state_dict
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+FLOOR = 5e-6  # the fixed floor of the "<= 2 x the fp32 path's error" rule
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _require_gpu_and_native_lib():
+    assert torch.cuda.is_available(), "pytest -m gpu needs the MI355X"
+    _lib.load()
+
+
+def rel(a, b):
+    a, b = a.double().cpu(), b.double().cpu()
+    return (torch.linalg.norm(a - b) / max(torch.linalg.norm(b).item(), 1e-300)).item()
+
+
+def terrain(seed, points):
+    """One seeded OpenGF-like sample: dsm [1,N,3], dem_coarse [1,M,3], dem [1,N,3] (CPU, divided by 50)."""
+    dsm, coarse, dem, _ = SyntheticDEM(1, seed, points)[0]
+    return dsm[None], coarse[None], dem[None]
+
+
+def l1(pred, dem):
+    """models/pointnet.py:162-166."""
+    return torch.mean(torch.sum(torch.abs(pred - dem), dim=-1), dim=1).mean(dim=0)
+
+
+def oracle_grads(sd, dsm, coarse, dem, dtype):
+    sdx = {k: v.to(dtype).requires_grad_() for k, v in sd.items()}
+    loss = l1(O.dem_transformer_forward(dsm.to(dtype), coarse.to(dtype), sdx), dem.to(dtype))
+    loss.backward()
+    return loss.item(), {k: v.grad for k, v in sdx.items()}
+
+
+def build_dem(seed, ns, nc, sd=None):
+    from scream_amd.model import DEMTransformer
+    net = DEMTransformer(256, ns, nc)
+    net.load_state_dict(make_state_dict(seed, 256, ns, nc, dem=True) if sd is None else sd)
+    return net.to(DEV)
+
+
+def gpu_grads(net, dsm, coarse, dem):
+    net.train()
+    net.zero_grad(set_to_none=True)
+    dem_, imgs = net(dsm.to(DEV), coarse.to(DEV), False)
+    assert dem_.grad_fn is not None and imgs is None
+    loss = net.loss(dem_, dem.to(DEV))
+    loss.backward()
+    return loss.item(), {n: p.grad.detach().cpu() for n, p in net.named_parameters()}
+
+
+def check_rule(g, g64, g32, ratio, floor):
+    bad = []
+    for k in g64:
+        e, e32 = rel(g[k], g64[k]), rel(g32[k], g64[k])
+        if not e <= max(ratio * e32, floor):
+            bad.append((k, e, e32))
+    return bad
+
+
+# ------------------------------------------------------------------------------------- model gradients
+# (ns, nc, points, ratio, floor): the rules of test_gpu_train.py::test_model_gradients_against_float64 -- 2 x the fp32 CPU
+# oracle's error (floor 5e-6) for one block per stage, 4 x / 5e-4 for the deeper models ("Training").
+@pytest.mark.parametrize("ns,nc,points,ratio,floor", [(1, 1, 700, 2, FLOOR), (2, 2, 690, 4, 5e-4), (6, 6, 2000, 4, 5e-4)])
+def test_model_gradients_against_float64(ns, nc, points, ratio, floor):
+    sd = make_state_dict(30 + ns, 256, ns, nc, dem=True)
+    dsm, coarse, dem = terrain(ns, points)
+    assert dsm.shape[1] % 128 != 0
+    loss64, g64 = oracle_grads(sd, dsm, coarse, dem, torch.float64)
+    _, g32 = oracle_grads(sd, dsm, coarse, dem, torch.float32)
+    net = build_dem(30 + ns, ns, nc)
+    loss, g = gpu_grads(net, dsm, coarse, dem)
+    assert len(g) == len(sd) and ((ns, nc) != (6, 6) or len(sd) == 250)
+    bad = check_rule(g, g64, g32, ratio, floor)
+    assert not bad, bad
+    # the training forward's loss against the inference path's and float64's
+    net.eval()
+    with torch.no_grad():
+        dem_, _ = net(dsm.to(DEV), coarse.to(DEV))
+        loss_inf = net.loss(dem_, dem.to(DEV)).item()
+    assert abs(loss - loss_inf) <= 1e-5 * abs(loss_inf)
+    assert abs(loss - loss64) <= 1e-5 * abs(loss64)
+
+
+def test_stem_gradients_split_per_side():
+    """A PointTransformer and a DEMTransformer with stem_dsm = stem_dem = stem and zero centres compute the same function; the
+    shared stem's gradient is the sum of the two sides'.  Each side on its own must also match float64 with the two stems
+    held apart, which a swapped or shared stem would not."""
+    from scream_amd.model import PointTransformer
+    ns, nc = 2, 2
+    sd_p = make_state_dict(40, 256, ns, nc)
+    sd_d = {}
+    for k, v in sd_p.items():
+        if k.startswith("stem."):
+            sd_d["stem_dsm." + k[5:]] = v.clone()
+            sd_d["stem_dem." + k[5:]] = v.clone()
+        else:
+            sd_d[k] = v.clone()
+    pnet = PointTransformer(256, ns, nc)
+    pnet.load_state_dict(sd_p)
+    pnet = pnet.to(DEV).train()
+    dnet = build_dem(0, ns, nc, sd_d).train()
+    dsm, coarse, dem = terrain(41, 650)
+    zero = torch.zeros(3, device=DEV)
+    grads = []
+    for net in (pnet, dnet):
+        net.zero_grad(set_to_none=True)
+        batch = PackedBatch.from_pairs([dsm[0].to(DEV)], [coarse[0].to(DEV)], [zero])
+        pred = net.forward_packed_train(batch)[: dsm.shape[1]][None]
+        l1(pred, dem.to(DEV)).backward()
+        grads.append({n: p.grad.detach().cpu() for n, p in net.named_parameters()})
+    gp, gd = grads
+    assert len(gd) == len(gp) + len([k for k in gp if k.startswith("stem.")])
+    bad = []
+    for k in gp:
+        if k.startswith("stem."):
+            a, b = gd["stem_dsm." + k[5:]], gd["stem_dem." + k[5:]]
+            if not rel(a + b, gp[k]) <= 1e-5:
+                bad.append((k, rel(a + b, gp[k])))
+            if not rel(a, b) > 1e-2:  # both sides carry their own, different, gradient
+                bad.append((k, "sides agree", rel(a, b)))
+        elif not rel(gd[k], gp[k]) <= 1e-5:
+            bad.append((k, rel(gd[k], gp[k])))
+    assert not bad, bad
+    _, g64 = oracle_grads(sd_d, dsm, coarse, dem, torch.float64)
+    _, g32 = oracle_grads(sd_d, dsm, coarse, dem, torch.float32)
+    bad = check_rule(gd, g64, g32, 4, 5e-4)
+    assert not bad, bad
+
+
+# ------------------------------------------------------------------------------------- kernels on the target side
+def _attn64(q, k, v):
+    """models/transformer.py:17-44 on one (query cloud, key cloud) pair, all heads: q [L,256], k/v [S,256] pre-activation."""
+    return O.linear_attention(q.view(1, -1, 8, 32), k.view(1, -1, 8, 32), v.view(1, -1, 8, 32)).view(-1, 256)
+
+
+def test_target_side_self_attention_against_float64():
+    """The self layer of stem_dem: rows [rows_src, rows_total), clouds [B, 2B), every pointer and row base offset by
+    rows_src, as train._block_fwd / _block_bwd pass them."""
+    rng = np.random.default_rng(50)
+    src_len, tgt_len = [300, 1, 129], [129, 1, 257]
+    B = 3
+    lens, row0, rs, rt, tile_cloud, max_chunks = PackedBatch.layout(src_len, tgt_len)
+    batch = PackedBatch(B, src_len, tgt_len, row0, lens, rs, rt, max_chunks, torch.zeros(rt, 3, device=DEV),
+                        torch.zeros(2 * B, 3, device=DEV), torch.from_numpy(tile_cloud).to(DEV), torch.from_numpy(row0).to(DEV),
+                        torch.from_numpy(lens).to(DEV))
+    pre = torch.from_numpy(rng.standard_normal((rt, 768)).astype(np.float32) * 0.7)  # q | k | v before elu + 1
+    dO = torch.from_numpy(rng.standard_normal((rt, 256)).astype(np.float32))
+    for i in range(2 * B):  # padded query rows carry no gradient
+        dO[row0[i] + lens[i]:row0[i] + (lens[i] + 127) // 128 * 128] = 0
+    elu1 = lambda t: torch.nn.functional.elu(t) + 1
+    qkv = torch.cat([elu1(pre[:, :512]), pre[:, 512:]], 1)[rs:].contiguous().to(DEV)  # the target rows only, row 0 = rs
+    R = rt - rs
+    kv = ops.kv_reduce(qkv[:, 256:], qkv[:, 512:], 768, rs, batch.cloud_row0, batch.cloud_len, B, B, max_chunks, 2 * B)
+    att = ops.attn_apply(qkv, 768, kv, batch.tile_cloud[rs // 128:], 0, batch.cloud_len, R)
+    dq = torch.full((R, 256), 7.0, device=DEV)
+    dkv = torch.full((R, 512), 7.0, device=DEV)
+    dOd = dO[rs:].contiguous().to(DEV)
+    train.attn_bwd(qkv.data_ptr(), 768, R, rs, att, dOd, qkv.data_ptr() + 256 * 4, qkv.data_ptr() + 512 * 4, 768, R, rs, kv, batch,
+                   B, B, 0, dq.data_ptr(), 256, dkv.data_ptr(), dkv.data_ptr() + 256 * 4, 512)
+    pre64 = pre.double().requires_grad_()
+    outs, want_att = [], torch.zeros(R, 256, dtype=torch.float64)
+    for c in range(B, 2 * B):
+        sl = slice(row0[c], row0[c] + lens[c])
+        o = _attn64(pre64[sl, :256], pre64[sl, 256:512], pre64[sl, 512:])
+        want_att[row0[c] - rs:row0[c] - rs + lens[c]] = o.detach()
+        outs.append((o * dO[sl].double()).sum())
+    sum(outs).backward()
+    real = torch.zeros(R, dtype=torch.bool)
+    for c in range(B, 2 * B):
+        real[row0[c] - rs:row0[c] - rs + lens[c]] = True
+    assert rel(att.cpu()[real], want_att[real]) < 1e-5, rel(att.cpu()[real], want_att[real])
+    g = pre64.grad[rs:]
+    assert rel(dq.cpu(), g[:, :256]) < 2e-5, rel(dq.cpu(), g[:, :256])
+    assert rel(dkv.cpu(), g[:, 256:]) < 2e-5, rel(dkv.cpu(), g[:, 256:])
+    assert (dq.cpu()[~real] == 0).all() and (dkv.cpu()[~real] == 0).all()  # padded rows: zero gradient
+    assert torch.isfinite(att).all()
+
+
+# ------------------------------------------------------------------------------------- batching
+def test_batched_gradients_are_the_mean_of_single_samples_and_deterministic():
+    ns, nc = 2, 2
+    sd = make_state_dict(60, 256, ns, nc, dem=True)
+    net = build_dem(60, ns, nc).train()
+    samples = [terrain(61 + i, n) for i, n in enumerate((300, 129, 520))]
+    single = [gpu_grads(net, *s)[1] for s in samples]
+    mean = {k: sum(g[k] for g in single) / 3 for k in sd}
+    runs = []
+    for _ in range(2):
+        net.zero_grad(set_to_none=True)
+        zero = torch.zeros(3, device=DEV)
+        batch = PackedBatch.from_pairs([s[0][0].to(DEV) for s in samples], [s[1][0].to(DEV) for s in samples], [zero] * 3)
+        pred = net.forward_packed_train(batch)
+        torch.stack([net.loss(x[None], s[2].to(DEV)) for x, s in zip(batch.unpack_src(pred), samples)]).mean().backward()
+        runs.append({n: p.grad.detach().cpu().clone() for n, p in net.named_parameters()})
+    for k in sd:
+        assert torch.equal(runs[0][k], runs[1][k]), "gradient of %s differs between two identical calls" % k
+    o64 = [oracle_grads(sd, *s, torch.float64)[1] for s in samples]
+    o32 = [oracle_grads(sd, *s, torch.float32)[1] for s in samples]
+    bad = []
+    for k in sd:
+        want = sum(g[k] for g in o64) / 3
+        e32 = rel(sum(g[k] for g in o32) / 3, want)
+        if not rel(runs[0][k], want) <= max(4 * e32, 5e-4):
+            bad.append((k, rel(runs[0][k], want), e32))
+        if not rel(runs[0][k], mean[k]) <= 1e-5:
+            bad.append((k, "vs mean of single samples", rel(runs[0][k], mean[k])))
+    assert not bad, bad
+
+
+# ------------------------------------------------------------------------------------- the reference's training loop
+def test_reference_training_loop_runs_and_learns():
+    """train_open_gf.py:79-116 with use_GAN=False: net.train(); net(dsm, dem_coarse, False); net.loss; backward; Adam.step()."""
+    from scream_amd.model import DEMTransformer
+    net = build_dem(70, 1, 1)
+    opt = torch.optim.Adam(net.parameters(), lr=2e-4)
+    dsm, coarse, dem = (t.to(DEV) for t in terrain(71, 600))
+    losses = []
+    for step in range(20):
+        net.train()
+        dem_pred, _ = net(dsm, coarse, False)
+        loss = net.loss(dem_pred, dem)
+        opt.zero_grad()
+        loss.backward()
+        grads = [p.grad for p in net.parameters()]
+        assert len(grads) == len(list(net.state_dict())) and all(g is not None and torch.isfinite(g).all() for g in grads)
+        opt.step()
+        losses.append(loss.item())
+    assert losses[-1] < losses[0], losses
+    # the inference images were rebuilt after the steps: eval() of the trained model equals, bit for bit, a fresh model
+    # loaded with its state_dict (evaluate() inside train_open_gf.py takes this path)
+    net.eval()
+    fresh = DEMTransformer(256, 1, 1)
+    fresh.load_state_dict({k: v.detach().cpu() for k, v in net.state_dict().items()})
+    fresh = fresh.to(DEV).eval()
+    a, _ = net(dsm, coarse)
+    b, _ = fresh(dsm, coarse)
+    assert a.grad_fn is None and torch.equal(a, b)
+
+
+def test_sgd_trajectory_matches_float64_oracle():
+    ns, nc = 1, 1
+    sd = make_state_dict(80, 256, ns, nc, dem=True)
+    dsm, coarse, dem = terrain(81, 500)
+    net = build_dem(80, ns, nc)
+    lr = 0.01
+    opt = torch.optim.SGD(net.parameters(), lr=lr)
+    sd64 = {k: v.double().clone().requires_grad_() for k, v in sd.items()}
+    opt64 = torch.optim.SGD(list(sd64.values()), lr=lr)
+    d = lambda t: t.double()
+    for step in range(10):
+        net.train()
+        dem_, _ = net(dsm.to(DEV), coarse.to(DEV), False)
+        loss = net.loss(dem_, dem.to(DEV))
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        loss64 = l1(O.dem_transformer_forward(d(dsm), d(coarse), sd64), d(dem))
+        opt64.zero_grad()
+        loss64.backward()
+        opt64.step()
+        tol = 1e-4 if step < 5 else 5e-4  # the tolerances of test_gpu_train.py::test_sgd_trajectory_matches_float64_oracle
+        assert abs(loss.item() - loss64.item()) <= tol * abs(loss64.item()), (step, loss.item(), loss64.item())
+
+
+# ------------------------------------------------------------------------------------- images in training
+def _clouds(n, m, seed):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.rand(1, n, 3, generator=g) * 1.8 - 0.9), (torch.rand(1, m, 3, generator=g) * 1.8 - 0.9)
+
+
+def _kernel_argmax(src, tgt, eulers, w=64, rho=24):
+    rot = torch.stack([rotation_matrix(e) for e in eulers]).to(DEV)
+    meta = torch.tensor([0, src.shape[0], 0, tgt.shape[0]], dtype=torch.int32, device=DEV)
+    return ops.render_depth(src.contiguous(), meta[0:1], meta[1:2], tgt.contiguous(), meta[2:3], meta[3:4], src.shape[0],
+                            tgt.shape[0], rot, w, rho)[1][0]
+
+
+def test_training_images_carry_the_gradient_into_the_model():
+    net = build_dem(90, 1, 1)
+    dsm, coarse = (t.to(DEV) for t in _clouds(500, 100, 90))  # N not a multiple of 128, M < 128
+    dem = dsm.clone()
+    dem[..., 2] *= 0.5
+    net.train()
+    dem_, imgs = net(dsm, coarse, True)
+    assert imgs.grad_fn is not None and imgs.shape == (1, 2, 64, 64)
+    up = torch.randn(imgs.shape, device=DEV, generator=torch.Generator(DEV).manual_seed(91))
+    g = torch.autograd.grad((imgs * up).sum(), dem_, retain_graph=True)[0][0]
+    eulers = view_eulers("single")
+    amax = _kernel_argmax(dem_[0].detach(), coarse[0], eulers)
+    g64 = RR.backward(dem_[0].detach().double(), coarse[0].double(), up, amax, 24, 64, eulers, dtype=torch.float64)
+    g32 = RR.backward(dem_[0].detach(), coarse[0], up, amax, 24, 64, eulers, dtype=torch.float32)
+    assert g64.abs().max() > 0
+    assert rel(g, g64) <= max(2 * rel(g32, g64), 1e-5), (rel(g, g64), rel(g32, g64))
+
+    def grads(which):  # one forward each: the model's training graph is freed by its backward
+        net.zero_grad(set_to_none=True)
+        d_, im = net(dsm, coarse, True)
+        loss, g_loss = net.loss(d_, dem), (im * up).mean()
+        (loss * which[0] + 0.1 * g_loss * which[1]).backward()
+        return torch.cat([p.grad.detach().reshape(-1) for p in net.parameters()])
+
+    both, only_l1, only_img = grads((1, 1)), grads((1, 0)), grads((0, 1))
+    assert only_img.abs().max() > 0
+    assert rel(both, only_l1 + only_img) <= 1e-5
+
+
+# ------------------------------------------------------------------------------------- inference unchanged
+def test_inference_path_is_unchanged_without_explicit_train():
+    dsm, coarse, _ = (t.to(DEV) for t in terrain(95, 400))
+    net = build_dem(95, 1, 1)  # default-constructed: never called train()
+    a, ia = net(dsm, coarse, True)
+    assert a.grad_fn is None and ia.grad_fn is None
+    net.train()
+    with torch.no_grad():
+        b, ib = net(dsm, coarse, True)
+    net.eval()
+    c, ic = net(dsm, coarse, True)
+    assert b.grad_fn is None and c.grad_fn is None and ib.grad_fn is None and ic.grad_fn is None
+    assert torch.equal(a, b) and torch.equal(a, c)
+    assert torch.equal(ia.nan_to_num(), ib.nan_to_num()) and torch.equal(ia.nan_to_num(), ic.nan_to_num())

@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
-"""Training throughput of PointTransformer (6 + 6 layers) on 3DMatch-like pairs, and the weight-gradient GEMM's rate.
+"""Training throughput of PointTransformer (6 + 6 layers) on 3DMatch-like pairs, and the weight-gradient GEMM's rate; or, with
+--model dem, of DEMTransformer (6 + 6 layers) on OpenGF-like terrain.
 
     python tools/train_bench.py [--batches 4,32] [--steps 3] [--warmup 1] [--wgrad-only] [--json OUT]
+    python tools/train_bench.py --model dem [--batches 1,8] [--points 4000,16000] [--steps 3] [--warmup 1] [--json OUT]
 
 One step = training forward + loss + backward + Adam (lr 2e-4) over a packed batch of B pairs; pairs/s = B / step time
 (wall clock around torch.cuda.synchronize).  The wgrad part times scream_gemm_wgrad_f32 (partial and reduce launches) with
-events at 64 k and 330 k rows and reports TFLOP/s = 2 rows N K / t against the 157 TF fp32 MFMA peak.  Run it under
+events at 64 k and 330 k rows and reports TFLOP/s = 2 rows N K / t against the 157 TF fp32 MFMA peak.  The DEM leg is
+train_open_gf.py's step (L1 loss, two stems) on scream_amd.evaluate_open_gf.SyntheticDEM samples of `points` DSM points and
+their coarse DEM (20 m voxels); it reports samples/s and the peak memory of each (points, B) leg.  Run it under
 `rocprofv3 --kernel-trace --stats -- python tools/train_bench.py` for the per-kernel split (tools/rocprof_summary.py)."""
 import argparse
 import json
@@ -18,7 +22,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from scream_amd import train  # noqa: E402
-from scream_amd.model import PointTransformer  # noqa: E402
+from scream_amd.evaluate_open_gf import SyntheticDEM  # noqa: E402
+from scream_amd.model import DEMTransformer, PointTransformer  # noqa: E402
 from scream_amd.packing import PackedBatch  # noqa: E402
 from scream_amd.synthetic import make_3dmatch_pair, make_state_dict  # noqa: E402
 
@@ -67,6 +72,39 @@ def bench_training(B, steps, warmup):
                 loss=float(loss.detach()), peak_mem_gb=torch.cuda.max_memory_allocated() / 2 ** 30)
 
 
+def bench_dem_training(B, points, steps, warmup):
+    """train_open_gf.py:79-116 (use_GAN=False) on B SyntheticDEM samples packed into one batch (zero centres, raw coordinates)."""
+    net = DEMTransformer(256, 6, 6)
+    net.load_state_dict(make_state_dict(0, 256, 6, 6, dem=True))
+    net = net.to(DEV).train()
+    opt = torch.optim.Adam(net.parameters(), lr=2e-4)
+    samples = [[t.to(DEV) for t in SyntheticDEM(1, 200 + i, points)[0][:3]] for i in range(B)]
+    zero = torch.zeros(3, device=DEV)
+    batch = PackedBatch.from_pairs([s[0] for s in samples], [s[1] for s in samples], [zero] * B)
+
+    def step():
+        pred = net.forward_packed_train(batch)
+        loss = torch.stack([net.loss(x[None], s[2][None]) for x, s in zip(batch.unpack_src(pred), samples)]).mean()
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        return loss
+
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        loss = step()
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / steps
+    return dict(B=B, points=points, step_s=dt, samples_per_s=B / dt, mean_coarse_points=sum(s[1].shape[0] for s in samples) / B,
+                rows_src=batch.rows_src, rows_total=batch.rows_total, loss=float(loss.detach()),
+                peak_mem_gb=torch.cuda.max_memory_allocated() / 2 ** 30)
+
+
 def bench_wgrad(reps=20):
     out = []
     for rows in (65536, 330 * 1024):
@@ -89,18 +127,32 @@ def bench_wgrad(reps=20):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", default="4,32")
+    ap.add_argument("--model", choices=("point", "dem"), default="point")
+    ap.add_argument("--batches", default=None, help="default 4,32 (point) or 1,8 (dem)")
+    ap.add_argument("--points", default="4000,16000", help="DSM points per sample (dem)")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--wgrad-only", action="store_true")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
+    if a.model == "dem":
+        res = dict(model="dem", train=[])
+        for pts in (int(p) for p in a.points.split(",")):
+            for B in (int(b) for b in (a.batches or "1,8").split(",")):
+                r = bench_dem_training(B, pts, a.steps, a.warmup)
+                res["train"].append(r)
+                print("dem train points %5d B %2d: %.3f s/step  %.1f samples/s  (%.0f coarse points, %d rows, peak %.1f GB)"
+                      % (pts, B, r["step_s"], r["samples_per_s"], r["mean_coarse_points"], r["rows_total"], r["peak_mem_gb"]))
+        if a.json:
+            os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
+            json.dump(res, open(a.json, "w"), indent=1)
+        return
     res = dict(wgrad=bench_wgrad())
     for r in res["wgrad"]:
         print("wgrad rows %7d N %4d K %4d: %8.1f us  %6.1f TFLOP/s  %.2f of peak" % (r["rows"], r["N"], r["K"], r["us"], r["tflops"], r["frac_of_peak"]))
     if not a.wgrad_only:
         res["train"] = []
-        for B in (int(b) for b in a.batches.split(",")):
+        for B in (int(b) for b in (a.batches or "4,32").split(",")):
             r = bench_training(B, a.steps, a.warmup)
             res["train"].append(r)
             print("train B %2d: %.3f s/step  %.1f pairs/s  (%.0f points/pair, peak %.1f GB)" % (B, r["step_s"], r["pairs_per_s"],
