@@ -438,6 +438,17 @@ int64_t scream_wgrad_workspace_bytes(int64_t rows, int32_t N, int32_t K);
 int scream_gemm_wgrad_f32(const float* dY, int64_t ldy, const float* X, int64_t ldx, int64_t rows, int32_t N,
                           int32_t K, float* dW, int32_t accumulate, float* colsum, void* workspace,
                           int64_t workspace_bytes, void* stream);
+/* The same weight gradient, same contract, on the 16-bit matrix cores with fp32 accumulation (train_backend "split"): both
+ * operands are split into exact sums of 16-bit planes on the way into LDS (csrc/split.h) and every 16-row step runs the split's
+ * products.  split: SCREAM_SPLIT_BF3 (three bf16 planes, six v_mfma_f32_32x32x16_bf16 per step; scale free: dY times a power of
+ * two gives dW times that power bit for bit, as long as nothing leaves fp32's normal range -- what a loss scale needs);
+ * any other value is SCREAM_EINVAL.  colsum is an fp32 sum of the unsplit dY.  Fixed-order slabs and the index-order reduce
+ * launch of scream_gemm_wgrad_f32, no atomics: two identical calls are bitwise identical.
+ * workspace: scream_wgrad_split_workspace_bytes(rows, N, K) bytes, 16-byte aligned. */
+int64_t scream_wgrad_split_workspace_bytes(int64_t rows, int32_t N, int32_t K);
+int scream_gemm_wgrad_split_f32(const float* dY, int64_t ldy, const float* X, int64_t ldx, int64_t rows, int32_t N,
+                                int32_t K, float* dW, int32_t accumulate, float* colsum, int32_t split, void* workspace,
+                                int64_t workspace_bytes, void* stream);
 /* y = LayerNorm(a + b) * gamma + beta over rows of 256 (b may be NULL), with the per-row mean and rstd = 1/sqrt(var + 1e-5). */
 int scream_ln_fwd(const float* a, const float* b, const float* gamma, const float* beta, float* y, float* mean,
                   float* rstd, int64_t rows, void* stream);

@@ -1,11 +1,14 @@
-// Backward pass of PointTransformer (training, fp32 throughout).  scream_amd/train.py composes these with the forward's
-// scream_gemm_f32 (data gradients dX = dY W run on transposed weights) into the gradient of every parameter.
+// Backward pass of PointTransformer (training).  scream_amd/train.py composes these with the forward's GEMMs (data gradients
+// dX = dY W run on transposed weights) into the gradient of every parameter.  Everything here is fp32 arithmetic; the weight
+// gradient exists twice: on the fp32-input MFMA (train_backend "f32") and, fp32-accurate by operand splitting (split.h), on the
+// bf16 matrix cores (train_backend "split").
 //
 // Every reduction here is deterministic: a kernel writes fixed-order partial sums into a slab with ordinary vector
 // stores, and a second launch adds the slab's entries in index order.  No float atomics, so two identical calls give
 // bitwise identical gradients.  Padded rows (clouds start on 128-row boundaries) carry zero gradient: the attention
 // backward writes zeros there, and everything else is row-wise, so zeros propagate.
 #include "common.h"
+#include "split.h"
 
 namespace {
 
@@ -148,6 +151,124 @@ int64_t wgrad_slice_rows(int64_t rows, int N, int K) {
     if (slices < 1) slices = 1;
     const int64_t per = (rows + slices - 1) / slices;
     return (per + WG_R - 1) / WG_R * WG_R;
+}
+
+// ------------------------------------------------------------------------------------------------ weight gradient, split
+// The same sum on the 16-bit matrix cores, a template over the operand split (split.h; instantiated for SplitBf3: bf16 keeps
+// fp32's exponent range, so a gradient of any scale -- tiny, or multiplied by a loss scale of 2^16 and more -- needs no
+// exponent, cannot overflow, and a power of two on dY comes out of dW bit for bit).  Same block tile (128 x 128, 4 waves of
+// 64 x 64), same row slices and the same reduce launch as above.  Per 32-row chunk (two 16-deep steps):
+//   * waves 0-1 stage dY, waves 2-3 stage X: thread (rg, cg) of its pair loads rows 8 rg .. 8 rg + 7 of columns 4 cg .. 4 cg + 3
+//     (eight 16-byte loads, every wave instruction two full 512-byte row segments), one chunk ahead of the MFMAs;
+//   * the transposing write pass: for each of its four columns the thread holds the eight consecutive ROWS -- exactly one
+//     lane's operand of a 16-deep step, the row being the contraction index -- splits them once (split8<SP>) and writes one
+//     16-byte vector per plane into the image [operand][plane][row group][position];
+//   * column c of the tile sits at position 32 (c & 3) + (c >> 2), so that writes (32 lanes = 32 consecutive positions) and
+//     fragment reads (lane i of a 32-wide MFMA tile = position 32 t + i) are both 512 contiguous bytes per half wave: no
+//     bank conflicts, no padding.  An MFMA tile therefore owns the columns 4 i + t of the block tile; the epilogue undoes it.
+//   * per step and wave: NP fragment reads per 32-column tile, then SP::products (six MFMAs for SplitBf3) per tile pair.
+// colsum stays an fp32 sum of the unsplit dY, taken from the staging registers (rows in order, then the four row groups in
+// order).  LDS: 2 NP x 4 x 128 x 16 B = 48 KiB (SplitBf3) + 2 KiB for the column sums.
+constexpr int WS_G = WG_R / 8;  // row groups of eight per chunk
+
+template <class SP>
+__global__ __launch_bounds__(256) void wgrad_split_partial_kernel(const float* __restrict__ dY, int64_t ldy,
+                                                                  const float* __restrict__ X, int64_t ldx, int64_t rows,
+                                                                  int N, int K, int64_t slice_rows, float* __restrict__ part,
+                                                                  float* __restrict__ colpart) {
+    typedef typename SP::vec V;
+    constexpr int NP = SP::NP;
+    __shared__ __attribute__((aligned(16))) V sm[2 * NP * WS_G * WG_T];
+    __shared__ float scol[WS_G * WG_T];
+    const int kt = K / WG_T;
+    const int n0 = (blockIdx.x / kt) * WG_T, k0 = (blockIdx.x % kt) * WG_T;
+    const int64_t r_begin = (int64_t)blockIdx.y * slice_rows;
+    const int64_t r_end = min(rows, r_begin + slice_rows);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wn = wave >> 1, wk = wave & 1, i = lane & 31, half = lane >> 5;
+    const bool do_col = colpart != nullptr && k0 == 0;
+    // staging role: operand (wave uniform), row group, column group
+    const int op = tid >> 7, rg = (tid >> 5) & 3, cg = tid & 31;
+    const float* src = op ? X + k0 + 4 * cg : dY + n0 + 4 * cg;
+    const int64_t ld = op ? ldx : ldy;
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+    float csum[4] = {0.f, 0.f, 0.f, 0.f};
+
+    f32x4 v[8];
+    auto load = [&](int64_t r0) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int64_t row = r0 + 8 * rg + q;
+            v[q] = row < r_end ? ld4(src + row * ld) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+    if (r_begin < r_end) load(r_begin);
+    for (int64_t r0 = r_begin; r0 < r_end; r0 += WG_R) {
+        __syncthreads();  // the previous chunk's fragment reads are done
+        if (do_col && op == 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float t = 0.f;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) t += v[q][j];
+                csum[j] += t;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            V p[NP];
+            split8<SP>(f32x4{v[0][j], v[1][j], v[2][j], v[3][j]}, f32x4{v[4][j], v[5][j], v[6][j], v[7][j]}, p);
+#pragma unroll
+            for (int pl = 0; pl < NP; ++pl) sm[((op * NP + pl) * WS_G + rg) * WG_T + j * 32 + cg] = p[pl];
+        }
+        __syncthreads();
+        if (r0 + WG_R < r_end) load(r0 + WG_R);
+#pragma unroll
+        for (int s = 0; s < WG_R / 16; ++s) {
+            V fa[2][NP], fb[2][NP];
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int pl = 0; pl < NP; ++pl) {
+                    fa[t][pl] = sm[(pl * WS_G + 2 * s + half) * WG_T + wn * 64 + t * 32 + i];
+                    fb[t][pl] = sm[((NP + pl) * WS_G + 2 * s + half) * WG_T + wk * 64 + t * 32 + i];
+                }
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) SP::template products<false>(acc[a][b], fa[a], fb[b], acc[a][b]);
+        }
+    }
+    // acc[a][b][e] = dW[n0 + 4 mfma32_row(e, half) + 2 wn + a][k0 + 4 i + 2 wk + b]  (position p <-> column 4 (p & 31) + (p >> 5))
+    float* out = part + (int64_t)blockIdx.y * N * K;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            float* o = out + (int64_t)(n0 + 4 * mfma32_row(e, half) + 2 * wn + a) * K + k0 + 4 * i + 2 * wk;
+            o[0] = acc[a][0][e];
+            o[1] = acc[a][1][e];
+        }
+    if (do_col) {  // block uniform
+        if (op == 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) scol[rg * WG_T + 4 * cg + j] = csum[j];
+        }
+        __syncthreads();
+        if (tid < WG_T) {
+            float t = 0.f;
+#pragma unroll
+            for (int g = 0; g < WS_G; ++g) t += scol[g * WG_T + tid];
+            colpart[(int64_t)blockIdx.y * N + n0 + tid] = t;
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ LayerNorm
@@ -548,6 +669,43 @@ extern "C" int scream_gemm_wgrad_f32(const float* dY, int64_t ldy, const float* 
     float* colpart = colsum ? part + slices * (int64_t)N * K : nullptr;
     const int tiles = (N / WG_T) * (K / WG_T);
     wgrad_partial_kernel<<<dim3(tiles, (unsigned)slices), dim3(256), 0, st>>>(dY, ldy, X, ldx, rows, N, K, per, part, colpart);
+    SCREAM_LAUNCH_CHECK();
+    const int64_t nk = (int64_t)N * K;
+    wgrad_reduce_kernel<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st>>>(part, (int)slices, nk, dW, accumulate, colpart, N,
+                                                                                 colsum);
+    SCREAM_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int64_t scream_wgrad_split_workspace_bytes(int64_t rows, int32_t N, int32_t K) {
+    return scream_wgrad_workspace_bytes(rows, N, K);  // the same row slices and slabs
+}
+
+extern "C" int scream_gemm_wgrad_split_f32(const float* dY, int64_t ldy, const float* X, int64_t ldx, int64_t rows, int32_t N,
+                                           int32_t K, float* dW, int32_t accumulate, float* colsum, int32_t split,
+                                           void* workspace, int64_t workspace_bytes, void* stream) {
+    SCREAM_REQUIRE(dY && X && dW, SCREAM_EINVAL);
+    SCREAM_REQUIRE(split == SCREAM_SPLIT_BF3, SCREAM_EINVAL);
+    SCREAM_REQUIRE(rows >= 0 && N > 0 && K > 0 && N % WG_T == 0 && K % WG_T == 0, SCREAM_EUNSUPPORTED);
+    SCREAM_REQUIRE(ldy >= N && ldx >= K && ldy % 4 == 0 && ldx % 4 == 0 && aligned16(dY) && aligned16(X), SCREAM_EINVAL);
+    hipStream_t st = as_stream(stream);
+    if (rows == 0) {  // an empty sum: dW (+)= 0
+        if (!accumulate) {
+            if (hipMemsetAsync(dW, 0, (size_t)N * K * sizeof(float), st) != hipSuccess) return SCREAM_EINVAL;
+            if (colsum && hipMemsetAsync(colsum, 0, (size_t)N * sizeof(float), st) != hipSuccess) return SCREAM_EINVAL;
+        }
+        return 0;
+    }
+    const int64_t need = scream_wgrad_split_workspace_bytes(rows, N, K);
+    SCREAM_REQUIRE(workspace && workspace_bytes >= need && aligned16(workspace), SCREAM_EINVAL);
+    const int64_t per = wgrad_slice_rows(rows, N, K);
+    const int64_t slices = (rows + per - 1) / per;
+    SCREAM_REQUIRE(slices <= 65535, SCREAM_EUNSUPPORTED);
+    float* part = static_cast<float*>(workspace);
+    float* colpart = colsum ? part + slices * (int64_t)N * K : nullptr;
+    const int tiles = (N / WG_T) * (K / WG_T);
+    wgrad_split_partial_kernel<SplitBf3><<<dim3(tiles, (unsigned)slices), dim3(256), 0, st>>>(dY, ldy, X, ldx, rows, N, K, per, part,
+                                                                                             colpart);
     SCREAM_LAUNCH_CHECK();
     const int64_t nk = (int64_t)N * K;
     wgrad_reduce_kernel<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st>>>(part, (int)slices, nk, dW, accumulate, colpart, N,

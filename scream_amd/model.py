@@ -105,6 +105,27 @@ class PointTransformer(nn.Module):
     # forward (evaluate_kitti.py:37); set only by evaluate_kitti.evaluate(autocast=True) or by hand, never a default.
     gemm_backend = os.environ.get("SCREAM_GEMM", "h2")
 
+    # Arithmetic of the TRAINING matrix products (scream_amd/train.py); inference never looks at it.  "f32" (default): the
+    # fp32-input MFMA everywhere.  "split": fp32-accurate products on the bf16 matrix cores (three planes, six products, scale
+    # free -- safe under a GradScaler) for the forward GEMMs, the data gradients and the weight gradients.  SCREAM_TRAIN_GEMM
+    # sets the class default; an assignment validates at once, a bad environment value raises at the first train().
+    TRAIN_BACKENDS = ("f32", "split")
+    _train_backend_default = os.environ.get("SCREAM_TRAIN_GEMM", "f32")
+
+    @classmethod
+    def _check_train_backend(cls, value):
+        if value not in cls.TRAIN_BACKENDS:
+            raise ValueError("train_backend must be one of %s, got %r" % (", ".join(repr(b) for b in cls.TRAIN_BACKENDS), value))
+        return value
+
+    @property
+    def train_backend(self) -> str:
+        return self.__dict__.get("_train_backend", type(self)._train_backend_default)
+
+    @train_backend.setter
+    def train_backend(self, value: str) -> None:
+        self.__dict__["_train_backend"] = self._check_train_backend(value)
+
     # split backends only: attention apply, merge + LayerNorm1 and the FFN + LayerNorm2 as one launch per block
     # (csrc/tail_split.hip); SCREAM_FUSED_TAIL=0 falls back to attn_apply + three GEMM launches (same arithmetic, the
     # intermediate activations then go through HBM)
@@ -351,6 +372,8 @@ class PointTransformer(nn.Module):
         """nn.Module.train, and: after an EXPLICIT train() with grad mode on, forward / forward_packed_train return a prediction
         that carries a grad_fn (the fp32 training forward and the HIP backward of scream_amd/train.py).  A module that never
         called train(), net.eval() and torch.no_grad() keep the inference path."""
+        if mode:
+            self._check_train_backend(self.train_backend)
         super().train(mode)
         self._grad_train = bool(mode)
         return self

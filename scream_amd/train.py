@@ -1,5 +1,15 @@
-"""Training of PointTransformer and DEMTransformer: an fp32 forward that keeps its activations, and the backward pass on the
+"""Training of PointTransformer and DEMTransformer: a forward that keeps its activations, and the backward pass on the
 HIP kernels of csrc/backward.hip, wired into torch.autograd.
+
+Two arithmetics for the matrix products, chosen per model by net.train_backend (every other kernel is the same fp32 code):
+  "f32"    (default) every product on the fp32-input MFMA: scream_gemm_f32 forward and data gradients, scream_gemm_wgrad_f32.
+  "split"  fp32-accurate products on the 16-bit matrix cores with fp32 accumulation (csrc/split.h, SplitBf3: three bf16 planes,
+           six products, scale free -- gradients of any magnitude, a GradScaler's 2^16 included, need no exponent): forward and
+           data gradients on scream_gemm_split_f32 against weights packed by scream_pack_w_split, weight gradients on
+           scream_gemm_wgrad_split_f32.  Weights change every step, so their packed images (and the packed transposes the data
+           gradients read) are made per step, each once (_Gemms).  A data gradient
+           whose summed dimension the split GEMM does not take (K = 768 of the self layers' q|k|v, K = 512 of the cross
+           layers' k|v) runs as K = 256 products added in column order.
 
 The forward is the unfused fp32 chain of the existing kernels (scream_pe_embed + scream_ln_fwd, scream_gemm_f32 with the
 elu + 1 / relu / bias + relu epilogues, scream_kv_reduce, scream_attn_apply, scream_ln_fwd, scream_coor_head).  The layers
@@ -25,7 +35,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib, ops
-from ._lib import check
+from ._lib import SPLIT_BF3, check
 from .ops import EPI_BIAS_RELU, EPI_ELU1, EPI_NONE, EPI_RELU, D_MODEL, _p, _stream, gemm_f32
 from .packing import PackedBatch
 
@@ -54,6 +64,63 @@ def wgrad(dY: torch.Tensor, X: torch.Tensor, dW: torch.Tensor, colsum: torch.Ten
                                     X.stride(0) if ldx is None else ldx, rows, N, K, _p(dW), int(accumulate), _p(colsum),
                                     ws.data_ptr(), ws.numel(), _stream()), "scream_gemm_wgrad_f32")
     return dW
+
+
+def wgrad_split(dY: torch.Tensor, X: torch.Tensor, dW: torch.Tensor, colsum: torch.Tensor = None, accumulate: bool = False,
+                ldy: int = None, ldx: int = None, rows: int = None, split: int = SPLIT_BF3) -> torch.Tensor:
+    """wgrad on the 16-bit matrix cores (scream_gemm_wgrad_split_f32): same contract, fp32-accurate by operand splitting."""
+    lib = _lib.load()
+    rows = dY.shape[0] if rows is None else rows
+    N, K = dY.shape[1], X.shape[1]
+    ws = torch.empty(max(lib.scream_wgrad_split_workspace_bytes(rows, N, K), 16), device=dY.device, dtype=torch.uint8)
+    check(lib.scream_gemm_wgrad_split_f32(dY.data_ptr(), dY.stride(0) if ldy is None else ldy, X.data_ptr(),
+                                          X.stride(0) if ldx is None else ldx, rows, N, K, _p(dW), int(accumulate), _p(colsum),
+                                          split, ws.data_ptr(), ws.numel(), _stream()), "scream_gemm_wgrad_split_f32")
+    return dW
+
+
+SPLIT_K = 256  # a data gradient whose K scream_gemm_split_f32 does not take (K != 64 + 192 j) runs as products of this depth
+
+
+class _Gemms:
+    """The matrix products of ONE training step in the arithmetic of net.train_backend: the single dispatch point of the
+    forward GEMMs, the data gradients and the weight gradients.  Every weight matrix enters one forward product and one
+    data-gradient product per step, so "split" packs each (and each transpose) exactly once per step, where it is used."""
+
+    def __init__(self, net):
+        self.split = net._check_train_backend(net.train_backend) == "split"
+
+    def fwd(self, A, W, epilogue: int = EPI_NONE, n_act: int = 0, bias=None):
+        """epilogue(A W^T) for W [N,K]."""
+        if not self.split:
+            return gemm_f32(A, W, epilogue, n_act=n_act, bias=bias)
+        return ops.gemm_split(A, ops.pack_w(W, SPLIT_BF3), epilogue, n_act=n_act, bias=bias)
+
+    def dgrad(self, dY, W, out=None):
+        """dX = dY W for W [N,K]: a GEMM against the transposed weight [K,N], which sums over N."""
+        Wt = transpose(W)
+        if not self.split:
+            return gemm_f32(dY, Wt, out=out)
+        N = W.shape[0]
+        if N >= 64 and N % 64 == 0 and (N // 32 - 2) % 3 == 0:  # what scream_gemm_split_f32 takes: 64 + 192 j
+            return ops.gemm_split(dY, ops.pack_w(Wt, SPLIT_BF3), out=out)
+        assert N % SPLIT_K == 0
+        lib, M = _lib.load(), dY.shape[0]
+        if out is None:
+            out = torch.empty(M, W.shape[1], device=dY.device, dtype=torch.float32)
+        tmp = torch.empty_like(out)
+        for c in range(0, N, SPLIT_K):  # column blocks of dY in order: a fixed-order sum
+            pk = ops.pack_w(Wt[:, c:c + SPLIT_K], SPLIT_BF3)
+            dst = tmp if c else out
+            check(lib.scream_gemm_split_f32(_ptr(dY, c), dY.stride(0), pk.data_ptr(), _p(dst), dst.stride(0), M, pk.N, SPLIT_K,
+                                            EPI_NONE, 0, None, None, 0, None, None, 0, SPLIT_BF3, 0, 0, _stream()),
+                  "scream_gemm_split_f32")
+            if c:
+                add_(out, tmp)
+        return out
+
+    def wgrad(self, dY, X, dW, colsum=None):
+        return (wgrad_split if self.split else wgrad)(dY, X, dW, colsum)
 
 
 def ln_fwd(a: torch.Tensor, b, gamma, beta, out: torch.Tensor = None):
@@ -115,7 +182,7 @@ def _cat(*ws) -> torch.Tensor:
     return torch.cat([w for w in ws], dim=0).contiguous()
 
 
-def _block_fwd(P, prefix: str, x: torch.Tensor, t, batch: PackedBatch, r0: int, cb: int, n: int,
+def _block_fwd(P, mm: _Gemms, prefix: str, x: torch.Tensor, t, batch: PackedBatch, r0: int, cb: int, n: int,
                out: torch.Tensor = None) -> (torch.Tensor, _Layer):
     """One block (models/transformer.py:74-90) on rows [r0, r0 + x.shape[0]) whose clouds are [cb, cb + n).  t: the target
     features (rows batch.rows_src ..) of a cross layer, None for a self layer.  out: where the block output goes (default:
@@ -125,27 +192,28 @@ def _block_fwd(P, prefix: str, x: torch.Tensor, t, batch: PackedBatch, r0: int, 
     L.cross, L.prefix, L.r0, L.rows, L.cb, L.n, L.x, L.t = t is not None, prefix, r0, x.shape[0], cb, n, x, t
     n_clouds = 2 * batch.n_pairs
     if t is None:
-        L.qkv = gemm_f32(x, _cat(w("q_proj.weight"), w("k_proj.weight"), w("v_proj.weight")), EPI_ELU1, n_act=2 * D_MODEL)
+        L.qkv = mm.fwd(x, _cat(w("q_proj.weight"), w("k_proj.weight"), w("v_proj.weight")), EPI_ELU1,
+                       n_act=2 * D_MODEL)
         L.kvp = None
         L.kv = ops.kv_reduce(L.qkv[:, D_MODEL:], L.qkv[:, 2 * D_MODEL:], 3 * D_MODEL, r0, batch.cloud_row0, batch.cloud_len, cb, n,
                              batch.max_chunks, n_clouds)
         L.att = ops.attn_apply(L.qkv, 3 * D_MODEL, L.kv, batch.tile_cloud[r0 // ops.ROW_TILE:], 0, batch.cloud_len, L.rows)
     else:
         B, rs = batch.n_pairs, batch.rows_src
-        L.qkv = gemm_f32(x, w("q_proj.weight").contiguous(), EPI_ELU1, n_act=D_MODEL)
-        L.kvp = gemm_f32(t, _cat(w("k_proj.weight"), w("v_proj.weight")), EPI_ELU1, n_act=D_MODEL)
+        L.qkv = mm.fwd(x, w("q_proj.weight").contiguous(), EPI_ELU1, n_act=D_MODEL)
+        L.kvp = mm.fwd(t, _cat(w("k_proj.weight"), w("v_proj.weight")), EPI_ELU1, n_act=D_MODEL)
         L.kv = ops.kv_reduce(L.kvp, L.kvp[:, D_MODEL:], 2 * D_MODEL, rs, batch.cloud_row0, batch.cloud_len, B, B, batch.max_chunks,
                              n_clouds)
         L.att = ops.attn_apply(L.qkv, D_MODEL, L.kv, batch.tile_cloud, B, batch.cloud_len, L.rows)
-    L.msg = gemm_f32(L.att, w("merge.weight").contiguous())
+    L.msg = mm.fwd(L.att, w("merge.weight").contiguous())
     L.m1, *L.s1 = ln_fwd(L.msg, x, w("norm1.weight"), w("norm1.bias"))
-    L.hid = gemm_f32(L.m1, w("mlp.0.weight").contiguous(), EPI_RELU)
-    L.ffn = gemm_f32(L.hid, w("mlp.2.weight").contiguous())
+    L.hid = mm.fwd(L.m1, w("mlp.0.weight").contiguous(), EPI_RELU)
+    L.ffn = mm.fwd(L.hid, w("mlp.2.weight").contiguous())
     y, *L.s2 = ln_fwd(L.ffn, x, w("norm2.weight"), w("norm2.bias"), out)
     return y, L
 
 
-def _block_bwd(P, G, L: _Layer, dy: torch.Tensor, batch: PackedBatch, dt) -> None:
+def _block_bwd(P, G, mm: _Gemms, L: _Layer, dy: torch.Tensor, batch: PackedBatch, dt) -> None:
     """dy [rows, 256] (the gradient of the block output) is REPLACED by the gradient of the block input; a cross layer adds
     the gradient of its key/value input into dt (the target features' gradient)."""
     w = lambda s: _w(P, L.prefix + s)
@@ -153,27 +221,27 @@ def _block_bwd(P, G, L: _Layer, dy: torch.Tensor, batch: PackedBatch, dt) -> Non
     dev, R = dy.device, L.rows
     dffn = torch.empty(R, D_MODEL, device=dev, dtype=torch.float32)
     ln_bwd(dy, L.ffn, L.x, L.s2[0], L.s2[1], w("norm2.weight"), dffn, None, g("norm2.weight"), g("norm2.bias"))
-    wgrad(dffn, L.hid, g("mlp.2.weight"))
-    dhid = gemm_f32(dffn, transpose(w("mlp.2.weight")))
+    mm.wgrad(dffn, L.hid, g("mlp.2.weight"))
+    dhid = mm.dgrad(dffn, w("mlp.2.weight"))
     relu_bwd(dhid, L.hid)
-    wgrad(dhid, L.m1, g("mlp.0.weight"))
-    dm1 = gemm_f32(dhid, transpose(w("mlp.0.weight")))
+    mm.wgrad(dhid, L.m1, g("mlp.0.weight"))
+    dm1 = mm.dgrad(dhid, w("mlp.0.weight"))
     del dhid
     dmsg = torch.empty(R, D_MODEL, device=dev, dtype=torch.float32)
     ln_bwd(dm1, L.msg, L.x, L.s1[0], L.s1[1], w("norm1.weight"), dmsg, dffn, g("norm1.weight"), g("norm1.bias"))  # dffn: dz2 + dz1
     del dm1
-    wgrad(dmsg, L.att, g("merge.weight"))
-    datt = gemm_f32(dmsg, transpose(w("merge.weight")))
+    mm.wgrad(dmsg, L.att, g("merge.weight"))
+    datt = mm.dgrad(dmsg, w("merge.weight"))
     del dmsg
     if not L.cross:
         dqkv = torch.empty(R, 3 * D_MODEL, device=dev, dtype=torch.float32)
         attn_bwd(_ptr(L.qkv), 3 * D_MODEL, R, L.r0, L.att, datt, _ptr(L.qkv, D_MODEL), _ptr(L.qkv, 2 * D_MODEL), 3 * D_MODEL, R, L.r0,
                  L.kv, batch, L.cb, L.n, 0, _ptr(dqkv), 3 * D_MODEL, _ptr(dqkv, D_MODEL), _ptr(dqkv, 2 * D_MODEL), 3 * D_MODEL)
         dW = torch.empty(3 * D_MODEL, D_MODEL, device=dev, dtype=torch.float32)
-        wgrad(dqkv, L.x, dW)
+        mm.wgrad(dqkv, L.x, dW)
         for i, nm in enumerate(("q_proj.weight", "k_proj.weight", "v_proj.weight")):
             G[L.prefix + nm] = dW[i * D_MODEL:(i + 1) * D_MODEL]
-        gemm_f32(dqkv, transpose(_cat(w("q_proj.weight"), w("k_proj.weight"), w("v_proj.weight"))), out=dy)
+        mm.dgrad(dqkv, _cat(w("q_proj.weight"), w("k_proj.weight"), w("v_proj.weight")), out=dy)
     else:
         B, rs = batch.n_pairs, batch.rows_src
         Rt = L.t.shape[0]
@@ -181,12 +249,12 @@ def _block_bwd(P, G, L: _Layer, dy: torch.Tensor, batch: PackedBatch, dt) -> Non
         dkvp = torch.empty(Rt, 2 * D_MODEL, device=dev, dtype=torch.float32)
         attn_bwd(_ptr(L.qkv), D_MODEL, R, 0, L.att, datt, _ptr(L.kvp), _ptr(L.kvp, D_MODEL), 2 * D_MODEL, Rt, rs, L.kv, batch, 0, B, B,
                  _ptr(dq), D_MODEL, _ptr(dkvp), _ptr(dkvp, D_MODEL), 2 * D_MODEL)
-        wgrad(dq, L.x, g("q_proj.weight"))
+        mm.wgrad(dq, L.x, g("q_proj.weight"))
         dW = torch.empty(2 * D_MODEL, D_MODEL, device=dev, dtype=torch.float32)
-        wgrad(dkvp, L.t, dW)
+        mm.wgrad(dkvp, L.t, dW)
         G[L.prefix + "k_proj.weight"], G[L.prefix + "v_proj.weight"] = dW[:D_MODEL], dW[D_MODEL:]
-        gemm_f32(dq, transpose(w("q_proj.weight")), out=dy)
-        add_(dt, gemm_f32(dkvp, transpose(_cat(w("k_proj.weight"), w("v_proj.weight")))))
+        mm.dgrad(dq, w("q_proj.weight"), out=dy)
+        add_(dt, mm.dgrad(dkvp, _cat(w("k_proj.weight"), w("v_proj.weight"))))
     add_(dy, dffn)
 
 
@@ -214,6 +282,7 @@ def forward_saving(net, batch: PackedBatch):
     """The training forward: packed src_pred [rows_src, 3] and what the backward needs."""
     from .model import pe_dim_t
     P = dict(net.named_parameters())
+    mm = _Gemms(net)
     dev = batch.xyz.device
     rs, rt, B = batch.rows_src, batch.rows_total, batch.n_pairs
     z0 = torch.empty(rt, D_MODEL, device=dev, dtype=torch.float32)
@@ -226,26 +295,27 @@ def forward_saving(net, batch: PackedBatch):
     for passes in _stem_passes(net, batch):
         y = torch.empty(rt, D_MODEL, device=dev, dtype=torch.float32)  # every application writes its own rows
         for prefix, r0, rows, cb, n in passes:
-            _, L = _block_fwd(P, prefix, f[r0:r0 + rows], None, batch, r0, cb, n, out=y[r0:r0 + rows])
+            _, L = _block_fwd(P, mm, prefix, f[r0:r0 + rows], None, batch, r0, cb, n, out=y[r0:r0 + rows])
             layers.append(L)
         f = y
     n_stem = len(layers)
     tf = f[rs:]
     sf = f[:rs]
     for j, prefix in enumerate(_layer_prefixes(net)[2]):
-        sf, L = _block_fwd(P, prefix, sf, tf if j % 2 else None, batch, 0, 0, B)
+        sf, L = _block_fwd(P, mm, prefix, sf, tf if j % 2 else None, batch, 0, 0, B)
         layers.append(L)
     c = lambda k: _w(P, "coor_mlp.%d" % k + ".weight")[:, :, 0].contiguous()
-    h1 = gemm_f32(sf, c(0), EPI_BIAS_RELU, bias=_w(P, "coor_mlp.0.bias"))
-    h2 = gemm_f32(h1, c(2), EPI_BIAS_RELU, bias=_w(P, "coor_mlp.2.bias"))
+    h1 = mm.fwd(sf, c(0), EPI_BIAS_RELU, bias=_w(P, "coor_mlp.0.bias"))
+    h2 = mm.fwd(h1, c(2), EPI_BIAS_RELU, bias=_w(P, "coor_mlp.2.bias"))
     out = ops.coor_head(h2, c(4), _w(P, "coor_mlp.4.bias"))
-    return out, dict(z0=z0, s0=s0, layers=layers, n_stem=n_stem, sf=sf, h1=h1, h2=h2)
+    return out, dict(z0=z0, s0=s0, layers=layers, n_stem=n_stem, sf=sf, h1=h1, h2=h2, mm=mm)
 
 
 def backward(net, batch: PackedBatch, saved, dout: torch.Tensor) -> List[torch.Tensor]:
     """Gradients of every parameter (named_parameters order) for the packed output gradient dout [rows_src, 3]."""
     P = dict(net.named_parameters())
     G = {n: torch.empty_like(p, dtype=torch.float32) for n, p in P.items()}
+    mm = saved["mm"]  # the arithmetic, and the packed weights, of the forward this backward belongs to
     dev = dout.device
     rs, rt = batch.rows_src, batch.rows_total
     dout = dout.to(torch.float32).contiguous()
@@ -255,18 +325,18 @@ def backward(net, batch: PackedBatch, saved, dout: torch.Tensor) -> List[torch.T
     grad3(h2, dout, G["coor_mlp.4.weight"], False, col_s=G["coor_mlp.4.bias"])
     dh2 = torch.empty(rs, D_MODEL, device=dev, dtype=torch.float32)
     check(_lib.load().scream_coor_head_bwd(_p(dout), _p(c(4)), _p(h2), _p(dh2), rs, _stream()), "scream_coor_head_bwd")
-    wgrad(dh2, h1, G["coor_mlp.2.weight"], G["coor_mlp.2.bias"])
-    dh1 = gemm_f32(dh2, transpose(c(2)))
+    mm.wgrad(dh2, h1, G["coor_mlp.2.weight"], G["coor_mlp.2.bias"])
+    dh1 = mm.dgrad(dh2, c(2))
     relu_bwd(dh1, h1)
-    wgrad(dh1, saved["sf"], G["coor_mlp.0.weight"], G["coor_mlp.0.bias"])
+    mm.wgrad(dh1, saved["sf"], G["coor_mlp.0.weight"], G["coor_mlp.0.bias"])
     dF = torch.zeros(rt, D_MODEL, device=dev, dtype=torch.float32)  # gradient of the features of all rows
-    gemm_f32(dh1, transpose(c(0)), out=dF[:rs])
+    mm.dgrad(dh1, c(0), out=dF[:rs])
     del dh1, dh2
     layers, n_stem = saved["layers"], saved["n_stem"]
     for L in reversed(layers[n_stem:]):  # cross stage: source rows; the target features collect every cross layer's gradient
-        _block_bwd(P, G, L, dF[:rs], batch, dF[rs:])
+        _block_bwd(P, G, mm, L, dF[:rs], batch, dF[rs:])
     for L in reversed(layers[:n_stem]):  # stem: each application on its own rows (all rows for one shared stem)
-        _block_bwd(P, G, L, dF[L.r0:L.r0 + L.rows], batch, None)
+        _block_bwd(P, G, mm, L, dF[L.r0:L.r0 + L.rows], batch, None)
     # pre_norm and the embedding (models/pointnet.py:45-48); the position embedding has no parameters
     dz0 = torch.empty(rt, D_MODEL, device=dev, dtype=torch.float32)
     z0, (m0, r0) = saved["z0"], saved["s0"]

@@ -2,12 +2,14 @@
 """Training throughput of PointTransformer (6 + 6 layers) on 3DMatch-like pairs, and the weight-gradient GEMM's rate; or, with
 --model dem, of DEMTransformer (6 + 6 layers) on OpenGF-like terrain.
 
-    python tools/train_bench.py [--batches 4,32] [--steps 3] [--warmup 1] [--wgrad-only] [--json OUT]
-    python tools/train_bench.py --model dem [--batches 1,8] [--points 4000,16000] [--steps 3] [--warmup 1] [--json OUT]
+    python tools/train_bench.py [--batches 4,32] [--steps 3] [--warmup 1] [--train-backend f32|split] [--wgrad-only] [--json OUT]
+    python tools/train_bench.py --model dem [--batches 1,8] [--points 4000,16000] [--train-backend f32|split] [--json OUT]
 
 One step = training forward + loss + backward + Adam (lr 2e-4) over a packed batch of B pairs; pairs/s = B / step time
-(wall clock around torch.cuda.synchronize).  The wgrad part times scream_gemm_wgrad_f32 (partial and reduce launches) with
-events at 64 k and 330 k rows and reports TFLOP/s = 2 rows N K / t against the 157 TF fp32 MFMA peak.  The DEM leg is
+(wall clock around torch.cuda.synchronize) in the arithmetic of --train-backend (net.train_backend).  The wgrad part times
+scream_gemm_wgrad_f32 and scream_gemm_wgrad_split_f32 (partial and reduce launches) with events at 64 k and 330 k rows and
+reports fp32-equivalent TFLOP/s = 2 rows N K / t, the first against the 157 TF fp32 MFMA peak, the second against the bf16 x 3
+roof (2 500 TF bf16 peak / 6 products = 417 TF).  The DEM leg is
 train_open_gf.py's step (L1 loss, two stems) on scream_amd.evaluate_open_gf.SyntheticDEM samples of `points` DSM points and
 their coarse DEM (20 m voxels); it reports samples/s and the peak memory of each (points, B) leg.  Run it under
 `rocprofv3 --kernel-trace --stats -- python tools/train_bench.py` for the per-kernel split (tools/rocprof_summary.py)."""
@@ -28,6 +30,7 @@ from scream_amd.packing import PackedBatch  # noqa: E402
 from scream_amd.synthetic import make_3dmatch_pair, make_state_dict  # noqa: E402
 
 PEAK_TF = 157.0
+PEAK_TF_BF3 = 2500.0 / 6  # six bf16 products per fp32-accurate one
 DEV = "cuda:0"
 
 
@@ -42,9 +45,10 @@ def pair(seed):
     return f(s * (src - c)), f(s * (tgt - c)), f(rot), f(s * (t - c.reshape(3, 1) + rot @ c.reshape(3, 1)))
 
 
-def bench_training(B, steps, warmup):
+def bench_training(B, steps, warmup, backend):
     net = PointTransformer(256, 6, 6)
     net.load_state_dict(make_state_dict(0, 256, 6, 6))
+    net.train_backend = backend
     net = net.to(DEV).train()
     opt = torch.optim.Adam(net.parameters(), lr=2e-4)
     pairs = [pair(100 + i) for i in range(B)]
@@ -68,14 +72,15 @@ def bench_training(B, steps, warmup):
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
     pts = sum(p[0].shape[0] + p[1].shape[0] for p in pairs) / B
-    return dict(B=B, step_s=dt, pairs_per_s=B / dt, mean_points_per_pair=pts, rows_total=batch.rows_total,
+    return dict(B=B, train_backend=backend, step_s=dt, pairs_per_s=B / dt, mean_points_per_pair=pts, rows_total=batch.rows_total,
                 loss=float(loss.detach()), peak_mem_gb=torch.cuda.max_memory_allocated() / 2 ** 30)
 
 
-def bench_dem_training(B, points, steps, warmup):
+def bench_dem_training(B, points, steps, warmup, backend):
     """train_open_gf.py:79-116 (use_GAN=False) on B SyntheticDEM samples packed into one batch (zero centres, raw coordinates)."""
     net = DEMTransformer(256, 6, 6)
     net.load_state_dict(make_state_dict(0, 256, 6, 6, dem=True))
+    net.train_backend = backend
     net = net.to(DEV).train()
     opt = torch.optim.Adam(net.parameters(), lr=2e-4)
     samples = [[t.to(DEV) for t in SyntheticDEM(1, 200 + i, points)[0][:3]] for i in range(B)]
@@ -100,7 +105,7 @@ def bench_dem_training(B, points, steps, warmup):
         loss = step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
-    return dict(B=B, points=points, step_s=dt, samples_per_s=B / dt, mean_coarse_points=sum(s[1].shape[0] for s in samples) / B,
+    return dict(B=B, points=points, train_backend=backend, step_s=dt, samples_per_s=B / dt, mean_coarse_points=sum(s[1].shape[0] for s in samples) / B,
                 rows_src=batch.rows_src, rows_total=batch.rows_total, loss=float(loss.detach()),
                 peak_mem_gb=torch.cuda.max_memory_allocated() / 2 ** 30)
 
@@ -112,16 +117,17 @@ def bench_wgrad(reps=20):
             dY = torch.randn(rows, N, device=DEV)
             X = torch.randn(rows, K, device=DEV)
             dW = torch.empty(N, K, device=DEV)
-            train.wgrad(dY, X, dW)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(reps):
-                train.wgrad(dY, X, dW)
-            e1.record()
-            e1.synchronize()
-            t = e0.elapsed_time(e1) / reps / 1e3
-            tf = 2.0 * rows * N * K / t / 1e12
-            out.append(dict(rows=rows, N=N, K=K, us=t * 1e6, tflops=tf, frac_of_peak=tf / PEAK_TF))
+            for kernel, fn, peak in (("f32", train.wgrad, PEAK_TF), ("split", train.wgrad_split, PEAK_TF_BF3)):
+                fn(dY, X, dW)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(reps):
+                    fn(dY, X, dW)
+                e1.record()
+                e1.synchronize()
+                t = e0.elapsed_time(e1) / reps / 1e3
+                tf = 2.0 * rows * N * K / t / 1e12
+                out.append(dict(kernel=kernel, rows=rows, N=N, K=K, us=t * 1e6, tflops=tf, frac_of_peak=tf / peak))
     return out
 
 
@@ -132,6 +138,7 @@ def main():
     ap.add_argument("--points", default="4000,16000", help="DSM points per sample (dem)")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--train-backend", choices=("f32", "split"), default="f32", help="net.train_backend of the training legs")
     ap.add_argument("--wgrad-only", action="store_true")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
@@ -139,24 +146,24 @@ def main():
         res = dict(model="dem", train=[])
         for pts in (int(p) for p in a.points.split(",")):
             for B in (int(b) for b in (a.batches or "1,8").split(",")):
-                r = bench_dem_training(B, pts, a.steps, a.warmup)
+                r = bench_dem_training(B, pts, a.steps, a.warmup, a.train_backend)
                 res["train"].append(r)
-                print("dem train points %5d B %2d: %.3f s/step  %.1f samples/s  (%.0f coarse points, %d rows, peak %.1f GB)"
-                      % (pts, B, r["step_s"], r["samples_per_s"], r["mean_coarse_points"], r["rows_total"], r["peak_mem_gb"]))
+                print("dem train %s points %5d B %2d: %.3f s/step  %.1f samples/s  (%.0f coarse points, %d rows, peak %.1f GB)"
+                      % (a.train_backend, pts, B, r["step_s"], r["samples_per_s"], r["mean_coarse_points"], r["rows_total"], r["peak_mem_gb"]))
         if a.json:
             os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
             json.dump(res, open(a.json, "w"), indent=1)
         return
     res = dict(wgrad=bench_wgrad())
     for r in res["wgrad"]:
-        print("wgrad rows %7d N %4d K %4d: %8.1f us  %6.1f TFLOP/s  %.2f of peak" % (r["rows"], r["N"], r["K"], r["us"], r["tflops"], r["frac_of_peak"]))
+        print("wgrad %-5s rows %7d N %4d K %4d: %8.1f us  %6.1f TFLOP/s  %.2f of its roof" % (r["kernel"], r["rows"], r["N"], r["K"], r["us"], r["tflops"], r["frac_of_peak"]))
     if not a.wgrad_only:
         res["train"] = []
         for B in (int(b) for b in (a.batches or "4,32").split(",")):
-            r = bench_training(B, a.steps, a.warmup)
+            r = bench_training(B, a.steps, a.warmup, a.train_backend)
             res["train"].append(r)
-            print("train B %2d: %.3f s/step  %.1f pairs/s  (%.0f points/pair, peak %.1f GB)" % (B, r["step_s"], r["pairs_per_s"],
-                                                                                                r["mean_points_per_pair"], r["peak_mem_gb"]))
+            print("train %s B %2d: %.3f s/step  %.1f pairs/s  (%.0f points/pair, peak %.1f GB)" % (a.train_backend, B, r["step_s"], r["pairs_per_s"],
+                                                                                                   r["mean_points_per_pair"], r["peak_mem_gb"]))
     if a.json:
         os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
         json.dump(res, open(a.json, "w"), indent=1)
