@@ -73,10 +73,36 @@ def linear_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, want: Op
     return out.contiguous()
 
 
+# ------------------------------------------------- the piecewise operations, under masks of the caller's
+def masked_relu(x: torch.Tensor, mask: Optional[torch.Tensor] = None, record: Optional[dict] = None, key=None) -> torch.Tensor:
+    """relu(x); with a mask m (the x > 0 of ANOTHER path through the same network) x * m instead: the smooth function that
+    path differentiated, so a gradient check against it sees rounding only and no disagreement about which units are on.
+    record: a dict that receives the mask in use under `key`."""
+    if record is not None:
+        record[key] = (x > 0).detach() if mask is None else mask
+    return torch.relu(x) if mask is None else x * mask.to(x.dtype)
+
+
+def masked_abs(x: torch.Tensor, sign: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """abs(x); with signs s (sign(x) of another path) x * s instead."""
+    return torch.abs(x) if sign is None else x * sign.to(x.dtype)
+
+
+def _coor_mlp(sf: torch.Tensor, sd: Dict[str, torch.Tensor], masks: Optional[dict], record: Optional[dict]) -> torch.Tensor:
+    """coor_mlp, pointnet.py:27-33,60 (Conv1d k=1 == per-point Linear with bias).  Mask keys ("coor_mlp.0.", "src") and
+    ("coor_mlp.2.", "src"): the two relu outputs [1,N,256]."""
+    m = (lambda k: None) if masks is None else (lambda k: masks[k])
+    k0, k2 = ("coor_mlp.0.", "src"), ("coor_mlp.2.", "src")
+    h = masked_relu(sf @ sd["coor_mlp.0.weight"][:, :, 0].t() + sd["coor_mlp.0.bias"], m(k0), record, k0)
+    h = masked_relu(h @ sd["coor_mlp.2.weight"][:, :, 0].t() + sd["coor_mlp.2.bias"], m(k2), record, k2)
+    return h @ sd["coor_mlp.4.weight"][:, :, 0].t() + sd["coor_mlp.4.bias"]
+
+
 # ------------------------------------------------------------------------ A2, A4
 def mh_attention(xq: torch.Tensor, xk: torch.Tensor, xv: torch.Tensor, sd: Dict[str, torch.Tensor],
-                 prefix: str, want: Optional[dict] = None) -> torch.Tensor:
-    """models/transformer.py:74-90.  Residual of norm2 is the block input (line 88)."""
+                 prefix: str, want: Optional[dict] = None, relu_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """models/transformer.py:74-90.  Residual of norm2 is the block input (line 88).
+    relu_mask: [bs,L,4d] taken in place of the FFN's own hid > 0 (masked_relu); None computes it."""
     d = xq.shape[-1]
     dim = d // NHEAD
     bs = xq.shape[0]
@@ -86,7 +112,7 @@ def mh_attention(xq: torch.Tensor, xk: torch.Tensor, xv: torch.Tensor, sd: Dict[
     att = linear_attention(q, k, v, want)
     msg = att.view(bs, -1, d) @ sd[prefix + "merge.weight"].t()
     m1 = F.layer_norm(msg + xq, (d,), sd[prefix + "norm1.weight"], sd[prefix + "norm1.bias"], LN_EPS)
-    hid = torch.relu(m1 @ sd[prefix + "mlp.0.weight"].t())
+    hid = masked_relu(m1 @ sd[prefix + "mlp.0.weight"].t(), relu_mask)
     ffn = hid @ sd[prefix + "mlp.2.weight"].t()
     out = F.layer_norm(xq + ffn, (d,), sd[prefix + "norm2.weight"], sd[prefix + "norm2.bias"], LN_EPS)
     if want is not None:
@@ -102,10 +128,14 @@ def layer_counts(sd: Dict[str, torch.Tensor]) -> Tuple[int, int]:
 
 
 def point_transformer_forward(src: torch.Tensor, tgt: torch.Tensor, sd: Dict[str, torch.Tensor],
-                              src_center: Optional[torch.Tensor] = None, wants: Optional[list] = None) -> torch.Tensor:
+                              src_center: Optional[torch.Tensor] = None, wants: Optional[list] = None,
+                              masks: Optional[dict] = None, record_masks: Optional[dict] = None) -> torch.Tensor:
     """models/pointnet.py:38-60: returns src_ [1,N,3] (predicted registered src coordinates).
     wants: a list that receives (prefix, side, intermediates of mh_attention) per block application, for tests that look at
-    the operand ranges inside the network."""
+    the operand ranges inside the network.
+    masks: {(prefix, "src" | "tgt"): bool [1,L,4d]} per block application plus the two of _coor_mlp: every relu takes its
+    mask from there (masked_relu) instead of computing it.  record_masks: a dict that receives the masks in use under
+    the same keys, so the masks of one run can be given to another."""
     assert src.shape[0] == 1 and tgt.shape[0] == 1
     n_self, n_cross = layer_counts(sd)
     if src_center is None:
@@ -113,8 +143,10 @@ def point_transformer_forward(src: torch.Tensor, tgt: torch.Tensor, sd: Dict[str
     sf = embed_prenorm(src, src - src_center, sd)
     tf = embed_prenorm(tgt, tgt, sd)
     def block(xq, xkv, p, side):
-        w = {} if wants is not None else None
-        out = mh_attention(xq, xkv, xkv, sd, p, w)
+        w = {} if wants is not None or record_masks is not None else None
+        out = mh_attention(xq, xkv, xkv, sd, p, w, None if masks is None else masks[(p, side)])
+        if record_masks is not None:
+            record_masks[(p, side)] = (w["hid"] > 0).detach() if masks is None else masks[(p, side)]
         if wants is not None:
             w.update(xq=xq, xkv=xkv)
             wants.append((p, side, w))
@@ -129,29 +161,34 @@ def point_transformer_forward(src: torch.Tensor, tgt: torch.Tensor, sd: Dict[str
             sf = block(sf, sf, "cross.%d." % i, "src")
         else:
             sf = block(sf, tf, "cross.%d.layer." % i, "src")
-    # coor_mlp, pointnet.py:27-33,60 (Conv1d k=1 == per-point Linear with bias)
-    h = torch.relu(sf @ sd["coor_mlp.0.weight"][:, :, 0].t() + sd["coor_mlp.0.bias"])
-    h = torch.relu(h @ sd["coor_mlp.2.weight"][:, :, 0].t() + sd["coor_mlp.2.bias"])
-    return h @ sd["coor_mlp.4.weight"][:, :, 0].t() + sd["coor_mlp.4.bias"]
+    return _coor_mlp(sf, sd, masks, record_masks)
 
 
-def dem_transformer_forward(dsm: torch.Tensor, dem_coarse: torch.Tensor, sd: Dict[str, torch.Tensor]) -> torch.Tensor:
-    """models/pointnet.py:134-153 (DEMTransformer): separate stems, raw coordinates embedded for both clouds."""
+def dem_transformer_forward(dsm: torch.Tensor, dem_coarse: torch.Tensor, sd: Dict[str, torch.Tensor],
+                            masks: Optional[dict] = None, record_masks: Optional[dict] = None) -> torch.Tensor:
+    """models/pointnet.py:134-153 (DEMTransformer): separate stems, raw coordinates embedded for both clouds.
+    masks / record_masks: as in point_transformer_forward (stem_dsm.i is the "src" side, stem_dem.i the "tgt" side)."""
     n_self = len({k.split(".")[1] for k in sd if k.startswith("stem_dsm.")})
     n_cross2 = len({k.split(".")[1] for k in sd if k.startswith("cross.")})
     sf = embed_prenorm(dsm, dsm, sd)
     tf = embed_prenorm(dem_coarse, dem_coarse, sd)
+
+    def block(xq, xkv, p, side):
+        w = {} if record_masks is not None else None
+        out = mh_attention(xq, xkv, xkv, sd, p, w, None if masks is None else masks[(p, side)])
+        if record_masks is not None:
+            record_masks[(p, side)] = (w["hid"] > 0).detach() if masks is None else masks[(p, side)]
+        return out
+
     for i in range(n_self):
-        sf = mh_attention(sf, sf, sf, sd, "stem_dsm.%d." % i)
-        tf = mh_attention(tf, tf, tf, sd, "stem_dem.%d." % i)
+        sf = block(sf, sf, "stem_dsm.%d." % i, "src")
+        tf = block(tf, tf, "stem_dem.%d." % i, "tgt")
     for i in range(n_cross2):
         if i % 2 == 0:
-            sf = mh_attention(sf, sf, sf, sd, "cross.%d." % i)
+            sf = block(sf, sf, "cross.%d." % i, "src")
         else:
-            sf = mh_attention(sf, tf, tf, sd, "cross.%d.layer." % i)
-    h = torch.relu(sf @ sd["coor_mlp.0.weight"][:, :, 0].t() + sd["coor_mlp.0.bias"])
-    h = torch.relu(h @ sd["coor_mlp.2.weight"][:, :, 0].t() + sd["coor_mlp.2.bias"])
-    return h @ sd["coor_mlp.4.weight"][:, :, 0].t() + sd["coor_mlp.4.bias"]
+            sf = block(sf, tf, "cross.%d.layer." % i, "src")
+    return _coor_mlp(sf, sd, masks, record_masks)
 
 
 # --------------------------------------------------------------------------- A7
@@ -301,10 +338,21 @@ def rmse_metric(trans: np.ndarray, info: np.ndarray) -> float:
     return (er.reshape(1, 6) @ info @ er.reshape(6, 1) / info[0, 0]).item()
 
 
-def point_loss(src_pred: torch.Tensor, src: torch.Tensor, rot: torch.Tensor, trans: torch.Tensor) -> torch.Tensor:
-    """models/pointnet.py:93-99."""
-    reg = (torch.matmul(rot, src.permute(0, 2, 1)) + trans).permute(0, 2, 1)
-    return torch.mean(torch.sum(torch.abs(src_pred - reg), dim=-1), dim=1).mean(dim=0)
+def registered(src: torch.Tensor, rot: torch.Tensor, trans: torch.Tensor) -> torch.Tensor:
+    """models/pointnet.py:94: the source cloud under the ground-truth pose, [B,N,3]."""
+    return (torch.matmul(rot, src.permute(0, 2, 1)) + trans).permute(0, 2, 1)
+
+
+def point_loss(src_pred: torch.Tensor, src: torch.Tensor, rot: torch.Tensor, trans: torch.Tensor,
+               sign: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """models/pointnet.py:93-99.  sign: [B,N,3] taken in place of sign(src_pred - reg) (masked_abs)."""
+    reg = registered(src, rot, trans)
+    return torch.mean(torch.sum(masked_abs(src_pred - reg, sign), dim=-1), dim=1).mean(dim=0)
+
+
+def dem_loss(dem_pred: torch.Tensor, dem: torch.Tensor, sign: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """models/pointnet.py:162-166.  sign: [B,N,3] taken in place of sign(dem_pred - dem)."""
+    return torch.mean(torch.sum(masked_abs(dem_pred - dem, sign), dim=-1), dim=1).mean(dim=0)
 
 
 # -------------------------------------------------------------------------- A12

@@ -8,36 +8,20 @@ import numpy as np
 import pytest
 import torch
 
+import train_ref as T
 from oracle import scream_ref as O
 from scream_amd import _lib, train
-from scream_amd.evaluate_open_gf import SyntheticDEM
-from scream_amd.synthetic import make_state_dict, make_trained_like_state_dict, random_rotation
+from scream_amd.synthetic import make_state_dict, make_trained_like_state_dict
+from train_ref import FLOOR, make_pair, packed_rows, rel  # the yardstick shared by the training test files
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-FLOOR = 5e-6  # the fixed floor of the "<= 2 x the fp32 path's error" rule
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _require_gpu_and_native_lib():
     assert torch.cuda.is_available(), "pytest -m gpu needs the MI355X"
     _lib.load()
-
-
-def rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return (torch.linalg.norm(a - b) / max(torch.linalg.norm(b).item(), 1e-300)).item()
-
-
-def packed_rows(lens, rng, width, pad_value=0.0):
-    """[sum(padded lens), width] with real rows random and padded tails `pad_value`."""
-    parts = []
-    for n in lens:
-        p = (n + 127) // 128 * 128
-        x = np.full((p, width), pad_value, dtype=np.float32)
-        x[:n] = rng.standard_normal((n, width)).astype(np.float32)
-        parts.append(x)
-    return torch.from_numpy(np.concatenate(parts))
 
 
 # ------------------------------------------------------------------------------------- the kernel
@@ -99,25 +83,6 @@ def test_wgrad_split_is_deterministic():
 
 
 # ------------------------------------------------------------------------------------- model gradients
-def make_pair(seed, n, m):
-    rng = np.random.default_rng(seed)
-    tgt = rng.uniform(-0.6, 0.6, size=(m, 3)).astype(np.float32)
-    R = random_rotation(rng, 30.0).astype(np.float32)
-    t = rng.uniform(-0.1, 0.1, size=(3, 1)).astype(np.float32)
-    base = tgt[rng.permutation(m)[:n]] if n <= m else np.concatenate([tgt, rng.uniform(-0.6, 0.6, size=(n - m, 3))])
-    src = ((base - t.T) @ R + 0.005 * rng.standard_normal((n, 3))).astype(np.float32)  # R src + t ~ tgt
-    return (torch.from_numpy(src)[None], torch.from_numpy(tgt)[None], torch.from_numpy(R)[None], torch.from_numpy(t)[None])
-
-
-def oracle_grads(sd, src, tgt, rot, trans, dtype):
-    sdx = {k: v.to(dtype).requires_grad_() for k, v in sd.items()}
-    c = lambda t: t.to(dtype)
-    pred = O.point_transformer_forward(c(src), c(tgt), sdx, c(trans).permute(0, 2, 1))
-    loss = O.point_loss(pred, c(src), c(rot), c(trans))
-    loss.backward()
-    return loss.item(), {k: v.grad for k, v in sdx.items()}
-
-
 def build_net(sd, ns, nc, backend=None):
     from scream_amd.model import PointTransformer
     net = PointTransformer(256, ns, nc)
@@ -128,60 +93,40 @@ def build_net(sd, ns, nc, backend=None):
 
 
 def gpu_grads(net, src, tgt, rot, trans):
-    net.train()
-    net.zero_grad(set_to_none=True)
-    src_, _, _ = net(src.to(DEV), tgt.to(DEV), trans.permute(0, 2, 1).to(DEV), 1.0)
-    assert src_.grad_fn is not None
-    loss = net.loss(src_, src.to(DEV), rot.to(DEV), trans.to(DEV))
-    loss.backward()
-    return loss.item(), {n: p.grad.detach().cpu() for n, p in net.named_parameters()}
+    return T.point_module_grads(net, src, tgt, rot, trans, DEV)
 
 
-def check_rule(what, g, g64, gref, ratio, floor, floors=None):
-    """Per tensor: error against float64 <= max(ratio x the yardstick's error against float64, floor).  floors: tensors with a
-    floor of their own.  Prints the worst tensor."""
-    bad, worst = [], (0.0, None, 0.0, 0.0)
-    for k in g64:
-        e, er = rel(g[k], g64[k]), rel(gref[k], g64[k])
-        bar = max(ratio * er, (floors or {}).get(k, floor))
-        if e / bar > worst[0]:
-            worst = (e / bar, k, e, er)
-        if not e <= bar:
-            bad.append((k, e, er))
-    print("%s: worst tensor %s at %.3g of its bar (error %.3g, yardstick %.3g); largest error %.3g; %d over the bar"
-          % (what, worst[1], worst[0], worst[2], worst[3], max(rel(g[k], g64[k]) for k in g64), len(bad)))
-    return bad
-
-
-# A finding (docs/design/oracle_and_parity.md, "Training under split arithmetic"): in the (1, 1) configuration ONE unit of
-# stem.0's FFN hidden layer (packed row 250, unit 619) has the pre-activation 5e-8 beside |m1| = 16, i.e. 3e-9 relative --
-# inside every fp32 product's rounding.  float64 and the fp32-input MFMA give it a positive sign (hid = 2.1e-7), bf16 x 3 gives
-# 0, so its relu mask differs and with it every gradient that flows through stem.0's hidden layer: the eleven tensors below land
-# at 9.2e-5 .. 5.53e-4 relative (measured; every other tensor of that model, and every tensor of four other seeds, stays within
-# 3.2e-6, the same as "f32").  It is the effect that gives the deeper models 4 x / 5e-4 in test_gpu_train.py, met here in the
-# shallow one.  Those eleven tensors take the issue's rule for a tensor that needs a looser bar: the measured worst case over
-# five seeds (5.53e-4) with a factor 2 on top.  That is above 5e-4 because one unit among the 1.8 M of that layer carries
-# 5.5e-4 of the gradient norm of v_proj here; every other tensor keeps max(2 x, 5e-6).
-BEHIND_STEM0_RELU = ["embedding.weight", "embedding.bias", "pre_norm.weight", "pre_norm.bias", "stem.0.q_proj.weight",
-                     "stem.0.k_proj.weight", "stem.0.v_proj.weight", "stem.0.merge.weight", "stem.0.norm1.weight",
-                     "stem.0.norm1.bias", "stem.0.mlp.0.weight"]
-RELU_FLIP_FLOOR = 2 * 5.53e-4
-
-
-# the three configurations, rule and (ratio, floor) of test_gpu_train.py::test_model_gradients_against_float64
-@pytest.mark.parametrize("ns,nc,n,m,ratio,floor", [(1, 1, 700, 900, 2, FLOOR), (2, 2, 690, 910, 4, 5e-4), (6, 6, 2000, 2100, 4, 5e-4)])
-def test_model_gradients_against_float64_split(ns, nc, n, m, ratio, floor):
-    sd = make_state_dict(5 + ns, 256, ns, nc)
-    src, tgt, rot, trans = make_pair(ns, n, m)
-    loss64, g64 = oracle_grads(sd, src, tgt, rot, trans, torch.float64)
-    _, g32 = oracle_grads(sd, src, tgt, rot, trans, torch.float32)
-    net = build_net(sd, ns, nc, "split")
-    loss, g = gpu_grads(net, src, tgt, rot, trans)
+def masked_rule(what, net, sd, pair):
+    """The rule of tests/train_ref.py for one pair on `net`: the gradients of a direct train.forward_saving / train.backward
+    pass (bitwise those of net(...); loss.backward()) against float64 under THAT pass's relu masks and L1 signs, per tensor
+    <= max(2 x the fp32 CPU oracle's error under the same masks, 5e-6).  Returns (loss, gradients)."""
+    loss, g, masks = T.point_gpu(net, [pair], DEV)
     assert len(g) == len(sd)
-    floors = {k: RELU_FLIP_FLOOR for k in BEHIND_STEM0_RELU} if (ns, nc) == (1, 1) else None
-    assert floors is None or all(k in sd for k in floors)
-    bad = check_rule("split (%d,%d)" % (ns, nc), g, g64, g32, ratio, floor, floors)
+    T.assert_bitwise("forward_saving + backward against net(...); loss.backward()", g, gpu_grads(net, *pair)[1])
+    g64m, g32m = T.masked_oracles(T.oracle_grads, sd, [pair], masks)
+    bad = T.rule(what, g, g64m, g32m)
     assert not bad, bad
+    return loss, g
+
+
+# The three configurations and the rule of test_gpu_train.py::test_model_gradients_against_float64.  The split products round
+# differently from the fp32-input MFMA, so a hidden unit within rounding of zero can be switched differently (in the (1, 1)
+# configuration unit 619 of packed row 250 of stem.0: pre-activation 5e-8 beside |m1| = 16; docs/design/oracle_and_parity.md,
+# "Training under split arithmetic"); under the split pass's OWN masks every tensor takes the one rule.
+# The case ids are the ones these cases have had since they were added: they end in the (ratio, floor) each case was held to
+# before every case took the one rule of masked_rule.  Kept, so that the record of a case stays one series; they set nothing.
+@pytest.mark.parametrize("ns,nc,n,m", [pytest.param(1, 1, 700, 900, id="1-1-700-900-2-5e-06"),
+                                      pytest.param(2, 2, 690, 910, id="2-2-690-910-4-0.0005"),
+                                      pytest.param(6, 6, 2000, 2100, id="6-6-2000-2100-4-0.0005")])
+def test_model_gradients_against_float64_split(ns, nc, n, m):
+    sd = make_state_dict(5 + ns, 256, ns, nc)
+    pair = make_pair(ns, n, m)
+    loss, _ = masked_rule("split (%d,%d)" % (ns, nc), build_net(sd, ns, nc, "split"), sd, pair)
+    d = lambda t: t.double()
+    src, tgt, rot, trans = pair
+    with torch.no_grad():  # float64 under its own masks
+        pred = O.point_transformer_forward(d(src), d(tgt), {k: d(v) for k, v in sd.items()}, d(trans).permute(0, 2, 1))
+        loss64 = O.point_loss(pred, d(src), d(rot), d(trans)).item()
     print("loss", loss, "float64", loss64)
     assert abs(loss - loss64) <= 1e-5 * abs(loss64)
 
@@ -190,64 +135,43 @@ def test_dem_gradients_against_float64_split():
     """The (2, 2) configuration of test_gpu_train_dem.py::test_model_gradients_against_float64: separate stems, the target-side
     stem's gradient through the cross layers' key/value path (the K = 512 data gradient)."""
     from scream_amd.model import DEMTransformer
-    ns, nc, points, ratio, floor = 2, 2, 690, 4, 5e-4
+    ns, nc, points = 2, 2, 690
     sd = make_state_dict(30 + ns, 256, ns, nc, dem=True)
-    dsm, coarse, dem, _ = SyntheticDEM(1, ns, points)[0]
-    dsm, coarse, dem = dsm[None], coarse[None], dem[None]
-    l1 = lambda pred, ref: torch.mean(torch.sum(torch.abs(pred - ref), dim=-1), dim=1).mean(dim=0)  # models/pointnet.py:162-166
-
-    def oracle(dtype):
-        sdx = {k: v.to(dtype).requires_grad_() for k, v in sd.items()}
-        loss = l1(O.dem_transformer_forward(dsm.to(dtype), coarse.to(dtype), sdx), dem.to(dtype))
-        loss.backward()
-        return loss.item(), {k: v.grad for k, v in sdx.items()}
-
-    loss64, g64 = oracle(torch.float64)
-    _, g32 = oracle(torch.float32)
+    sample = T.terrain(ns, points)
     net = DEMTransformer(256, ns, nc)
     net.load_state_dict(sd)
     net.train_backend = "split"
     net = net.to(DEV).train()
-    dem_, imgs = net(dsm.to(DEV), coarse.to(DEV), False)
-    assert dem_.grad_fn is not None and imgs is None
-    loss = net.loss(dem_, dem.to(DEV))
-    loss.backward()
-    g = {n: p.grad.detach().cpu() for n, p in net.named_parameters()}
+    loss, g, masks = T.dem_gpu(net, [sample], DEV)
     assert len(g) == len(sd)
-    bad = check_rule("split DEM (2,2)", g, g64, g32, ratio, floor)
+    T.assert_bitwise("forward_saving + backward against net(...); loss.backward()", g, T.dem_module_grads(net, *sample, DEV)[1])
+    g64m, g32m = T.masked_oracles(T.dem_oracle_grads, sd, [sample], masks)
+    bad = T.rule("split DEM (2,2)", g, g64m, g32m)
     assert not bad, bad
-    assert abs(loss.item() - loss64) <= 1e-5 * abs(loss64)
+    dsm, coarse, dem = (t.double() for t in sample)
+    with torch.no_grad():
+        loss64 = O.dem_loss(O.dem_transformer_forward(dsm, coarse, {k: v.double() for k, v in sd.items()}), dem).item()
+    assert abs(loss - loss64) <= 1e-5 * abs(loss64)
 
 
 def test_trained_like_weights_split_against_the_f32_backend():
     """LayerNorm gains up to 240 (make_trained_like_state_dict): an fp16 x 2 forward would leave its range here; bf16 x 3 has
-    none to leave.  No training test used these weights before, so the yardstick is the "f32" backend on the same model and
-    input: per tensor, the "split" error against float64 <= max(4 x the "f32" backend's error against float64, 5e-4)."""
+    none to leave.  The two backends switch hidden units differently, so each is held to the rule against float64 under its
+    own masks."""
     ns, nc = 2, 2
     sd = make_trained_like_state_dict(3, 256, ns, nc)
-    src, tgt, rot, trans = make_pair(21, 690, 910)
-    _, g64 = oracle_grads(sd, src, tgt, rot, trans, torch.float64)
-    _, gf = gpu_grads(build_net(sd, ns, nc, "f32"), src, tgt, rot, trans)
-    _, gs = gpu_grads(build_net(sd, ns, nc, "split"), src, tgt, rot, trans)
-    assert all(torch.isfinite(v).all() for v in gs.values())
-    ratios = {k: rel(gs[k], g64[k]) / max(rel(gf[k], g64[k]), 1e-300) for k in sd}
-    k = max(ratios, key=ratios.get)
-    print("trained-like: largest split / f32 error ratio %.3g (%s: split %.3g, f32 %.3g); median ratio %.3g"
-          % (ratios[k], k, rel(gs[k], g64[k]), rel(gf[k], g64[k]), float(np.median(list(ratios.values())))))
-    bad = check_rule("split trained-like (2,2) vs f32 backend", gs, g64, gf, 4, 5e-4)
-    assert not bad, bad
+    pair = make_pair(21, 690, 910)
+    for backend in ("f32", "split"):
+        _, g = masked_rule("%s trained-like (2,2)" % backend, build_net(sd, ns, nc, backend), sd, pair)
+        assert all(torch.isfinite(v).all() for v in g.values())
 
 
 def test_the_two_backends_agree_within_the_float64_rule():
     ns, nc = 2, 2
     sd = make_state_dict(17, 256, ns, nc)
-    src, tgt, rot, trans = make_pair(22, 640, 800)
-    _, g64 = oracle_grads(sd, src, tgt, rot, trans, torch.float64)
-    _, g32 = oracle_grads(sd, src, tgt, rot, trans, torch.float32)
+    pair = make_pair(22, 640, 800)
     for backend in ("f32", "split"):
-        _, g = gpu_grads(build_net(sd, ns, nc, backend), src, tgt, rot, trans)
-        bad = check_rule("%s (2,2)" % backend, g, g64, g32, 4, 5e-4)
-        assert not bad, (backend, bad)
+        masked_rule("%s (2,2)" % backend, build_net(sd, ns, nc, backend), sd, pair)
 
 
 def test_sgd_trajectory_matches_float64_oracle_split():
