@@ -372,6 +372,11 @@ int scream_square_distance(const float* src, const float* dst, float* out, int32
  *   the corr="src_pred" branch of evaluate_3d_match.py:99-101); centroids sum/(K + 1e-6);
  *   H = sum (A-cA)(B-cB)^T; 3x3 SVD by one-sided Jacobi in registers (fp64), R = V diag(1,1,det(V U^T)) U^T,
  *   t = cB - R cA.  K == 0 gives the identity, as torch.svd of a zero matrix does.
+ * Domain of the solve (both entry points): H is held in fp32, as the reference holds it, and the SVD is scale-free, so the
+ *   pose has the accuracy of an O(1) problem while the largest entry of H is a normal fp32 number with its 24 bits, i.e.
+ *   2^-102 <= max |H_ij| < 2^127: centred coordinates between about 2^-50 / sqrt(K) and 2^62 / sqrt(K) in both clouds
+ *   (tests hold 2^-40 .. 2^20).  Below that H loses bits to gradual underflow and the rotation degrades with it (still a
+ *   proper rotation; H == 0 exactly gives the identity); above it H overflows.  Neither is detected.
  * T_out [n_pairs,16] row-major 4x4; n_corr [n_pairs] (int32) = K.  c is [n_pairs,3]. */
 int scream_kabsch_corr(const float* src, const float* ref, const int32_t* src_row0,
                        const int32_t* src_len, const int32_t* ref_row0, const int32_t* idx,

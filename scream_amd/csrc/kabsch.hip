@@ -43,8 +43,11 @@ __device__ void jacobi_svd3(const double H[3][3], double U[3][3], double V[3][3]
             const int p = (pq == 2) ? 1 : 0;
             const int q = (pq == 0) ? 1 : 2;
             const double alpha = dot3(g[p], g[p]), beta = dot3(g[q], g[q]), gamma = dot3(g[p], g[q]);
-            const double lim = 1e-30 + 1e-16 * sqrt(alpha * beta);
-            if (fabs(gamma) > lim) {
+            // scale-free: |cos| of the angle between the two columns against 1e-16, whatever |H| (an absolute term here stopped the
+            // sweep early for |H| < 1e-13 and skipped it altogether below 1e-15; the reference's LAPACK SVD is scale-invariant).
+            // alpha * beta cannot leave the double range for any fp32 H; gamma == 0 covers a zero column.
+            const double lim = 1e-16 * sqrt(alpha * beta);
+            if (gamma != 0.0 && fabs(gamma) > lim) {
                 off += fabs(gamma);
                 const double zeta = (beta - alpha) / (2.0 * gamma);
                 const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
@@ -83,7 +86,7 @@ __device__ void jacobi_svd3(const double H[3][3], double U[3][3], double V[3][3]
         }
     }
     double u[3][3];
-    if (!(s[0] > 1e-300)) {
+    if (!(s[0] > 0.0)) {
         // H == 0 (no correspondences): torch.svd returns U = V = I -> identity transform (utils.py:155-175)
 #pragma unroll
         for (int c = 0; c < 3; ++c)

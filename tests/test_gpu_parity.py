@@ -617,7 +617,9 @@ def test_transformation_error_vs_reference_golden(golden):
     Tp = dev(np.repeat(P, n, axis=0))
     Tg = dev(np.tile(P, (n, 1, 1)))
     re, te = ops.transformation_error_batched(Tp, Tg)
-    np.testing.assert_allclose(re.cpu().numpy().reshape(n, n), g["re"], atol=0.03)  # acos near 1 is ill conditioned in fp32
+    re_dev, ends = re.cpu().numpy().reshape(n, n), (g["re"] < 0.5) | (g["re"] > 179.5)
+    np.testing.assert_allclose(re_dev[ends], g["re"][ends], atol=0.03)  # acos near +-1 is ill conditioned in fp32
+    np.testing.assert_allclose(re_dev[~ends], g["re"][~ends], atol=1e-3)  # (the interval bar: tests/test_gpu_pose_backend.py)
     np.testing.assert_allclose(te.cpu().numpy().reshape(n, n), g["te"], rtol=1e-6, atol=1e-7)
     r0, t0 = transformation_error(dev(P[0]), dev(P[3]))
     assert r0.dim() == 0 and abs(r0.item() - g["re"][0, 3]) < 1e-3 and abs(t0.item() - g["te"][0, 3]) < 1e-6
