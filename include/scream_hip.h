@@ -519,6 +519,32 @@ int scream_render_depth_bwd(const float* src, const int32_t* s_row0, const int32
                             const float* dimgs, const int32_t* argmax, void* workspace, int64_t workspace_bytes, float* dsrc,
                             void* stream);
 
+/* ---- voxel_down_sample of a batch of clouds (open3d's legacy voxel_down_sample as the reference calls it on every cloud it
+ * feeds the models: process_3d_match.py:30-32, process_kitti.py:55-56, datasets/kitti.py:137-138, datasets/open_gf.py:22,42,62;
+ * csrc/voxel.hip).  Cloud c is rows row0[c] .. + len[c] of xyz [rows,3]; the clouds need no 128-row alignment here and must not
+ * overlap.  Per cloud, with v = voxel[c] (DEVICE doubles, one per cloud):
+ *   origin = min_bound - v / 2                 (min_bound the exact per-axis fp32 minimum, the rest in float64),
+ *   (i, j, k) = floor((p - origin) / v)        (float64 from the fp32 coordinate, a real division),
+ *   one output row per occupied voxel = the float64 sum of its points in ascending row index, divided in float64 by their
+ *   number and rounded once to fp32; rows in ascending (i, j, k), i most significant (the order of np.unique(axis=0)),
+ * written to out_xyz rows row0[c] .. + out_len[c] (out_xyz [rows,3]: compact from the cloud's own first row; the rows behind are
+ * not written), their point counts to out_count [rows] at the same rows unless out_count is NULL, and the number of voxels to
+ * out_len[c].  Fixed-order sums, no float atomics: the result is a pure function of the cloud -- bitwise repeatable, independent of
+ * the other clouds of the call and equal bit for bit to the float64 numpy restatement of tests/voxel_ref.py.  Parity with open3d
+ * itself is not pinned (its output order is that of a hash map).
+ * Refused clouds are reported, not faulted: out_len[c] = -1 and no rows for a cloud whose grid needs more than 2^21 cells on an
+ * axis, that holds a non-finite coordinate, whose voxel is not a positive finite number, or whose rows break the bounds below;
+ * the other clouds are unaffected.  len[c] = 0 gives out_len[c] = 0.
+ * max_len (host) bounds every len[c] and sizes the grids.  workspace: scream_voxel_workspace_bytes(rows_total, n_clouds) bytes,
+ * 16-byte aligned, rows_total (<= 2^31 - 1) the row count of xyz: the rows the workspace was sized for are recovered from
+ * workspace_bytes, every cloud must end inside them, and less than scream_voxel_workspace_bytes(max_len, n_clouds) is
+ * SCREAM_EINVAL.  n_clouds <= 65535 (SCREAM_EUNSUPPORTED beyond); n_clouds = 0 does nothing.  The passes of the radix sort a cloud
+ * does not need are skipped on the device; the call never synchronises with the host. */
+int64_t scream_voxel_workspace_bytes(int64_t rows_total, int32_t n_clouds);
+int scream_voxel_down_sample(const float* xyz, const int32_t* row0, const int32_t* len, int32_t n_clouds, int32_t max_len,
+                             const double* voxel, float* out_xyz, int32_t* out_len, int32_t* out_count, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@ Importing the package is cheap and CPU-safe (synthetic data, packing metadata); 
 computes needs libscream_hip.so and an MI355X and raises ``ScreamHipError`` otherwise.
 """
 from ._lib import ScreamHipError  # noqa: F401
+from .voxel import voxel_down_sample, voxel_down_sample_batch  # noqa: F401
 
-__all__ = ["ScreamHipError"]
+__all__ = ["ScreamHipError", "voxel_down_sample", "voxel_down_sample_batch"]
 __version__ = "0.1.0"

@@ -31,6 +31,7 @@ SOURCES = {
     "kabsch.hip": ["-ffp-contract=off"],
     "icp_grid.hip": ["-ffp-contract=off"],
     "render.hip": ["-ffp-contract=off"],
+    "voxel.hip": ["-ffp-contract=off"],
 }
 # SCREAM_HIPCC_EXTRA="file.hip:-flag,-flag;file2.hip:-flag": extra compiler flags per source (experiments; empty in the product)
 EXTRA_DEFINES = {}

@@ -46,6 +46,18 @@ def normalize_pair(src: np.ndarray, tgt: np.ndarray, T: np.ndarray, mode: str = 
     return (torch.Tensor(src_n), torch.Tensor(tgt_n), torch.Tensor(rot), torch.Tensor(trans_n), s, torch.Tensor(c))
 
 
+def downsample_pair(src_raw, tgt_raw, T: np.ndarray, voxel: float, mode: str = "ball", device=None):
+    """A raw pair to the models' input in one call: both scans ([N,3] / [M,3], numpy or torch, any float type; registered by the
+    4x4 T) are voxel-down-sampled in one batched HIP call (scream_amd/voxel.py, fp32 centroids) and handed to ``normalize_pair``.
+    Returns its tuple (src, tgt, rot, trans, s, c); INTEGRATION.md shows the way from there to ``net(...)`` / ``evaluate_loader``.
+    process_3d_match.py:30-32 (voxel 0.0625, mode "ball") and process_kitti.py:55-56 (voxel 0.7, mode "bbox") are this step."""
+    from .voxel import voxel_down_sample_batch
+    device = torch.device(device if device is not None else "cuda")
+    raw = [torch.as_tensor(a).to(device=device, dtype=torch.float32) for a in (src_raw, tgt_raw)]
+    src, tgt = (c.cpu().numpy().astype(np.float64) for c in voxel_down_sample_batch(raw, float(voxel)))
+    return normalize_pair(src, tgt, np.asarray(T, dtype=np.float64), mode)
+
+
 class PairFileDataset(Dataset):
     """A split directory in the reference's on-disk format (process_3d_match.py:38-40,199-200):
     src%d.npy / tgt%d.npy float64 [N,3], T%d.npy [4,4], info/idx%d.npy, info/covariance%d.npy,

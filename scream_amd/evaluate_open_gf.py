@@ -41,17 +41,37 @@ def voxel_down_sample(points: np.ndarray, voxel: float) -> np.ndarray:
     return out / cnt[:, None]
 
 
-def make_sample(dsm_dem: np.ndarray, center=None):
-    """datasets/open_gf.py:58-69 for one [N,6] array."""
+def _check_coarse(coarse: str) -> str:
+    if coarse not in ("host", "gpu"):
+        raise ValueError("coarse must be 'host' or 'gpu', got %r" % (coarse,))
+    return coarse
+
+
+def make_sample(dsm_dem: np.ndarray, center=None, coarse: str = "host"):
+    """datasets/open_gf.py:58-69 for one [N,6] array.  coarse="gpu": the second entry is the RAW DEM (fp32, metres, not divided)
+    instead of the coarse DEM; ``coarse_dems`` down-samples a whole batch of those on the GPU (``evaluate_samples`` does)."""
     dsm, dem = dsm_dem[:, :3], dsm_dem[:, 3:]
-    dem_coarse = voxel_down_sample(dem, DEM_COARSE_RESOLUTION)
     f = lambda a: torch.from_numpy(np.ascontiguousarray(a / SCALE_FACTOR, dtype=np.float32))
+    if _check_coarse(coarse) == "gpu":
+        return f(dsm), torch.from_numpy(np.ascontiguousarray(dem, dtype=np.float32)), f(dem), center
+    dem_coarse = voxel_down_sample(dem, DEM_COARSE_RESOLUTION)
     return f(dsm), f(dem_coarse), f(dem), center
 
 
+def coarse_dems(raw_dems: Sequence[torch.Tensor], device=None, scaled: bool = True) -> List[torch.Tensor]:
+    """The coarse DEMs of B raw DEMs ([N,3] fp32, metres) in one batched HIP voxel_down_sample at 20 m (scream_amd/voxel.py),
+    then divided by 50 in fp32 (scaled=False: left in metres).  The host path rounds float64 centroids of the float64 file
+    values once; this one takes the centroids of the fp32 coordinates and divides in fp32 -- the same voxels, coordinates that
+    differ in the last bits, which is why it is opt-in.  DEMTransformer's batched training can build its clouds the same way."""
+    from .voxel import voxel_down_sample_batch
+    device = device or raw_dems[0].device
+    out = voxel_down_sample_batch([d.to(device) for d in raw_dems], float(DEM_COARSE_RESOLUTION))
+    return [c / SCALE_FACTOR for c in out] if scaled else out
+
+
 class OpenGFFiles(torch.utils.data.Dataset):
-    def __init__(self, root: str = "OpenGF_test", count: int = 650):
-        self.root, self.count = root, count
+    def __init__(self, root: str = "OpenGF_test", count: int = 650, coarse: str = "host"):
+        self.root, self.count, self.coarse = root, count, _check_coarse(coarse)
 
     def __len__(self):
         return self.count
@@ -60,15 +80,15 @@ class OpenGFFiles(torch.utils.data.Dataset):
         import os
         arr = np.load(os.path.join(self.root, "%d.npy" % (item + 1)))
         cpath = os.path.join(self.root, "centers", "%d.npy" % (item + 1))
-        return make_sample(arr, np.load(cpath) if os.path.exists(cpath) else None)
+        return make_sample(arr, np.load(cpath) if os.path.exists(cpath) else None, self.coarse)
 
 
 class SyntheticDEM(torch.utils.data.Dataset):
     """Seeded terrain patches (500 m square, smooth relief) with box-shaped 'buildings' and noisy 'vegetation' lifted
     above the ground in the DSM; DEM rows are the ground under the same (x, y)."""
 
-    def __init__(self, n: int, seed0: int = 0, points: int = 4000):
-        self.n, self.seed0, self.points = n, seed0, points
+    def __init__(self, n: int, seed0: int = 0, points: int = 4000, coarse: str = "host"):
+        self.n, self.seed0, self.points, self.coarse = n, seed0, points, _check_coarse(coarse)
 
     def __len__(self):
         return self.n
@@ -86,15 +106,20 @@ class SyntheticDEM(torch.utils.data.Dataset):
         lift = np.where(veg & (lift == 0), rng.uniform(1, 12, size=self.points), lift)
         dsm = np.concatenate([xy, (ground + lift)[:, None]], axis=1)
         dem = np.concatenate([xy, ground[:, None]], axis=1)
-        return make_sample(np.concatenate([dsm, dem], axis=1), np.array([250.0, 250.0, 0.0]))
+        return make_sample(np.concatenate([dsm, dem], axis=1), np.array([250.0, 250.0, 0.0]), self.coarse)
 
 
 @torch.no_grad()
-def evaluate_samples(net, samples: Sequence[tuple], device: Optional[torch.device] = None) -> np.ndarray:
-    """One batch of samples -> [B, 3] (chamfer, height MAE, height MSE), each x 1000 (evaluate_open_gf.py:57-68)."""
+def evaluate_samples(net, samples: Sequence[tuple], device: Optional[torch.device] = None, coarse: str = "host") -> np.ndarray:
+    """One batch of samples -> [B, 3] (chamfer, height MAE, height MSE), each x 1000 (evaluate_open_gf.py:57-68).
+    coarse="gpu": the samples come from a coarse="gpu" dataset (their second entry is the raw DEM) and the coarse DEMs of the
+    whole batch are built here, in one batched call."""
     device = device or next(net.parameters()).device
     dsms = [s[0].to(device) for s in samples]
-    coarse = [s[1].to(device) for s in samples]
+    if _check_coarse(coarse) == "gpu":
+        coarse = coarse_dems([s[1] for s in samples], device)
+    else:
+        coarse = [s[1].to(device) for s in samples]
     dems = [s[2].to(device) for s in samples]
     preds = net.forward_batch(dsms, coarse)
     rows = torch.zeros(len(samples), 3, dtype=torch.float64)
@@ -115,7 +140,7 @@ def evaluate_dem_generation(net, dataset, batch_samples: int = 8, verbose: bool 
     rows: List[np.ndarray] = []
     for lo in range(0, len(mine), batch_samples):
         ids = mine[lo:lo + batch_samples]
-        r = evaluate_samples(net, [dataset[i] for i in ids])
+        r = evaluate_samples(net, [dataset[i] for i in ids], coarse=getattr(dataset, "coarse", "host"))
         full = np.zeros((len(ids), sdist.ROW_WIDTH))
         full[:, sdist.COL_PAIR] = ids
         full[:, 1:4] = r

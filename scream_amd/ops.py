@@ -390,6 +390,27 @@ def render_depth_bwd(dimgs: torch.Tensor, argmax: torch.Tensor, src: torch.Tenso
     return dsrc
 
 
+def voxel_down_sample_packed(xyz: torch.Tensor, row0: torch.Tensor, length: torch.Tensor, max_len: int, voxel: torch.Tensor,
+                             want_counts: bool = False) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+    """scream_voxel_down_sample on packed rows: xyz [rows,3] fp32, row0 / length int32 [B] and voxel float64 [B] on the device.
+    Returns (out_xyz [rows,3], out_len int32 [B], out_count int32 [rows] or None), all on the device: cloud c's voxels are rows
+    row0[c] .. + out_len[c] of out_xyz (the rows behind are not written), out_len[c] = -1 for a refused cloud.  No host sync."""
+    n_clouds, rows, dev = row0.shape[0], xyz.shape[0], xyz.device
+    need = _lib.load().scream_voxel_workspace_bytes(rows, n_clouds)
+    if need < 0:
+        raise _lib.ScreamHipError("scream_voxel_workspace_bytes(%d, %d): invalid argument" % (rows, n_clouds))
+    workspace = torch.empty(max(need, 16), device=dev, dtype=torch.uint8)
+    out_xyz = torch.empty(max(rows, 1), 3, device=dev, dtype=torch.float32)
+    out_len = torch.empty(max(n_clouds, 1), device=dev, dtype=torch.int32)
+    out_count = torch.empty(max(rows, 1), device=dev, dtype=torch.int32) if want_counts else None
+    xyz_p = _p(xyz) if rows else out_xyz.data_ptr()  # an all-empty batch still reports its lengths
+    check(_lib.load().scream_voxel_down_sample(xyz_p, _p(row0, torch.int32), _p(length, torch.int32), n_clouds, int(max_len),
+                                               _p(voxel, torch.float64), _p(out_xyz), _p(out_len, torch.int32),
+                                               _p(out_count, torch.int32), _p(workspace, torch.uint8), workspace.numel(), _stream()),
+          "scream_voxel_down_sample")
+    return out_xyz[:rows], out_len[:n_clouds], (out_count[:rows] if want_counts else None)
+
+
 def kabsch_corr(src, ref, src_row0, src_len, ref_row0, idx, valid, s, c) -> Tuple[torch.Tensor, torch.Tensor]:
     """Returns (T [n_pairs,4,4], n_corr int32 [n_pairs])."""
     n_pairs = s.shape[0]
