@@ -33,10 +33,6 @@ SOURCES = {
     "render.hip": ["-ffp-contract=off"],
     "voxel.hip": ["-ffp-contract=off"],
 }
-# SCREAM_HIPCC_EXTRA="file.hip:-flag,-flag;file2.hip:-flag": extra compiler flags per source (experiments; empty in the product)
-EXTRA_DEFINES = {}
-for _item in filter(None, os.environ.get("SCREAM_HIPCC_EXTRA", "").split(";")):
-    EXTRA_DEFINES[_item.split(":")[0]] = _item.split(":", 1)[1].split(",")
 ASM_LOADS = ("gemm_split.hip", "tail_split.hip", "proj_ring.hip")  # verified after code generation, see verify_one
 # kernels that must not touch scratch at all: a spill inside a ring stage costs a round trip per stage, and hipcc orders a scratch
 # reload against the LDS-DMA in flight with vmcnt(0) -- the ring would drain once per stage (the layer tail's history)
@@ -72,7 +68,6 @@ def build(force: bool = False, verbose: bool = False, out: str = None) -> str:
 
     def compile_one(item):
         src, extra = item
-        extra = extra + EXTRA_DEFINES.get(src, [])
         obj = os.path.join(objdir, src.replace(".hip", ".o"))
         cmd = common + extra + ["-c", os.path.join(CSRC, src), "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
@@ -90,7 +85,7 @@ def build(force: bool = False, verbose: bool = False, out: str = None) -> str:
         sys.path.insert(0, os.path.join(HERE, "..", "tools"))
         import asm_inflight_check as chk
         asm = os.path.join(objdir, src.replace(".hip", ".s"))
-        cmd = common + SOURCES[src] + EXTRA_DEFINES.get(src, []) + ["-S", "--cuda-device-only", os.path.join(CSRC, src), "-o", asm]
+        cmd = common + SOURCES[src] + ["-S", "--cuda-device-only", os.path.join(CSRC, src), "-o", asm]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("hipcc -S failed for %s:\n%s" % (src, r.stderr))

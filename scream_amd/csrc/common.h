@@ -88,6 +88,6 @@ __device__ __forceinline__ float elu1(float x) {
     return elu1s(x, Elu1Consts{1.0f, 1.44269502162933349609375f, 1.925963033500011e-08f});
 }
 
-#ifndef SCREAM_MAX_GRID
-#define SCREAM_MAX_GRID 256  // blocks of the persistent grids: one per CU (tuning builds: fewer)
-#endif
+// blocks of the persistent grids: one per CU (fewer measured slower: 240 / 224 blocks 1 872 / 1 882 pairs/s against 1 898,
+// profiles/r04_persistent_grid_sweep.txt)
+constexpr int SCREAM_MAX_GRID = 256;

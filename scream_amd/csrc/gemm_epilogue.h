@@ -226,11 +226,6 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[8], float* slabs, in
 #pragma unroll
                     for (int c = 0; c < 4; ++c) vv[i][c] = fmaxf(vv[i][c] + p0[c], 0.f);
             }
-#ifdef X3_ABLATE
-            if (X3_ABLATE & 64) {  // tuning aid: keep the arithmetic, drop the stores
-                if (vv[0][0] + vv[1][1] + vv[2][2] + vv[3][3] != 123.456f) continue;
-            }
-#endif
 #pragma unroll
             for (int i = 0; i < 4; ++i) *reinterpret_cast<f32x4*>(C + (row0 + i) * ldc + col) = vv[i];
         }

@@ -36,40 +36,20 @@
 //     the loop back edge and would wait for vmcnt(0) everywhere.  Counted waits are used only where nothing but loads
 //     is in flight; the first barrier of an output tile, behind the previous epilogue's stores, drains the queue.
 //   * The two waves of a SIMD are not symmetric: the older one gets the matrix pipe first (s_memtime stamps,
-//     tools/gemm_stamps.py: 1.8 k cycles for its first 48 MFMAs against 3.8 k for the younger wave's), so the younger
+//     tools/gemm_stamps.py, removed after 9d64f79: 1.8 k cycles for its first 48 MFMAs against 3.8 k for the younger wave's), so the younger
 //     waves (4-7) do their operand split AFTER the barrier, where they would be starved anyway, the older ones before.
 //   * A dedicated 64 KiB LDS region holds the epilogue slabs, so the first k-tile of the next output tile is already
 //     in flight during the epilogue (for every epilogue kind).
-// What was measured and rejected on the way (tools/gemm_ablate.py, tools/ubench/, profiles/r01_x3_ablation.txt): two
+// What was measured and rejected on the way (profiles/r01_x3_ablation.txt, profiles/r03_gemm_ablation_h2.txt): two
 // independent 128-row blocks per CU (doubles the W traffic; same speed), one wave per SIMD with 64-row wave tiles and
 // 512 registers (slower: a lone in-order wave does not keep the pipe full), spreading the fragment reads between the
 // MFMAs, starting the CUs out of phase, non-temporal stores.  On this chip a wave that issues MFMAs back to back
 // starves the LDS and vector-memory instructions of the other wave on its SIMD (not its VALU), which is why the
 // k-tile time is close to the SUM of the MFMA, LDS, VMEM and VALU issue times rather than their maximum.
-// Tuning aid (tools/gemm_ablate.py builds variants): bit 0 no epilogue, 1 no W DMA after the first k-tile, 2 no A loads
-// after the first, 3 no MFMAs, 4 no LDS fragment reads, 5 no operand split, 6 no epilogue stores, 7 no key/value-tile epilogue
-// (the fused K^T V reduce), 8 no query-tile epilogue (elu + 1 and the fragment-major stores).  Always 0 in libscream_hip.so.
-#ifndef X3_ABLATE
-#define X3_ABLATE 0
-#endif
 #include <type_traits>
 
 #include "gemm_epilogue.h"
 #include "split.h"
-
-#ifdef X3_STAMPS  // tuning aid: s_memtime stamps of one output tile per block (tools/gemm_stamps.py)
-__device__ long long gemm_stamps[256 * 8 * 160];
-extern "C" int scream_gemm_stamps_read(long long* host) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(gemm_stamps), sizeof(long long) * 256 * 8 * 160);
-}
-#define STAMP(slot)                                                                                    \
-    do {                                                                                               \
-        if (stamp_on && lane == 0 && (slot) < 160)                                                      \
-            gemm_stamps[((int)blockIdx.x * 8 + wave) * 160 + (slot)] = __builtin_amdgcn_s_memtime();     \
-    } while (0)
-#else
-#define STAMP(slot) do {} while (0)
-#endif
 
 namespace {
 
@@ -175,15 +155,7 @@ __global__ __launch_bounds__(XTHREADS, 2) void gemm_split_kernel(const float* __
 
     V pa_s0[NP];  // split planes of the first 16-deep step of the k-tile about to be computed
     const bool late = wave >= 4;  // the second wave of each SIMD
-#ifdef X3_STAMPS
-    int tile_no = 0;
-#endif
     for (;;) {
-#ifdef X3_STAMPS
-        const bool stamp_on = tile_no == 2 && blockIdx.x < 256;
-        ++tile_no;
-        STAMP(0);
-#endif
         f32x16 acc[8];
 #pragma unroll
         for (int tn = 0; tn < 8; ++tn)
@@ -203,15 +175,11 @@ __global__ __launch_bounds__(XTHREADS, 2) void gemm_split_kernel(const float* __
 #pragma unroll
             for (int tn = 0; tn < 8; ++tn) {
                 const int cur = tn & 1, nxt = cur ^ 1;
-                if (s * 8 + tn + 1 < 16 && !(X3_ABLATE & 16)) {  // fragments of the next (step, N-tile), one group ahead
+                if (s * 8 + tn + 1 < 16) {  // fragments of the next (step, N-tile), one group ahead
                     const int s2 = (s * 8 + tn + 1) >> 3, t2 = (s * 8 + tn + 1) & 7;
 #pragma unroll
                     for (int p = 0; p < NP; ++p)
                         fb[nxt][p] = *reinterpret_cast<const V*>(wb + p * PLANE_BYTES + t2 * 32 * 64 + boff[s2]);
-                }
-                if (X3_ABLATE & 8) {
-                    acc[tn][0] += (float)pa[0][0] + (float)pa[NP - 1][1] + (float)fb[cur][0][0] + (float)fb[cur][NP - 1][0];
-                    continue;
                 }
                 if (decltype(tr)::value) SP::template products<false>(acc[tn], fb[cur], pa, acc[tn]);
                 else SP::template products<true>(acc[tn], pa, fb[cur], acc[tn]);
@@ -223,15 +191,8 @@ __global__ __launch_bounds__(XTHREADS, 2) void gemm_split_kernel(const float* __
             }
         };
         auto split_of = [&](const f32x4& lo, const f32x4& hi, V (&pa)[NP]) {
-            if (X3_ABLATE & 32) {
-                pa[0] = __builtin_bit_cast(V, lo);
-                pa[1] = __builtin_bit_cast(V, hi);
-                pa[NP - 1] = pa[0];
-            } else if (SP::SCALED) {
-                split8<SP>(lo * a_scale, hi * a_scale, pa);  // exact: a power of two
-            } else {
-                split8<SP>(lo, hi, pa);
-            }
+            if (SP::SCALED) split8<SP>(lo * a_scale, hi * a_scale, pa);  // exact: a power of two
+            else split8<SP>(lo, hi, pa);
         };
         // (always_inline: with two copies of the k-loop in the kernel hipcc otherwise leaves `step` out of line in some
         // instantiations -- operands passed through memory, behind the back of the hand-counted waits; the build's checker refused it)
@@ -243,10 +204,8 @@ __global__ __launch_bounds__(XTHREADS, 2) void gemm_split_kernel(const float* __
             // the previous epilogue's STORES are in the queue there, and a counted wait is only sound among loads --
             // stores complete out of order with respect to older loads (tools/gemm_soak.py caught vmcnt(4 + #stores)
             // returning with a load still in flight, once in ~10^8 tile boundaries).
-            STAMP(4 + kt * 4 + 0);
             if (FIRST || TAIL == 2) ring_barrier<0>();
             else ring_barrier<4>();
-            STAMP(4 + kt * 4 + 1);
             if (FIRST || late) {  // the younger waves of each SIMD split their first half here: they would only be
                 asm volatile("" : "+v"(ac[0]));  // starved by the older wave's MFMAs for that long anyway, and the
                 asm volatile("" : "+v"(ac[1]));  // barrier is released that much earlier
@@ -258,10 +217,9 @@ __global__ __launch_bounds__(XTHREADS, 2) void gemm_split_kernel(const float* __
 #pragma unroll
             for (int p = 0; p < NP; ++p) fb[0][p] = *reinterpret_cast<const V*>(wb + p * PLANE_BYTES + boff[0]);
             groups(tr, wb, 0, pa_s0, fb);
-            STAMP(4 + kt * 4 + 2);
-            if (TAIL <= 1 && !(X3_ABLATE & 2)) dma_w(n0, stage ^ 1, kt + 1);
+            if (TAIL <= 1) dma_w(n0, stage ^ 1, kt + 1);
             __builtin_amdgcn_sched_barrier(0);  // the counted waits rely on this issue order: D(kt+1), then A(kt+2)
-            if (TAIL == 0 && !(X3_ABLATE & 4)) load_a(an2, kt + 2);
+            if (TAIL == 0) load_a(an2, kt + 2);
             __builtin_amdgcn_sched_barrier(0);
             V pa_s1[NP];
             asm volatile("" : "+v"(ac[2]));
@@ -269,7 +227,6 @@ __global__ __launch_bounds__(XTHREADS, 2) void gemm_split_kernel(const float* __
             split_of(ac[2], ac[3], pa_s1);
             __builtin_amdgcn_sched_barrier(0);
             groups(tr, wb, 1, pa_s1, fb);
-            STAMP(4 + kt * 4 + 3);
             if (TAIL <= 1 && !late) {  // A(kt+1) is older than what was requested above: wait for it alone, split its first half
                 if (TAIL == 0) __builtin_amdgcn_s_waitcnt(0x0F70 | (WPW + 4)); else __builtin_amdgcn_s_waitcnt(0x0F70 | WPW);  // vmcnt only
                 asm volatile("" : "+v"(an1[0]));
@@ -311,7 +268,6 @@ __global__ __launch_bounds__(XTHREADS, 2) void gemm_split_kernel(const float* __
             k_loop(std::integral_constant<bool, false>{});
         }
 
-        STAMP(1);
         // next output tile: its first k-tile lands under the epilogue (the slabs have their own LDS region)
         const unsigned v_next = v + gridDim.x;
         const bool has_next = v_next < total_tiles;
@@ -326,46 +282,34 @@ __global__ __launch_bounds__(XTHREADS, 2) void gemm_split_kernel(const float* __
             ga = a_ptr(m0, rows_ok);
         }
         if (has_next) request_first();
-        const bool skip_epi = (X3_ABLATE & 1) || ((X3_ABLATE & 128) && EPI == SCREAM_EPI_QKV && n0_cur >= ep.n_act) ||
-                              ((X3_ABLATE & 256) && CAN_TR && tr_cur);
-        if (skip_epi) {
-            float keep = 0.f;
+        if (SP::SCALED) {  // back to true units: 2^-(a_exp + w_exp), exact
 #pragma unroll
-            for (int tn = 0; tn < 8; ++tn)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) keep += acc[tn][e];
-            if (keep == 123.456f) C[0] = keep;
-        } else {
-            if (SP::SCALED) {  // back to true units: 2^-(a_exp + w_exp), exact
-#pragma unroll
-                for (int tn = 0; tn < 8; ++tn) acc[tn] *= c_scale;
-            }
-            if (CAN_TR && tr_cur) {
-                // Q' = elu(q) + 1, fragment-major (SCREAM_ACT_FRAG), straight from the transposed accumulators: register
-                // 4a + b of lane (r, half) in tile tn is feature 32 tn + 8 a + 4 half + b of row r, i.e. float
-                // ((tn * 4 + a) * 64 + lane) * 4 + b of the wave's 32-row group -- one contiguous 1 KiB per store instruction,
-                // no LDS slab, no transposition (the slab epilogue was a third of this kernel's time on query tiles,
-                // profiles/r03_gemm_ablation_h2.txt)
-                if (rows_cur) {
-                    float* cg = C + (m0_cur + wave * 32) * 256 + lane * 4;
-#pragma unroll
-                    for (int tn = 0; tn < 8; ++tn)
-#pragma unroll
-                        for (int a = 0; a < 4; ++a) {
-                            f32x4 o;
-#pragma unroll
-                            for (int b = 0; b < 4; ++b) {
-                                const float x = acc[tn][4 * a + b];
-                                o[b] = elu1(x);
-                            }
-                            *reinterpret_cast<f32x4*>(cg + (tn * 4 + a) * 256) = o;
-                        }
-                }
-            } else {
-                gemm_epilogue<EPI, XWAVES, SP::SCALED>(acc, slabs, wave, lane, tid, rows_cur, m0_cur, n0_cur, ep, C, ldc);
-            }
+            for (int tn = 0; tn < 8; ++tn) acc[tn] *= c_scale;
         }
-        STAMP(2);
+        if (CAN_TR && tr_cur) {
+            // Q' = elu(q) + 1, fragment-major (SCREAM_ACT_FRAG), straight from the transposed accumulators: register
+            // 4a + b of lane (r, half) in tile tn is feature 32 tn + 8 a + 4 half + b of row r, i.e. float
+            // ((tn * 4 + a) * 64 + lane) * 4 + b of the wave's 32-row group -- one contiguous 1 KiB per store instruction,
+            // no LDS slab, no transposition (the slab epilogue was a third of this kernel's time on query tiles,
+            // profiles/r03_gemm_ablation_h2.txt)
+            if (rows_cur) {
+                float* cg = C + (m0_cur + wave * 32) * 256 + lane * 4;
+#pragma unroll
+                for (int tn = 0; tn < 8; ++tn)
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) {
+                        f32x4 o;
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) {
+                            const float x = acc[tn][4 * a + b];
+                            o[b] = elu1(x);
+                        }
+                        *reinterpret_cast<f32x4*>(cg + (tn * 4 + a) * 256) = o;
+                    }
+            }
+        } else {
+            gemm_epilogue<EPI, XWAVES, SP::SCALED>(acc, slabs, wave, lane, tid, rows_cur, m0_cur, n0_cur, ep, C, ldc);
+        }
         if (!has_next) break;
         v = v_next;
     }

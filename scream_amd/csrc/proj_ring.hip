@@ -36,21 +36,10 @@
 
 #include "ring.h"
 
-#ifndef P_PF
-#define P_PF 2  // register sets of weight fragments: fragments are read P_PF - 1 MFMA groups ahead (a third set does not fit: 512 registers)
-#endif
-#ifndef P_LB
-#define P_LB 2  // x segments per load batch at a tile boundary (two batches in flight)
-#endif
-#ifndef P_NT
-#define P_NT 3  // non-temporal hint on: 1 the x row loads, 2 the Q' stores, 4 the K^T V partial stores
-#endif
-#ifndef P_ABLATE
-#define P_ABLATE 0  // tuning aid (SCREAM_HIPCC_EXTRA builds): 1 no rides (epilogues dropped), 2 no MFMA, 8 no W DMA after the first two stages (-DT_ABLATE=4: no LDS fragment reads);
-                    // inside the rides: 32 elu + 1 without its exponential, 64 no Q' stores, 128 no K'^T V products, 256 no operand splits of K' and V, 512 no slab / partial traffic
-#endif
-
 namespace {
+
+constexpr int P_PF = 2;  // register sets of weight fragments: fragments are read P_PF - 1 MFMA groups ahead (a third set does not fit: 512 registers)
+constexpr int P_LB = 2;  // x segments per load batch at a tile boundary (two batches in flight)
 
 constexpr int P_KV_ELEMS = (SCREAM_HEAD_DIM + 1) * SCREAM_HEAD_DIM;  // 1056
 constexpr int P_SLAB_BYTES = 4 * P_KV_ELEMS * 4;                      // one K^T V tile + Ksum per wave
@@ -98,7 +87,6 @@ __global__ __launch_bounds__(TT, 1) void proj_ring_kernel(ProjArgs pa) {
 
     unsigned q = 0;  // ring stages consumed so far
     auto dma_piece = [&](unsigned qq, int u) __attribute__((always_inline)) {
-        if ((P_ABLATE & 8) && qq >= 2) return;
         const unsigned img = (unsigned)(s0 + qq) % (unsigned)S, slot = qq % (unsigned)T_SLOTS;
         const char* sbase = pa.Wimg + (size_t)img * STAGE + (wave * PIECES + (u & ~3)) * 1024;
         dma_1k(sbase + v_lane16, smem + slot * STAGE + (wave * PIECES + (u & ~3)) * 1024, u & 3);
@@ -141,8 +129,7 @@ __global__ __launch_bounds__(TT, 1) void proj_ring_kernel(ProjArgs pa) {
             for (int k = 0; k < LB; ++k)
 #pragma unroll
                 for (int a = 0; a < 4; ++a)
-                    raw[b & 1][k][a] = (P_NT & 1) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + rg * 8192 + ((blk0 + k) * 4 + a) * 256))
-                                                  : *reinterpret_cast<const f32x4*>(g + rg * 8192 + ((blk0 + k) * 4 + a) * 256);
+                    raw[b & 1][k][a] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + rg * 8192 + ((blk0 + k) * 4 + a) * 256));
         };
         request(0);
 #pragma unroll
@@ -190,15 +177,9 @@ __global__ __launch_bounds__(TT, 1) void proj_ring_kernel(ProjArgs pa) {
         for (int e = 0; e < 16; ++e) z[e] = 0.f;
 #pragma unroll
         for (int rg = 0; rg < 2; ++rg) {
-            if (P_ABLATE & 2) {
-                if (zero) a[rg] = z;
-                a[rg][0] += (float)w[0][0] + (float)w[NP - 1][1] + (float)xp[rg][g][0][0] + (float)xp[rg][g][NP - 1][1];
-                continue;
-            }
             if (KIND == 0) SP::products(a[rg], w, xp[rg][g], zero ? z : a[rg]);
             else SP::products(a[rg], xp[rg][g], w, zero ? z : a[rg]);
         }
-        if (P_ABLATE & 2) return;
         // first MFMA, then the prefetch reads of the next fragments (one per plane), then the other MFMAs with NV ride slots each
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, NP, 0);
@@ -233,7 +214,7 @@ __global__ __launch_bounds__(TT, 1) void proj_ring_kernel(ProjArgs pa) {
                 for (int u = (g - 9) * 2; u < (g - 8) * 2; ++u)
                     if (u < PIECES) dma_piece(q + 2, u);
             }
-            if (!(P_ABLATE & 1)) ride(g);
+            ride(g);
             group(kind, a, wf[g % P_PF], g, g == 0);
         }
         ++q;
@@ -249,18 +230,17 @@ __global__ __launch_bounds__(TT, 1) void proj_ring_kernel(ProjArgs pa) {
 #pragma unroll
             for (int rg = 0; rg < 2; ++rg)
 #pragma unroll
-                for (int e = 0; e < 2; ++e) t[rg][2 * g + e] = (P_ABLATE & 32) ? fmaxf(__builtin_fmaf(t[rg][2 * g + e], pa.ec.c, 1.0f), 0.25f) : elu1s(t[rg][2 * g + e], pa.ec);
+                for (int e = 0; e < 2; ++e) t[rg][2 * g + e] = elu1s(t[rg][2 * g + e], pa.ec);
         }
         if (g == 8) {
             __builtin_amdgcn_sched_barrier(0);
-            if (q_pend_ok && (!(P_ABLATE & 64) || t[0][0] == 123.456f)) {
+            if (q_pend_ok) {
 #pragma unroll
                 for (int rg = 0; rg < 2; ++rg)
 #pragma unroll
                     for (int a = 0; a < 4; ++a) {
                         const f32x4 o = {t[rg][4 * a], t[rg][4 * a + 1], t[rg][4 * a + 2], t[rg][4 * a + 3]};
-                        if (P_NT & 2) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(q_pend + rg * 8192 + a * 256));
-                        else *reinterpret_cast<f32x4*>(q_pend + rg * 8192 + a * 256) = o;
+                        __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(q_pend + rg * 8192 + a * 256));
                     }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -273,10 +253,10 @@ __global__ __launch_bounds__(TT, 1) void proj_ring_kernel(ProjArgs pa) {
         if (g == 0) ks = 0.f;
 #pragma unroll
         for (int rg = 0; rg < 2; ++rg) {
-            float a = (P_ABLATE & 32) ? fmaxf(__builtin_fmaf(t[rg][g], pa.ec.c, 1.0f), 0.25f) : elu1s(t[rg][g], pa.ec);
+            float a = elu1s(t[rg][g], pa.ec);
             if (decltype(mask)::value && (g & 3) + 8 * (g >> 2) + 32 * rg >= valid) a = 0.f;  // row mfma32_row(g, half) + 32 rg of the wave's 64 (valid carries the half)
             ks += a;
-            if (P_ABLATE & 256) kp[rg][g >> 3][0][g & 7] = (_Float16)a; else SplitH2::split1s(a, pa.kv_sk, g & 7, kp[rg][g >> 3]);
+            SplitH2::split1s(a, pa.kv_sk, g & 7, kp[rg][g >> 3]);
         }
         if (g == 15) ks += __shfl_xor(ks, 32);
     };
@@ -290,23 +270,18 @@ __global__ __launch_bounds__(TT, 1) void proj_ring_kernel(ProjArgs pa) {
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
                     const int i = 8 * s2 + 2 * (g & 3) + e;
-                    if (P_ABLATE & 256) vp[rg][0][i & 7] = (_Float16)t[rg][i]; else SplitH2::split1s(t[rg][i], pa.kv_cv, i & 7, vp[rg]);
+                    SplitH2::split1s(t[rg][i], pa.kv_cv, i & 7, vp[rg]);
                 }
             if ((g & 3) == 3) {
                 f32x16 z;
 #pragma unroll
                 for (int e = 0; e < 16; ++e) z[e] = 0.f;
-                if (P_ABLATE & 128) {
-                    kv = s2 == 0 ? z : kv;
-                    kv[0] += (float)kp[0][s2][0][0] + (float)vp[0][0][0] + (float)kp[1][s2][1][1] + (float)vp[1][1][1];
-                } else {
-                    SplitH2::products(kv, kp[0][s2], vp[0], s2 == 0 ? z : kv);
-                    SplitH2::products(kv, kp[1][s2], vp[1], kv);
-                }
+                SplitH2::products(kv, kp[0][s2], vp[0], s2 == 0 ? z : kv);
+                SplitH2::products(kv, kp[1][s2], vp[1], kv);
             }
         }
         if (g == 9) kv *= pa.kv_inv;  // exact: a power of two (1 / v_length is applied once, in scream_kv_finalize_image)
-        if (g >= 10 && g < 14 && (!(P_ABLATE & 512) || kv[0] == 123.456f)) {
+        if (g >= 10 && g < 14) {
             float* sw = slabs + wave * P_KV_ELEMS;
 #pragma unroll
             for (int e = 4 * (g - 10); e < 4 * (g - 9); ++e) sw[mfma32_row(e, half) * 32 + r] = kv[e];  // [d][v]
@@ -317,10 +292,9 @@ __global__ __launch_bounds__(TT, 1) void proj_ring_kernel(ProjArgs pa) {
     auto ride_kvstore = [&](int g) __attribute__((always_inline)) {
         if (g > 8) return;
         const int i = (wave & 1) * 64 + lane + 128 * g;
-        if (i < P_KV_ELEMS && part_pend_ok && !(P_ABLATE & 512)) {
+        if (i < P_KV_ELEMS && part_pend_ok) {
             const float* s2 = slabs + (wave & ~1) * P_KV_ELEMS + i;
-            if (P_NT & 4) __builtin_nontemporal_store(s2[0] + s2[P_KV_ELEMS], part_pend + i);
-            else part_pend[i] = s2[0] + s2[P_KV_ELEMS];
+            part_pend[i] = s2[0] + s2[P_KV_ELEMS];  // a plain store: non-temporal, kv_finalize_image reads the partials from memory (profiles/r04_nontemporal_and_stash.txt)
         }
     };
 
@@ -369,30 +343,18 @@ __global__ __launch_bounds__(TT, 1) void proj_ring_kernel(ProjArgs pa) {
     }
     // ---- the pipeline's end, in the open
     __builtin_amdgcn_sched_barrier(0);
-    if (!(P_ABLATE & 1)) {
-        if (prev == 1) {
+    if (prev == 1) {
 #pragma unroll
-            for (int g = 0; g < 9; ++g) ride_q(acc[1], g);
-        } else if (prev == 2) {
-            lds_only_barrier();  // every wave has read the previous head's slabs (the ride of the stage just finished)
+        for (int g = 0; g < 9; ++g) ride_q(acc[1], g);
+    } else if (prev == 2) {
+        lds_only_barrier();  // every wave has read the previous head's slabs (the ride of the stage just finished)
 #pragma unroll
-            for (int g = 0; g < 14; ++g) ride_v(acc[1], g);
-            lds_only_barrier();
+        for (int g = 0; g < 14; ++g) ride_v(acc[1], g);
+        lds_only_barrier();
 #pragma unroll
-            for (int g = 0; g < 9; ++g) ride_kvstore(g);
-        }
+        for (int g = 0; g < 9; ++g) ride_kvstore(g);
     }
 #undef LAMBDA
-    if (P_ABLATE & 1) {  // keep the accumulators alive
-        float keep = 0.f;
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int rg = 0; rg < 2; ++rg)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) keep += acc[b][rg][e];
-        if (keep == 123.456f) pa.kv_partial[0] = keep;
-    }
     VM_WAIT(0);  // the ring's last two stages (requested past the end) must have landed before the LDS is released
 }
 

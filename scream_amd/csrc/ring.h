@@ -3,15 +3,11 @@
 // LDS-DMA pieces with shared address registers, fragment reads, the MFMA group of one 16-deep step with its scheduling
 // pattern, and the inline-asm register loads (scalar base + 32-bit lane offset) with their hand-counted waits.
 #pragma once
-#ifndef T_ABLATE
-#define T_ABLATE 0  // tuning aid (tools/tail_ablate.py); always 0 in libscream_hip.so
-#endif
-#ifndef T_PF
-#define T_PF 3  // register sets of weight fragments: fragments are read T_PF - 1 MFMA groups ahead
-#endif
 #include "split.h"
 
 namespace {
+
+constexpr int T_PF = 3;  // register sets of weight fragments: fragments are read T_PF - 1 MFMA groups ahead
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -29,8 +25,7 @@ template <class SP> constexpr int wave_pieces() { return SP::NP * 4; }
 // this wave -- the DMA pieces of the stage after the one about to be read -- stay in flight across the barrier.
 template <int N>
 __device__ __forceinline__ void ring_barrier() {
-    constexpr int W = (T_ABLATE & 1) ? 0 : N;  // the "no DMA" tuning build has no pieces to leave in flight: it must drain,
-    __builtin_amdgcn_s_waitcnt(0x0070 | (W & 15) | ((W >> 4) << 14));  // or row operands would still be pending at their use
+    __builtin_amdgcn_s_waitcnt(0x0070 | (N & 15) | ((N >> 4) << 14));
     __builtin_amdgcn_s_barrier();
 }
 
@@ -62,11 +57,6 @@ __device__ __forceinline__ void dma_1k(const char* src_lane, char* dst, int k) {
 // one 1 KiB weight fragment (16 bytes per lane) from the current stage
 template <class V>
 __device__ __forceinline__ V ld_frag(const char* p) {
-    if (T_ABLATE & 4) {
-        V v;
-        asm volatile("" : "=v"(v));  // opaque, undefined: keeps the consumers alive without the LDS read
-        return v;
-    }
     return *reinterpret_cast<const V*>(p);
 }
 
@@ -83,11 +73,6 @@ __device__ __forceinline__ void mfma_group(f32x16& acc, const typename SP::vec (
     f32x16 z;
 #pragma unroll
     for (int e = 0; e < 16; ++e) z[e] = 0.f;
-    if (T_ABLATE & 2) {
-        if (zero) acc = z;
-        acc[0] += (float)w[0][0] + (float)w[SP::NP - 1][1] + (float)a[0][0] + (float)a[SP::NP - 1][1];
-        return;
-    }
     SP::products(acc, w, a, zero ? z : acc);
     if (NV < 0) return;
     // first MFMA, then the prefetch reads of the next fragment group (one per plane), then the other MFMAs
@@ -146,9 +131,9 @@ __device__ __forceinline__ void pin(f32x4& v) { asm volatile("" : "+v"(v)); }
 // s_waitcnt vmcnt(N) alone, as an asm statement: ordered against the other asm statements (slab reads, register loads)
 #define VM_WAIT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
 template <int N>
-__device__ __forceinline__ void vm_wait() {  // N = the weight pieces that may stay in flight ("no DMA" tuning build: none exist, drain)
+__device__ __forceinline__ void vm_wait() {  // N = the weight pieces that may stay in flight
     static_assert(N == 0 || N == 4 || N == 8 || N == 12, "");
-    if (N == 0 || (T_ABLATE & 1)) VM_WAIT(0);
+    if (N == 0) VM_WAIT(0);
     else if (N == 4) VM_WAIT(4);
     else if (N == 8) VM_WAIT(8);
     else VM_WAIT(12);

@@ -48,76 +48,30 @@
 // The attention apply itself (12 matrix instructions per head, 3 % of a tile's) stays on the bf16 x 3 split in both
 // instantiations: its KV operand is a data-dependent sum with no useful static bound.
 //
-// Tuning aids (tools/tail_ablate.py builds variants; always 0 in libscream_hip.so): T_ABLATE bit 0 no weight DMA after the
-// first two stages, 1 no MFMAs, 2 no LDS fragment reads, 4 no row loads/stores, 5 no Q', 6 no x, 7 no y stores, 8 no KV
-// operands, 9 no apply rides, 10 no residual adds, 11 every row request goes to the first tile (cache hits).
+// (tools/tail_stamps.py and tools/tail_ablate.py, named below as the source of cycle counts, built time-stamped and ablated
+// variants of this kernel; they were removed with their switches, last present in 9d64f79 -- tools/README.md.)
 #include <type_traits>
 
 #include "ring.h"
 
-#ifndef T_MIX
-// fp16 splits: operand planes by v_fma_mix (split.h: split2s), bit 0 in the FFN's relu / split ride (the default: 103 -> 52 vector
-// instructions per down stage, bit-identical, 1.043 vs 1.046 ms per 333 k-row launch), bit 1 in norm1, the apply and the y planes
-// as well (measured SLOWER, 1.057 ms: the asm statements keep hipcc from packing the norm arithmetic into v_pk_* -- profiles/r04_tail_mix_ab.txt)
-#define T_MIX 1
-#endif
-#ifndef T_RIDE0
-#define T_RIDE0 3  // SplitH2: first MFMA group of a down stage that carries a relu / split pair of the ride (eight groups from there); 0 / 3 / 6: 1.044 / 1.040 / 1.041 ms per 333 k-row launch (profiles/r04_tail_ride0_ab.txt)
-#endif
-#ifndef T_STASH
-#define T_STASH 3  // x segments kept in LDS between their two reads (fp16 kernels; 0: every segment is read twice from memory)
-#endif
-#ifndef T_NT
-#define T_NT 7  // non-temporal hint on: 1 the Q' loads, 2 the y (and next-layer Q') stores, 4 the second (last) read of the x rows, 8 their first read
-#endif
-#ifndef T_DEFER_H2
-#define T_DEFER_H2 2  // SplitH2: MFMA groups of a stage deferred across the barrier into the next stage (1 or 2)
-#endif
-
-// -DT_STAMPS (tools/tail_stamps.py): s_memtime stamps of the phases of the SECOND tile of every block, lane 0 of each wave.
-// Diagnostic build only -- tools/tail_stamps.py runs tools/asm_inflight_check.py on it first: the extra registers can push
-// hipcc into spilling a pending load destination (it did, with one stamp per stage).
-#ifdef T_STAMPS
-#define T_STAMP_SLOTS 24  // 0-5: phase boundaries (64-bit s_memtime); 8-23: low words of the stamps taken at stage tops (TMARK)
-__device__ long long t_stamps[256 * 4 * T_STAMP_SLOTS];
-extern "C" int scream_tail_stamps_read(long long* host) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(t_stamps), sizeof(long long) * 256 * 4 * T_STAMP_SLOTS);
-}
-#define TSTAMP(slot)                                                                                 \
-    do {                                                                                             \
-        if (stamp_on && lane == 0) t_stamps[((int)blockIdx.x * 4 + wave) * T_STAMP_SLOTS + (slot)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-// a stamp that stays in a scalar register until the tile's end: no memory instruction inside the stages
-#define TMARK(i) marks[i] = (unsigned)__builtin_amdgcn_s_memtime()
-#define TMARK2(i, prev) do { marks[prev] = marks[i]; TMARK(i); } while (0)
-#define TMARKS_FLUSH()                                                                               \
-    do {                                                                                             \
-        if (stamp_on && lane == 0)                                                                   \
-            for (int i_ = 0; i_ < 16; ++i_) t_stamps[((int)blockIdx.x * 4 + wave) * T_STAMP_SLOTS + 8 + i_] = marks[i_]; \
-    } while (0)
-#else
-#define TSTAMP(slot) do {} while (0)
-#define TMARK(i) do {} while (0)
-#define TMARK2(i, prev) do {} while (0)
-#define TMARKS_FLUSH() do {} while (0)
-#endif
-
 namespace {
+
+// SplitH2: first MFMA group of a down stage that carries a relu / split pair of the ride (eight groups from there); 0 / 3 / 6: 1.044 / 1.040 / 1.041 ms per 333 k-row launch (profiles/r04_tail_ride0_ab.txt)
+constexpr int T_RIDE0 = 3;
+constexpr int T_STASH = 3;     // x segments kept in LDS between their two reads (fp16 kernels; 0: every segment is read twice from memory)
+constexpr int T_DEFER_H2 = 2;  // SplitH2: MFMA groups of a stage deferred across the barrier into the next stage (1 or 2)
 
 constexpr int TAIL_STAGES = 72;
 constexpr int NEXT_Q_STAGES = 8;  // tail_kernel<SP, true>: the NEXT layer's 256 -> 256 query projection rides behind norm2 (below)
 constexpr int KV_PLANES_BYTES = 8 * 3 * 2 * 1024;            // per cloud: [head][plane][step][lane][8] bf16
 constexpr int KV_IMAGE_BYTES = KV_PLANES_BYTES + 8 * 32 * 4;  // + Ksum [head][32] fp32
 
-// fp16 splits (round 4, T_APPLY_H2): the apply runs on fp16 x 2 as well.  The image then holds, per head, KV_h^T / S * 2^e_h in TWO fp16
+// fp16 splits (round 4): the apply runs on fp16 x 2 as well.  The image then holds, per head, KV_h^T / S * 2^e_h in TWO fp16
 // planes ([head][plane][step][lane][8], 4 KiB per head) with e_h the largest exponent that keeps the head's largest |element| at or
 // below 2^15 -- computed on the device by kv_finalize_image_kernel from the reduced sum itself (a maximum: exact and independent of
 // any order, so batched == single pair stays bitwise) -- and 2^-e_h eight times over in the 32 bytes of head h at KV_H2_SCALE_OFF.
 constexpr int KV_H2_HEAD_BYTES = 2 * 2 * 1024;
 constexpr int KV_H2_SCALE_OFF = 8 * KV_H2_HEAD_BYTES;  // 32 KiB: inside the plane area the bf16 layout fills, unused by this one
-#ifndef T_APPLY_H2
-#define T_APPLY_H2 1  // 0: the attention apply of the fp16 kernels stays on bf16 x 3 (rounds 2-3)
-#endif
 
 struct HeadOps {   // the per-cloud operands of one head's apply, as loaded (Q' travels separately: f32x4 q[4], pieces a = 0 .. 3)
     f32x4 kv[6];   // KV_h^T fragments [plane][step], 16 bytes per lane (fp16 x 2: four of them)
@@ -174,12 +128,8 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
     constexpr int NP = SP::NP;
     constexpr int STAGE = stage_bytes<SP>();
     constexpr int PIECES = wave_pieces<SP>();  // LDS-DMA pieces per wave and stage = what a counted ring wait leaves in flight
-    constexpr bool APPLY_H2 = SP::SCALED && T_APPLY_H2;  // the attention apply on fp16 x 2 planes (image written by kv_finalize_image in that form)
-#ifdef T_NV_MERGE  // tuning aid (tools/tail_stamps.py, T_EXTRA): another ride-slot count
-    constexpr int NV_MERGE = T_NV_MERGE;
-#else
+    constexpr bool APPLY_H2 = SP::SCALED;  // the attention apply on fp16 x 2 planes (image written by kv_finalize_image in that form)
     constexpr int NV_MERGE = SP::NPROD >= 6 ? 6 : 8;  // ride slots behind every MFMA of a merge stage (32 cycles / 4 per VALU issue)
-#endif
     // The last ND MFMA groups of every stage are DEFERRED across the barrier (below): 192 cycles of work on register operands
     // must cover the barrier skew and the first fragment reads of the next stage -- one group of six bf16 products, two groups
     // of three fp16 products.
@@ -210,7 +160,6 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
     // weight pieces: uniform (scalar) source address + the 32-bit lane offset.  A per-lane 64-bit pointer kept across the
     // kernel was spilled by hipcc and reloaded from scratch in EVERY stage -- behind a vmcnt(0) that drained the ring.
     auto dma_piece = [&](unsigned q, int u) {
-        if ((T_ABLATE & 1) && q >= 2) return;
         const unsigned src = q % (unsigned)N_STAGES, slot = q % (unsigned)T_SLOTS;
         const char* sbase = Wimg + (size_t)src * STAGE + (wave * PIECES + (u & ~3)) * 1024;
         dma_1k(sbase + v_lane16, smem + slot * STAGE + (wave * PIECES + (u & ~3)) * 1024, u & 3);
@@ -229,12 +178,9 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
     // the uniform part of the address of segment seg in the 32-row group starting at float `grp`
     auto seg_base = [&](const float* base, int64_t grp, int seg) { return base + grp + seg * 1024; };
     auto req_q = [&](f32x4 (&qb)[4], int64_t grp, int h) {  // Q' of head h: the one operand that comes from HBM
-        if (T_ABLATE & (16 | 32)) return;
-        if (T_ABLATE & 2048) grp = (int64_t)wave * 32 * SCREAM_D_MODEL;  // tuning aid: always the first tile's rows (cache hits)
-        ld_asm4<1024, (T_NT & 1) != 0>(qb, seg_base(Q, grp, h), v_lane16);
+        ld_asm4<1024, true>(qb, seg_base(Q, grp, h), v_lane16);
     };
     auto req_head = [&](HeadOps& o, const char* kvc, int h) {  // KV^T fragments and Ksum of head h: L2-hot per-cloud data
-        if (T_ABLATE & (16 | 256)) return;
         f32x4 (&kv4)[4] = reinterpret_cast<f32x4 (&)[4]>(o.kv[0]);
         if (APPLY_H2) {
             ld_asm4<1024>(kv4, kvc + h * KV_H2_HEAD_BYTES, v_lane16);
@@ -246,10 +192,8 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
         }
         ld_asm4<32>(o.ks, kvc + KV_PLANES_BYTES + 128 * h, v_half16);
     };
-    auto req_x = [&](f32x4 (&xs)[4], int64_t grp, int blk, auto second) {  // second: the FFN's read (norm2 residual), the last use of the rows
-        if (T_ABLATE & (16 | 64)) return;
-        if (T_ABLATE & 2048) grp = (int64_t)wave * 32 * SCREAM_D_MODEL;
-        ld_asm4<1024, (T_NT & (decltype(second)::value ? 4 : 8)) != 0>(xs, seg_base(xres, grp, blk), v_lane16);
+    auto req_x = [&](f32x4 (&xs)[4], int64_t grp, int blk, auto second) {  // second: the FFN's read (norm2 residual), the last use of the rows: non-temporal
+        ld_asm4<1024, decltype(second)::value>(xs, seg_base(xres, grp, blk), v_lane16);
     };
     auto pin_head = [&](HeadOps& o) {
 #pragma unroll
@@ -261,10 +205,7 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
     // the residual x joins an accumulator tile: plain add, or (SplitH2) fma with the tile's unit c
     auto add_x4 = [&](f32x16& t, const f32x4 (&xs)[4], int a, float c) {  // one quarter (registers 4a .. 4a + 3)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float xv = (T_ABLATE & 16) ? 1.0f : xs[a][k];
-            t[4 * a + k] = SP::SCALED ? __builtin_fmaf(xv, c, t[4 * a + k]) : t[4 * a + k] + xv;
-        }
+        for (int k = 0; k < 4; ++k) t[4 * a + k] = SP::SCALED ? __builtin_fmaf(xs[a][k], c, t[4 * a + k]) : t[4 * a + k] + xs[a][k];
     };
     auto pin_x = [&](f32x4 (&xs)[4]) {
 #pragma unroll
@@ -284,7 +225,7 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
     f32x4 xs[4], xs2[4];    // x segments (xs2: only segment 7 of the norm1 residual)
     V apA[2][NP], apB[2][NP];  // planes of att_h^T, the B operand of the merge GEMM: heads of even / odd index
     f32x16 aT;              // att_h^T tile of the head being applied
-    bf16x8 qp[2][3];        // bf16 x 3 apply (SplitBf3 kernels; the fp16 kernels with T_APPLY_H2 = 0)
+    bf16x8 qp[2][3];        // bf16 x 3 apply (the SplitBf3 kernel)
     f16x8 qph[2][2];        // fp16 x 2 apply: the planes of Q' 2^t
     float Zs = 0.f;
     int tq = 0;             // fp16 x 2 apply: exponent t of the row and head being applied (apply_qscale)
@@ -312,9 +253,8 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
         const int hb = (int)(__float_as_uint(op.sc[0]) >> 23);  // 127 - e_h
         tq = min(max(14 - ((int)(__float_as_uint(m) >> 23) - 127), sc.e_q), min(127, sc.e_att + hb - 1));
     };
-    auto apply_qsplit = [&](f32x4 (&qb)[4], int tile_tag, int s2) {  // 16-deep step s2 of Q' into its planes
-        f32x4 lo = qb[2 * s2], hi = qb[2 * s2 + 1];
-        if (T_ABLATE & 16) lo = hi = f32x4{(float)lane, 1.0f, 0.5f, (float)tile_tag};
+    auto apply_qsplit = [&](f32x4 (&qb)[4], int s2) {  // 16-deep step s2 of Q' into its planes
+        const f32x4 lo = qb[2 * s2], hi = qb[2 * s2 + 1];
         if (APPLY_H2) split8s<SplitH2>(lo, hi, __uint_as_float((uint32_t)(tq + 127) << 23), qph[s2]);
         else split8<SplitBf3>(lo, hi, qp[s2]);
     };
@@ -346,18 +286,14 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
     };
     auto apply_split_pair = [&](int k, V (&ap)[2][NP], float S) {  // elements 2k, 2k+1: (aT * Z) * S, then the operand split
         const int s2 = k >> 2, j = (2 * k) & 7;
-        if constexpr (SP::SCALED && (T_MIX & 2)) {
-            SP::split2s((aT[2 * k] * Zs) * S, (aT[2 * k + 1] * Zs) * S, 1.0f, j, ap[s2]);
-        } else {
 #pragma unroll
-            for (int e = 0; e < 2; ++e) SP::split1((aT[2 * k + e] * Zs) * S, j + e, ap[s2]);
-        }
+        for (int e = 0; e < 2; ++e) SP::split1((aT[2 * k + e] * Zs) * S, j + e, ap[s2]);
     };
     // the pieces of one apply as they ride in group g of a 16-group stage: operands consumed in groups 0-3
-    auto apply_ride = [&](f32x4 (&qb)[4], int g, V (&ap)[2][NP], float S, int tile_tag) {
+    auto apply_ride = [&](f32x4 (&qb)[4], int g, V (&ap)[2][NP], float S) {
         if (g == 0 && APPLY_H2) apply_qscale(qb);
-        if (g == 0) apply_qsplit(qb, tile_tag, 0);
-        if (g == 1) apply_qsplit(qb, tile_tag, 1);
+        if (g == 0) apply_qsplit(qb, 0);
+        if (g == 1) apply_qsplit(qb, 1);
         if (g == 1) apply_mfma(0);
         if (g == 2) apply_mfma(1);
         if (g == 3) apply_z(qb);
@@ -382,26 +318,39 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
             pin_x(qA);
             pin_head(op);
 #pragma unroll
-            for (int g = 0; g < 12; ++g) apply_ride(qA, g, h == 0 ? apA : apB, S, tile);
+            for (int g = 0; g < 12; ++g) apply_ride(qA, g, h == 0 ? apA : apB, S);
         }
     }
 
-#ifdef T_STAMPS
-    int tile_no = 0;
-#endif
     while (tile < n_tiles) {
-#ifdef T_STAMPS
-        const bool stamp_on = tile_no == 1;
-        ++tile_no;
-        unsigned marks[16] = {};
-#endif
-        TSTAMP(0);  // tile start
         // The last MFMA group(s) of every stage are DEFERRED across the barrier: their weight fragments are read into wfd, and
         // the next stage issues them right after the first fragment reads of its own -- work with register
         // operands exactly where a lone in-order wave otherwise waits for the LDS (tools/tail_stamps.py: 3.8 k cycles per
         // 3.07 k-cycle stage of the bf16 kernel).  `flush` arguments below name the deferred groups of the preceding stage.
         V wfd[ND][NP];
         f32x16 acc[8];  // (started by the first product of merge stage 0 / of the first down stage: no zeroing moves)
+        // The MFMA groups of one ring stage with their weight fragments read T_PF - 1 groups ahead: body(g, w) is group g = 0 .. NG - 1
+        // with its fragments w; the fragments of the last ND groups go to wfd.  `flush` (the deferred groups of the stage before)
+        // runs right behind the first fragment reads.
+        auto ring_groups = [&](auto flush, auto body) __attribute__((always_inline)) {
+            const char* wb = smem + (q % T_SLOTS) * STAGE + lane * 16;
+            V wf[T_PF][NP];
+#pragma unroll
+            for (int g0 = 0; g0 < T_PF - 1; ++g0)
+#pragma unroll
+                for (int p = 0; p < NP; ++p) wf[g0][p] = ld_frag<V>(wb + (p * 16 + g0) * 1024);
+            flush();
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                if (g + T_PF - 1 < 16) {
+#pragma unroll
+                    for (int p = 0; p < NP; ++p)
+                        (g + T_PF - 1 >= NG ? wfd[g + T_PF - 1 - NG][p] : wf[(g + T_PF - 1) % T_PF][p]) = ld_frag<V>(wb + (p * 16 + g + T_PF - 1) * 1024);
+                }
+                body(g, wf[g % T_PF]);
+            }
+            ++q;
+        };
         // the block's next tile (its heads 0 and 1 are applied under / right after this tile's last stage)
         const int tile_next = tile + (int)gridDim.x;
         const bool has_next = tile_next < n_tiles;
@@ -432,7 +381,6 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
             // wait is only sound among loads, so this one barrier per tile drains)
             if (h == 0) { if (NQ) ring_barrier<0>(); else lds_only_barrier(); }
             else ring_barrier<PIECES>();
-            TMARK(h);  // T_STAMPS builds: marks 0-7 = the tops of the merge stages
             __builtin_amdgcn_sched_barrier(0);
             f32x4 (&x_prev)[4] = (h & 1) ? xs : xs2;   // segment h - 1 (landed: requested by stage h - 1)
             f32x4 (&x_req)[4] = (h & 1) ? xs2 : xs;    // segment h
@@ -452,20 +400,7 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
             if (h + 2 < 8) req_q(q_req, grp, h + 2);  // consumed by stage h + 1
             if (h == 0) req_head(op, kvc, 2);
             __builtin_amdgcn_sched_barrier(0);
-            const char* wb = smem + (q % T_SLOTS) * STAGE + lane * 16;
-            V wf[T_PF][NP];
-#pragma unroll
-            for (int g0 = 0; g0 < T_PF - 1; ++g0)
-#pragma unroll
-                for (int p = 0; p < NP; ++p) wf[g0][p] = ld_frag<V>(wb + (p * 16 + g0) * 1024);
-            flush();
-#pragma unroll
-            for (int g = 0; g < NG; ++g) {  // g = blk * 2 + s2; the last ND groups are deferred to the next stage
-                if (g + T_PF - 1 < 16) {
-#pragma unroll
-                    for (int p = 0; p < NP; ++p)
-                        (g + T_PF - 1 >= NG ? wfd[g + T_PF - 1 - NG][p] : wf[(g + T_PF - 1) % T_PF][p]) = ld_frag<V>(wb + (p * 16 + g + T_PF - 1) * 1024);
-                }
+            ring_groups(flush, [&](int g, const V (&w)[NP]) __attribute__((always_inline)) {  // g = blk * 2 + s2; the last ND groups are deferred to the next stage
                 if (g == 4 && RIDE && h + 2 < 8) {
                     __builtin_amdgcn_sched_barrier(0);
                     req_head(op, kvc, h + 2);
@@ -473,16 +408,15 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
                 }
                 if (g >= 4 && g - 4 < PIECES) dma_piece(q + 2, g - 4);
                 if (PIECES == 12 && g == 14) dma_piece(q + 2, 11);  // (group 15 is deferred: the twelfth piece goes out with the eleventh)
-                if (RIDE && !(T_ABLATE & 512)) apply_ride(q_cons, g, ap_next, S, tile);
+                if (RIDE) apply_ride(q_cons, g, ap_next, S);
                 // the norm1 residual: segment h - 1 joins accumulator tile h - 1 in quarters, in late groups that do not
                 // accumulate into that tile (its MFMAs are groups 2h - 2 and 2h - 1)
                 if (h > 0) {
                     const int pc = xadd_slot(h, g, ND);
-                    if (pc >= 0 && !(T_ABLATE & 1024)) add_x4(acc[h > 0 ? h - 1 : 0], x_prev, pc, sc.c1);
+                    if (pc >= 0) add_x4(acc[h > 0 ? h - 1 : 0], x_prev, pc, sc.c1);
                 }
-                mfma_group<SP, (h > 0 ? NV_MERGE : 0)>(acc[g >> 1], wf[g % T_PF], ap[g & 1], h == 0 && (g & 1) == 0);
-            }
-            ++q;
+                mfma_group<SP, (h > 0 ? NV_MERGE : 0)>(acc[g >> 1], w, ap[g & 1], h == 0 && (g & 1) == 0);
+            });
         };
         constexpr std::integral_constant<bool, true> yes{};
         constexpr std::integral_constant<bool, false> no{};
@@ -510,7 +444,6 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
         pin_x(xs2);
         add_x(acc[7], xs2, sc.c1);
 
-        TSTAMP(1);  // end of the merge phase
         // ---- m1 = LayerNorm1(merge + x) (models/transformer.py:84), straight into the B-operand planes of FFN-up ---
         V mp[16][NP];
         {
@@ -545,11 +478,10 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
 #pragma unroll
                         for (int k = 0; k < 4; ++k) v[a2][k] = acc[b][4 * a + k] * rstd * g4[k] + b4[k];
                     }
-                    if (T_MIX & 2) split8s<SP>(v[0], v[1], 1.0f, mp[2 * b + s2]); else split8<SP>(v[0], v[1], mp[2 * b + s2]);
+                    split8<SP>(v[0], v[1], mp[2 * b + s2]);
                 }
         }
 
-        TSTAMP(2);  // end of norm1
         // ---- FFN; x segments 0 .. 7 (the norm2 residual) are added under the first eight down stages
         f32x16 hT;
         V hpA[2][NP], hpB[2][NP];
@@ -559,18 +491,12 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
             // relu as ONE v_max_f32: fmaxf() (and every builtin that folds to it) costs a second instruction that quiets a NaN the
             // accumulator cannot hold
             float x0, x1;
-            if (T_MIX & 1) {
-                asm("v_max_f32 %0, 0, %1" : "=v"(x0) : "v"(hT[2 * k]));
-                asm("v_max_f32 %0, 0, %1" : "=v"(x1) : "v"(hT[2 * k + 1]));
-            } else {
-                x0 = fmaxf(hT[2 * k], 0.f);
-                x1 = fmaxf(hT[2 * k + 1], 0.f);
-            }
-            if constexpr (SP::SCALED && (T_MIX & 1)) {
-                SP::split2s(x0, x1, sc.ch, j, hout[s2]);  // the planes of x 2^e, one v_fma_mix each (split.h)
-            } else if constexpr (SP::SCALED) {
-                SP::split1(x0 * sc.ch, j, hout[s2]);
-                SP::split1(x1 * sc.ch, j + 1, hout[s2]);
+            asm("v_max_f32 %0, 0, %1" : "=v"(x0) : "v"(hT[2 * k]));
+            asm("v_max_f32 %0, 0, %1" : "=v"(x1) : "v"(hT[2 * k + 1]));
+            if constexpr (SP::SCALED) {
+                // the planes of x 2^e, one v_fma_mix each (split.h): 103 -> 52 vector instructions per down stage against fmaxf / split1,
+                // bit-identical, 1.043 vs 1.046 ms per 333 k-row launch (profiles/r04_tail_mix_ab.txt)
+                SP::split2s(x0, x1, sc.ch, j, hout[s2]);
             } else {
                 SP::split1(x0, j, hout[s2]);
                 SP::split1(x1, j + 1, hout[s2]);
@@ -581,31 +507,16 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
             constexpr int XLOAD = decltype(xload)::value;
             // FIRST: the norm1 block above used ordinary loads (gamma, beta), which hipcc waits for with vmcnt(0)
             if (decltype(first)::value) ring_barrier<0>(); else ring_barrier<PIECES>();
-            TMARK2(8, 10);  // T_STAMPS builds: tops of the last two up stages
             __builtin_amdgcn_sched_barrier(0);
             if (XLOAD >= 0 && XLOAD < NSTASH) {
 #pragma unroll
                 for (int a = 0; a < 4; ++a) xs[a] = stash[(XLOAD * 4 + a) * 64];
             } else if (XLOAD >= 0) req_x(xs, grp, XLOAD, std::true_type{});
             __builtin_amdgcn_sched_barrier(0);
-            const char* wb = smem + (q % T_SLOTS) * STAGE + lane * 16;
-            V wf[T_PF][NP];
-#pragma unroll
-            for (int g0 = 0; g0 < T_PF - 1; ++g0)
-#pragma unroll
-                for (int p = 0; p < NP; ++p) wf[g0][p] = ld_frag<V>(wb + (p * 16 + g0) * 1024);
-            flush();
-#pragma unroll
-            for (int g = 0; g < NG; ++g) {  // the last ND groups (hT += wfd . mp[g]) are deferred to the next stage
-                if (g + T_PF - 1 < 16) {
-#pragma unroll
-                    for (int p = 0; p < NP; ++p)
-                        (g + T_PF - 1 >= NG ? wfd[g + T_PF - 1 - NG][p] : wf[(g + T_PF - 1) % T_PF][p]) = ld_frag<V>(wb + (p * 16 + g + T_PF - 1) * 1024);
-                }
+            ring_groups(flush, [&](int g, const V (&w)[NP]) __attribute__((always_inline)) {  // the last ND groups (hT += wfd . mp[g]) are deferred to the next stage
                 if (g < PIECES) dma_piece(q + 2, g);
-                mfma_group<SP>(hT, wf[g % T_PF], mp[g], g == 0);
-            }
-            ++q;
+                mfma_group<SP>(hT, w, mp[g], g == 0);
+            });
         };
         // XADD: x segment (requested by the previous stage) to add into its accumulator tile (-1: none).
         // RIDE (the tile's last two stages, when the FFN's operand planes are dead and registers are available again):
@@ -614,22 +525,14 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
         auto stage_down = [&](V (&hin)[2][NP], V (&hout)[2][NP], auto with_split, auto xadd, auto ride, auto flush) {
             constexpr int XADD = decltype(xadd)::value;
             constexpr int RIDE = decltype(ride)::value;
-#ifdef T_PROBE_NOBAR  // TIMING PROBE ONLY (wrong results): the down stages wait for their pieces but skip the workgroup barrier
-            __builtin_amdgcn_s_waitcnt(0x0070 | (PIECES & 15) | ((PIECES >> 4) << 14));
-#else
             ring_barrier<PIECES>();
-#endif
-            TMARK2(9, 11);  // ... and of the last two down stages
             __builtin_amdgcn_sched_barrier(0);
             if (XADD == 0) {  // the tile's first down stage starts the accumulators: tile 0 from its x segment, the others from 0
                 pin_x(xs);
 #pragma unroll
                 for (int a = 0; a < 4; ++a)
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const float xv = (T_ABLATE & 16) ? 1.0f : xs[a][k];
-                        acc[0][4 * a + k] = SP::SCALED ? xv * sc.c2 : xv;
-                    }
+                    for (int k = 0; k < 4; ++k) acc[0][4 * a + k] = SP::SCALED ? xs[a][k] * sc.c2 : xs[a][k];
             } else if (XADD > 0) {
                 pin_x(xs);
                 add_x(acc[XADD > 0 ? XADD : 0], xs, sc.c2);
@@ -644,20 +547,7 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
                 req_head(op, kvc_next, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            const char* wb = smem + (q % T_SLOTS) * STAGE + lane * 16;
-            V wf[T_PF][NP];
-#pragma unroll
-            for (int g0 = 0; g0 < T_PF - 1; ++g0)
-#pragma unroll
-                for (int p = 0; p < NP; ++p) wf[g0][p] = ld_frag<V>(wb + (p * 16 + g0) * 1024);
-            flush();
-#pragma unroll
-            for (int g = 0; g < NG; ++g) {  // g = blk * 2 + s2; the last ND groups (acc[7] += wfd . hin[g & 1]) are deferred to the next stage
-                if (g + T_PF - 1 < 16) {
-#pragma unroll
-                    for (int p = 0; p < NP; ++p)
-                        (g + T_PF - 1 >= NG ? wfd[g + T_PF - 1 - NG][p] : wf[(g + T_PF - 1) % T_PF][p]) = ld_frag<V>(wb + (p * 16 + g + T_PF - 1) * 1024);
-                }
+            ring_groups(flush, [&](int g, const V (&w)[NP]) __attribute__((always_inline)) {  // g = blk * 2 + s2; the last ND groups (acc[7] += wfd . hin[g & 1]) are deferred to the next stage
                 if (RIDE == 2 && g == 4) {
                     __builtin_amdgcn_sched_barrier(0);
                     req_q(qA, grp_next, 1);  // head 1 into the buffers head 0 has just left (a second Q' buffer here, at the
@@ -670,15 +560,14 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
                 } else {
                     if (g < PIECES) dma_piece(q + 2, g);
                 }
-                if (RIDE == 2) apply_ride(qA, g, apA, S_next, tile_next);
+                if (RIDE == 2) apply_ride(qA, g, apA, S_next);
                 // the relu / split of the h^T tile the previous stage finished: eight pairs, in every other group (in the first
                 // eight groups when group 14 is deferred)
                 // (T_RIDE0: the first group that carries a pair -- the h^T tile was completed by the deferred groups flushed at this stage's
                 // top, and a vector instruction that reads it stalls the whole in-order wave, MFMAs included, until those have drained)
                 if (decltype(with_split)::value && (ND == 1 ? (g & 1) == 0 : (g >= T_RIDE0 && g < T_RIDE0 + 8))) split_pair(ND == 1 ? g >> 1 : g - T_RIDE0, hout);
-                mfma_group<SP>(acc[g >> 1], wf[g % T_PF], hin[g & 1], XADD == 0 && g >= 2 && (g & 1) == 0);
-            }
-            ++q;
+                mfma_group<SP>(acc[g >> 1], w, hin[g & 1], XADD == 0 && g >= 2 && (g & 1) == 0);
+            });
         };
         constexpr std::integral_constant<int, -1> none{};
         constexpr std::integral_constant<int, 0> ride0{};
@@ -718,16 +607,14 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
         // head is applied here in the open (12 MFMAs), so that nothing pending lives across the norm2 block, and the y
         // stores below are YOUNGER than every load a later counted wait is meant to cover (stores retire out of order with
         // respect to loads, gemm_split.hip; stage 0 of the next tile starts without a vector-memory wait).
-        TSTAMP(3);  // end of the last stage
         VM_WAIT(0);
         if (has_next) {
             pin_head(op);
             pin_x(qA);
 #pragma unroll
-            for (int g = 0; g < 12; ++g) apply_ride(qA, g, apB, S_next, tile_next);
+            for (int g = 0; g < 12; ++g) apply_ride(qA, g, apB, S_next);
         }
 
-        TSTAMP(4);  // after the open apply of the next tile's head 1
         // ---- y = LayerNorm2(x + ffn) (the residual is already in the accumulators), stored fragment-major ------------
         V yp[NQ ? 16 : 1][NP];  // NQ: the planes of y
         {
@@ -764,16 +651,10 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
 #pragma unroll
                         for (int k = 0; k < 4; ++k) o[k] = acc[b][4 * a + k] * rstd * g4[k] + b4[k];
                         // one contiguous 1 KiB per wave instruction
-                        if (!(T_ABLATE & (16 | 128)) || o[0] + o[1] + o[2] + o[3] == 123.456f) {
-                            if (T_NT & 2) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(yg + (b * 4 + a) * 256));
-                            else *reinterpret_cast<f32x4*>(yg + (b * 4 + a) * 256) = o;
-                        }
+                        __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(yg + (b * 4 + a) * 256));
                         o2[a2] = o;
                     }
-                    if (NQ) {  // B operand of the query stages below
-                        if (T_MIX & 2) split8s<SP>(o2[0], o2[1], sc.s_y, yp[NQ ? 2 * b + s2 : 0]);
-                        else split8<SP>(o2[0] * sc.s_y, o2[1] * sc.s_y, yp[NQ ? 2 * b + s2 : 0]);
-                    }
+                    if (NQ) split8<SP>(o2[0] * sc.s_y, o2[1] * sc.s_y, yp[NQ ? 2 * b + s2 : 0]);  // B operand of the query stages below
                 }
         }
         if constexpr (NQ) {
@@ -795,34 +676,20 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
             };
             auto store_chunk = [&](int j) {
 #pragma unroll
-                for (int a = 0; a < 4; ++a)
-                    if (!(T_ABLATE & (16 | 128)) || oq[a][0] == 123.456f) {
-                        if (T_NT & 2) __builtin_nontemporal_store(oq[a], reinterpret_cast<f32x4*>(qg + (j * 4 + a) * 256));
-                        else *reinterpret_cast<f32x4*>(qg + (j * 4 + a) * 256) = oq[a];
-                    }
+                for (int a = 0; a < 4; ++a) __builtin_nontemporal_store(oq[a], reinterpret_cast<f32x4*>(qg + (j * 4 + a) * 256));
             };
             constexpr int PP = (PIECES + NG - 9) / (NG - 8);  // weight pieces per group from group 8 on
             auto stage_q = [&](auto jj) {
                 constexpr int j = decltype(jj)::value;
                 if (j == 0) lds_only_barrier(); else ring_barrier<PIECES>();  // (stage 0: the queue was drained in front of norm2)
                 __builtin_amdgcn_sched_barrier(0);
-                const char* wb = smem + (q % T_SLOTS) * STAGE + lane * 16;
-                V wf[T_PF][NP];
+                auto flush_q = [&]() {  // the deferred groups of chunk j - 1
+                    if (j > 0) {
 #pragma unroll
-                for (int g0 = 0; g0 < T_PF - 1; ++g0)
-#pragma unroll
-                    for (int p = 0; p < NP; ++p) wf[g0][p] = ld_frag<V>(wb + (p * 16 + g0) * 1024);
-                if (j > 0) {
-#pragma unroll
-                    for (int i = 0; i < ND; ++i) mfma_group<SP, -1>(hq[(j + 1) & 1], wfd[i], yp[NG + i]);
-                }
-#pragma unroll
-                for (int g = 0; g < NG; ++g) {
-                    if (g + T_PF - 1 < 16) {
-#pragma unroll
-                        for (int p = 0; p < NP; ++p)
-                            (g + T_PF - 1 >= NG ? wfd[g + T_PF - 1 - NG][p] : wf[(g + T_PF - 1) % T_PF][p]) = ld_frag<V>(wb + (p * 16 + g + T_PF - 1) * 1024);
+                        for (int i = 0; i < ND; ++i) mfma_group<SP, -1>(hq[(j + 1) & 1], wfd[i], yp[NG + i]);
                     }
+                };
+                ring_groups(flush_q, [&](int g, const V (&w)[NP]) __attribute__((always_inline)) {
                     if (j > 0 && g < 8) elu_pair(g, hq[(j + 1) & 1]);
                     if (g == 8) {
                         __builtin_amdgcn_sched_barrier(0);
@@ -834,9 +701,8 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
                         for (int u = (g - 8) * PP; u < (g - 7) * PP; ++u)
                             if (u < PIECES) dma_piece(q + 2, u);
                     }
-                    mfma_group<SP, 8>(hq[j & 1], wf[g % T_PF], yp[g], g == 0);
-                }
-                ++q;
+                    mfma_group<SP, 8>(hq[j & 1], w, yp[g], g == 0);
+                });
             };
             stage_q(std::integral_constant<int, 0>{});
             stage_q(std::integral_constant<int, 1>{});
@@ -852,8 +718,6 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
             for (int k = 0; k < 8; ++k) elu_pair(k, hq[1]);
             store_chunk(7);
         }
-        TSTAMP(5);  // tile end
-        TMARKS_FLUSH();
         tile = tile_next;
         grp = ((int64_t)tile_next * 128 + wave * 32) * SCREAM_D_MODEL;
         kvc = kvc_next;
@@ -1104,7 +968,7 @@ extern "C" int scream_kv_finalize_image(const float* kv_partial, const int32_t* 
                    SCREAM_EINVAL);
     if (n_kv == 0) return 0;
     const dim3 grid(n_kv * SCREAM_NHEAD, n_layers), block(KVF_THREADS);
-    if (split != SCREAM_SPLIT_BF3 && T_APPLY_H2)
+    if (split != SCREAM_SPLIT_BF3)
         kv_finalize_image_kernel<true><<<grid, block, 0, as_stream(stream)>>>(kv_partial, cloud_row0, cloud_len, row_base, cloud_begin,
                                                                               reinterpret_cast<char*>(kv_image), partial_layer_stride, image_layer_stride);
     else

@@ -519,18 +519,17 @@ def test_the_static_checker_detects_what_it_is_there_for():
     assert not chk.check_mfma_asm_read_hazard("k", lines("v_mfma_f32_32x32x16_f16 a[0:15], v[40:43], v[44:47], a[0:15]\nv_fma_mixlo_f16 v48, v3, s50, 0"))
 
 
-def test_tuning_builds_are_verified_before_they_can_be_launched(tmp_path):
-    """tools/tail_ablate.py / tail_stamps.py / gemm_ablate.py / gemm_stamps.py compile -D variants of the two hand-scheduled kernels;
-    every variant goes through asm_inflight_check.verify_source first (round 2 launched an unverified one and faulted the GPU).
-    The "no weight DMA" variant of the fp16 layer tail -- the variant that faulted, now with draining waits -- passes; a
-    variant in which hipcc moves a pending register raises instead of producing a library."""
+def test_verify_source_refuses_asm_loads_touched_in_flight(tmp_path):
+    """asm_inflight_check.verify_source compiles a source with the flags of the object that will run and checks the generated
+    code: it refuses to hand back a library whose inline-asm loads are touched while still in flight (round 2 launched an
+    unverified build of the layer tail with exactly that defect and faulted the GPU), and the shipped fp16 layer tail passes it."""
     import shutil
     if shutil.which("hipcc") is None:
         pytest.skip("hipcc not available")
     sys.path.insert(0, os.path.join(REPO, "tools"))
     import asm_inflight_check as chk
     src = os.path.join(REPO, "scream_amd", "csrc", "tail_split.hip")
-    assert chk.verify_source(src, ["-ffp-contract=off", "-DT_ABLATE=1"], str(tmp_path / "t1.s"), "11tail_kernelINS_7SplitH2ELb0EE") == 1  # (the instance the tuning tools launch)
+    assert chk.verify_source(src, ["-ffp-contract=off"], str(tmp_path / "t1.s"), "11tail_kernelINS_7SplitH2ELb0EE") == 1  # (the shipped flags, scream_amd/build.py)
     bad = tmp_path / "bad.hip"  # a register load consumed behind a wait that does not cover it
     bad.write_text("""#include <hip/hip_runtime.h>
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -227,12 +227,12 @@ def kernels(path):
 
 def verify_source(src, flags, out_s, want=""):
     """Compile `src` to assembly with `flags` (the flags of the object that will run) and apply all three checks to every kernel
-    whose mangled name contains `want`; raises RuntimeError naming the first violation.  The ablation / stamp builds of the
-    tuning tools call this on EVERY variant before they produce a library: a -D switch that removes memory operations changes
-    what a hand-counted vmcnt(N) leaves in flight (round 2, gpurun_out/r2i: the "no weight DMA" variant of the layer tail was
-    launched with its ring waits still counting twelve pieces that no longer existed; the row operands were consumed while
-    pending, their registers recycled as per-lane 64-bit addresses, the loads landed in them, and the next access left the
-    aperture -- HSA_STATUS_ERROR_MEMORY_APERTURE_VIOLATION)."""
+    whose mangled name contains `want`; raises RuntimeError naming the first violation.  For any build other than the one
+    scream_amd/build.py verifies itself: whatever removes or adds memory operations changes what a hand-counted vmcnt(N) leaves
+    in flight (round 2: a "no weight DMA" tuning variant of the layer tail -- since removed -- was launched with its ring waits
+    still counting twelve pieces that no longer existed; the row operands were consumed while pending, their registers recycled
+    as per-lane 64-bit addresses, the loads landed in them, and the next access left the aperture --
+    HSA_STATUS_ERROR_MEMORY_APERTURE_VIOLATION)."""
     import subprocess
     r = subprocess.run(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only", *flags, src, "-o", out_s],
                        capture_output=True, text=True)
