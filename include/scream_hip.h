@@ -545,6 +545,47 @@ int scream_voxel_down_sample(const float* xyz, const int32_t* row0, const int32_
                              const double* voxel, float* out_xyz, int32_t* out_len, int32_t* out_count, void* workspace,
                              int64_t workspace_bytes, void* stream);
 
+/* ---- DSM extraction for a batch of OpenGF windows (the reference's process_open_gf.py:219-228: for every ground point, the
+ * highest window point within the radius in the xy plane; csrc/dsm.hip).  Cloud c's window points ("patch") are rows
+ * p_row0[c] .. + p_len[c] of patch [patch_rows_total,3], its ground points ("dem") rows d_row0[c] .. + d_len[c] of dem
+ * [dem_rows_total,3] (DEVICE int32 arrays; no 128-row alignment; the clouds must not overlap).  With q a dem row and p a patch
+ * row of the same cloud, every step one IEEE operation:
+ *   R   = float64(float32(radius));  R2 = R * R                      (one float64 rounding; exact, R being an fp32 value)
+ *   dx  = float32(p.x - q.x),  dy = float32(p.y - q.y)               (one fp32 rounding each, as the reference subtracts fp32 tensors)
+ *   d2  = float64(dx)*float64(dx) + float64(dy)*float64(dy)          (both products exact in float64, so a contracted fma gives the same bits)
+ *   p is a candidate of q  iff  d2 <= R2
+ *   winner = the candidate with the largest z; equal z -> the LOWEST patch row index   (torch.max's first-maximum rule on patch[dis <= r])
+ *   out_xyz = the winner's three fp32 coordinates unchanged, out_idx = its row;   no candidate: out_xyz = q unchanged, out_idx = -1
+ * written at the dem's own rows: out_xyz [dem_rows_total,3], out_idx [dem_rows_total] (int32, the patch row relative to
+ * p_row0[c]).  The reference compares the fp32 sqrt of the fp32 sum with 0.8; that differs from the above only for points within
+ * about one fp32 ulp of the radius (tests/test_dsm_host.py pins it).  The result is a pure function of the cloud: bitwise
+ * repeatable, independent of the other clouds of the call and of the launch geometry, equal bit for bit to the brute-force
+ * float64 restatement of tests/dsm_ref.py.  The kernels use a per-cloud uniform 2-D grid with a bounded number of cells as a
+ * conservative candidate filter (its cells grow with the extent: no cloud is refused for its size); the predicate above alone
+ * decides membership.  No float atomics, no host synchronisation.
+ * p_len[c] = 0: every dem row of the cloud returns itself with -1.  d_len[c] = 0 writes nothing.  n_clouds = 0 does nothing.
+ * Non-finite coordinates are outside the contract (voxel_down_sample refuses such clouds upstream): no fault, no hang, the
+ * values returned for them are unspecified.
+ * SCREAM_EINVAL: a radius that is not a positive finite number; row totals outside 0 .. 2^31 - 1, max_p_len / max_d_len (host
+ * bounds of every p_len[c] / d_len[c]) negative or beyond their totals; a workspace smaller than
+ * scream_dsm_workspace_bytes(patch_rows_total, n_clouds, max_p_len) or not 16-byte aligned.  SCREAM_EUNSUPPORTED: n_clouds > 65535.
+ * All of these are decided before any launch.  The per-cloud arrays live on the device and the call does not synchronise, so a
+ * cloud whose own rows fall outside the arrays or exceed max_p_len / max_d_len is found on the device: it reads and writes
+ * nothing, the other clouds are unaffected. */
+int64_t scream_dsm_workspace_bytes(int64_t patch_rows_total, int32_t n_clouds, int32_t max_p_len);
+int scream_dsm_extract(const float* patch, const int32_t* p_row0, const int32_t* p_len, int32_t max_p_len,
+                       int64_t patch_rows_total, const float* dem, const int32_t* d_row0, const int32_t* d_len, int32_t max_d_len,
+                       int64_t dem_rows_total, int32_t n_clouds, float radius, float* out_xyz, int32_t* out_idx, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+/* The [n,6] sample rows of process_open_gf.py:234-242.  Cloud c is rows row0[c] .. + len[c] of dsm and dem (both [rows_total,3],
+ * the dsm at the dem's rows as scream_dsm_extract writes it).  Per cloud and axis, in fp32 as numpy does on fp32 arrays:
+ *   centre = float32(min + max) / 2   over the cloud's dsm and dem rows together (min and max are exact in any order),
+ *   out[row] = float32(dsm - centre) | float32(dem - centre)          (out [rows_total,6]),
+ * centre written to centre [n_clouds,3] (zeros for len[c] = 0).  Same refusals as above; a cloud whose rows fall outside the
+ * arrays writes no rows and a zero centre. */
+int scream_dsm_dem_assemble(const float* dsm, const float* dem, const int32_t* row0, const int32_t* len, int32_t n_clouds,
+                            int32_t max_len, int64_t rows_total, float* out, float* centre, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,9 @@ Importing the package is cheap and CPU-safe (synthetic data, packing metadata); 
 computes needs libscream_hip.so and an MI355X and raises ``ScreamHipError`` otherwise.
 """
 from ._lib import ScreamHipError  # noqa: F401
+from .dsm import extract_dsm, extract_dsm_batch, make_dsm_dem, make_dsm_dem_batch, tile_windows  # noqa: F401
 from .voxel import voxel_down_sample, voxel_down_sample_batch  # noqa: F401
 
-__all__ = ["ScreamHipError", "voxel_down_sample", "voxel_down_sample_batch"]
+__all__ = ["ScreamHipError", "voxel_down_sample", "voxel_down_sample_batch", "extract_dsm", "extract_dsm_batch", "make_dsm_dem",
+           "make_dsm_dem_batch", "tile_windows"]
 __version__ = "0.1.0"

@@ -114,6 +114,9 @@ SIGNATURES = {
     "scream_render_depth_bwd": (C.c_int, [V, V, V, I32, I32, I64, V, I32, I32, F32, V, V, V, I64, V, V]),
     "scream_voxel_workspace_bytes": (C.c_int64, [I64, I32]),
     "scream_voxel_down_sample": (C.c_int, [V, V, V, I32, I32, V, V, V, V, V, I64, V]),
+    "scream_dsm_workspace_bytes": (C.c_int64, [I64, I32, I32]),
+    "scream_dsm_extract": (C.c_int, [V, V, V, I32, I64, V, V, V, I32, I64, I32, F32, V, V, V, I64, V]),
+    "scream_dsm_dem_assemble": (C.c_int, [V, V, V, V, I32, I32, I64, V, V, V]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -32,6 +32,7 @@ SOURCES = {
     "icp_grid.hip": ["-ffp-contract=off"],
     "render.hip": ["-ffp-contract=off"],
     "voxel.hip": ["-ffp-contract=off"],
+    "dsm.hip": ["-ffp-contract=off"],
 }
 ASM_LOADS = ("gemm_split.hip", "tail_split.hip", "proj_ring.hip")  # verified after code generation, see verify_one
 # kernels that must not touch scratch at all: a spill inside a ring stage costs a round trip per stage, and hipcc orders a scratch

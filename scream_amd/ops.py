@@ -411,6 +411,39 @@ def voxel_down_sample_packed(xyz: torch.Tensor, row0: torch.Tensor, length: torc
     return out_xyz[:rows], out_len[:n_clouds], (out_count[:rows] if want_counts else None)
 
 
+def dsm_extract_packed(patch: torch.Tensor, p_row0: torch.Tensor, p_len: torch.Tensor, max_p_len: int, dem: torch.Tensor,
+                       d_row0: torch.Tensor, d_len: torch.Tensor, max_d_len: int, radius: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """scream_dsm_extract on packed rows: patch [P,3] / dem [D,3] fp32, the four int32 [B] arrays on the device.  Returns
+    (out_xyz [D,3], out_idx int32 [D]) on the device; rows of dem outside every cloud are not written.  No host sync."""
+    n_clouds, P, D, dev = p_row0.shape[0], patch.shape[0], dem.shape[0], dem.device
+    lib = _lib.load()
+    need = lib.scream_dsm_workspace_bytes(P, n_clouds, int(max_p_len))
+    if need < 0:
+        raise _lib.ScreamHipError("scream_dsm_workspace_bytes(%d, %d, %d): invalid argument" % (P, n_clouds, max_p_len))
+    workspace = torch.empty(max(need, 16), device=dev, dtype=torch.uint8)
+    out_xyz = torch.empty(max(D, 1), 3, device=dev, dtype=torch.float32)
+    out_idx = torch.empty(max(D, 1), device=dev, dtype=torch.int32)
+    patch_p = _p(patch) if P else _p(workspace, torch.uint8)  # a batch of empty windows: nothing is read through it
+    dem_p = _p(dem) if D else out_xyz.data_ptr()
+    check(lib.scream_dsm_extract(patch_p, _p(p_row0, torch.int32), _p(p_len, torch.int32), int(max_p_len), P, dem_p,
+                                 _p(d_row0, torch.int32), _p(d_len, torch.int32), int(max_d_len), D, n_clouds, float(radius),
+                                 _p(out_xyz), _p(out_idx, torch.int32), _p(workspace, torch.uint8), workspace.numel(), _stream()),
+          "scream_dsm_extract")
+    return out_xyz[:D], out_idx[:D]
+
+
+def dsm_dem_assemble_packed(dsm: torch.Tensor, dem: torch.Tensor, row0: torch.Tensor, length: torch.Tensor,
+                            max_len: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """scream_dsm_dem_assemble: dsm / dem [rows,3] fp32 at the same rows -> (out [rows,6], centre [B,3]), on the device."""
+    n_clouds, rows, dev = row0.shape[0], dem.shape[0], dem.device
+    out = torch.empty(max(rows, 1), 6, device=dev, dtype=torch.float32)
+    centre = torch.empty(max(n_clouds, 1), 3, device=dev, dtype=torch.float32)
+    check(_lib.load().scream_dsm_dem_assemble(_p(dsm) if rows else out.data_ptr(), _p(dem) if rows else out.data_ptr(),
+                                              _p(row0, torch.int32), _p(length, torch.int32), n_clouds, int(max_len), rows,
+                                              _p(out), _p(centre), _stream()), "scream_dsm_dem_assemble")
+    return out[:rows], centre[:n_clouds]
+
+
 def kabsch_corr(src, ref, src_row0, src_len, ref_row0, idx, valid, s, c) -> Tuple[torch.Tensor, torch.Tensor]:
     """Returns (T [n_pairs,4,4], n_corr int32 [n_pairs])."""
     n_pairs = s.shape[0]
