@@ -393,10 +393,16 @@ int scream_point_loss(const float* src_pred, const float* src, const int32_t* sr
  * evaluate_3d_match.py:106-113 / evaluate_kitti.py:61-70 (open3d is absent here: parity with open3d is
  * unpinned; the loop is open3d's published RegistrationICP and is checked against oracle/icp_ref.py).
  * src/ref packed, normalised frame; metric points are x / s + c.  T [n_pairs,16] holds the initial
- * transforms on entry and the refined ones on return.  Per iteration (one launch): transform the source, thresholded
- * 1-NN (distance <= max_corr_dist), fitness = #corr / N and inlier_rmse = sqrt(mean d^2); stop a pair when
- * both change by less than rel_fitness / rel_rmse or after max_iter updates; otherwise compose the Kabsch
- * update of the correspondences.  fitness_rmse [n_pairs,2] and iters [n_pairs] may be NULL.  The clouds of a batch may be
+ * transforms on entry and the refined ones on return.  Per iteration (one launch): transform the source (a = T x, fp32),
+ * thresholded 1-NN: the nearest target b is a correspondence iff d^2 < max_corr_dist * max_corr_dist (strict; the fp32 product,
+ * compared with the search's fp32 value d^2 = (-2 a.b + |a|^2) + |b|^2, which SELECTS and is used for nothing else);
+ * fitness = #corr / N and inlier_rmse = sqrt(mean |a - b|^2) with the DIFFERENCE a - b taken in fp64 (what open3d measures;
+ * exactly 0 for coincident clouds in any frame); stop a pair when both change by less than rel_fitness / rel_rmse or after
+ * max_iter updates; otherwise compose the Kabsch update of the correspondences, T <- dT . T.  iters = the number of updates
+ * applied.  A pair that finds no correspondence (an empty source included) has fitness 0 and inlier_rmse 0, takes the identity
+ * as its update and goes on, as open3d's loop does: its T stays the initial T bit for bit, and iters is 1 when both thresholds
+ * are positive (its second evaluation repeats the first, so it stops there), max_iter when a threshold is 0 (|change| < 0 never
+ * holds), and 0 when max_iter is 0.  fitness_rmse [n_pairs,2] and iters [n_pairs] may be NULL.  The clouds of a batch may be
  * packed in any order (the per-chunk partial sums are indexed by a prefix sum of the source lengths).
  * ASYNCHRONOUS, like every entry point: scream_icp_p2p enqueues the whole schedule (max_iter + 2 launches at most) and never
  * waits for the device; a pair that has stopped freezes there (its blocks return at their first instruction).  A caller with a

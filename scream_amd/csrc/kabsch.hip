@@ -401,7 +401,7 @@ __global__ __launch_bounds__(256) void fill_f32_kernel(float* __restrict__ p, fl
 }
 
 // ---- the ICP iteration (round 3, second version): ONE launch per iteration --------------------------------------------------
-// A search launch leaves, per 256-point chunk of a pair, a PARTIAL of its correspondences: count, sum d^2, sum a, sum b, sum a b^T
+// A search launch leaves, per 256-point chunk of a pair, a PARTIAL of its correspondences: count, sum |a - b|^2, sum a, sum b, sum a b^T
 // (17 doubles; a = the transformed source point, b = its target).  The next launch starts, in EVERY block of the pair, by summing
 // the pair's partials in a fixed order and deriving from them what rounds 1-3's separate update launch derived from a second
 // gathering pass: fitness / inlier RMSE, the convergence test, and the Kabsch update composed into T -- then searches under the
@@ -533,9 +533,11 @@ __device__ bool icp_pose_step(const IcpArgs& a, int p, int it, bool writer, floa
     return stop;
 }
 
-// the block's partial of search `it`: one correspondence (or none) per thread, summed over the 256 threads in a fixed order
-__device__ void icp_store_partial(const IcpArgs& a, int p, int c, int it, bool ok, float ax, float ay, float az, const float (&b)[3],
-                                  float d) {
+// the block's partial of search `it`: one correspondence (or none) per thread, summed over the 256 threads in a fixed order.
+// The squared residual is the DIFFERENCE a - b in fp64 (what open3d's inlier_rmse measures), not the search's fp32 value
+// (-2 a.b + |a|^2) + |b|^2: that one selects the correspondence, but away from the origin it carries the cancellation error of
+// |a|^2 and can be negative -- summed, it made the RMSE of coincident clouds NaN from a few metres out and biased it further out.
+__device__ void icp_store_partial(const IcpArgs& a, int p, int c, int it, bool ok, float ax, float ay, float az, const float (&b)[3]) {
     __shared__ double red[4 * ICP_NP];
     double v[ICP_NP];
 #pragma unroll
@@ -543,9 +545,10 @@ __device__ void icp_store_partial(const IcpArgs& a, int p, int c, int it, bool o
     if (ok) {
         const float av[3] = {ax, ay, az};
         v[0] = 1.0;
-        v[1] = (double)d;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
+            const double e = (double)av[k] - (double)b[k];
+            v[1] += e * e;
             v[2 + k] = (double)av[k];
             v[5 + k] = (double)b[k];
         }
@@ -597,7 +600,7 @@ __global__ __launch_bounds__(256) void icp_iter_kernel(IcpArgs a, const float* _
         scream_internal::grid_search_point(gp[p], start + (int64_t)p * (ICP_GRID_CELLS + 1), sorted_prep + (int64_t)r_row0[p] * 4,
                                            sorted_idx + r_row0[p], ax, ay, az, thresh, bi, d, ok, b);
     }
-    icp_store_partial(a, p, c, it, ok != 0, ax, ay, az, b, d);
+    icp_store_partial(a, p, c, it, ok != 0, ax, ay, az, b);
 }
 
 // one block per pair: the evaluation (+ update) alone -- the last search's, and every iteration's on the brute-force yardstick
@@ -611,13 +614,13 @@ __global__ __launch_bounds__(256) void icp_pose_kernel(IcpArgs a, int it) {
 // SCREAM_ICP_BRUTE=1: the partials of a search done by icp_transform_kernel + scream_nn_search (same per-thread values, same sums)
 __global__ __launch_bounds__(256) void icp_partials_kernel(IcpArgs a, const float* __restrict__ q, const float* __restrict__ ref,
                                                           const int32_t* __restrict__ ref_row0, const int32_t* __restrict__ idx,
-                                                          const uint8_t* __restrict__ valid, const float* __restrict__ dmin, int it) {
+                                                          const uint8_t* __restrict__ valid, int it) {
     const int p = blockIdx.y, c = blockIdx.x;
     if (a.done[p]) return;
     const int n = a.src_len[p];
     if (c >= icp_chunks(n)) return;
     const int i = c * 256 + threadIdx.x;
-    float ax = 0.f, ay = 0.f, az = 0.f, d = 0.f, b[3] = {0.f, 0.f, 0.f};
+    float ax = 0.f, ay = 0.f, az = 0.f, b[3] = {0.f, 0.f, 0.f};
     bool ok = false;
     if (i < n) {
         const int64_t row = (int64_t)a.src_row0[p] + i;
@@ -629,10 +632,9 @@ __global__ __launch_bounds__(256) void icp_partials_kernel(IcpArgs a, const floa
             az = q[row * 3 + 2];
 #pragma unroll
             for (int k = 0; k < 3; ++k) b[k] = ref[rrow * 3 + k];
-            d = dmin[row];
         }
     }
-    icp_store_partial(a, p, c, it, ok, ax, ay, az, b, d);
+    icp_store_partial(a, p, c, it, ok, ax, ay, az, b);
 }
 
 }  // namespace
@@ -781,7 +783,7 @@ extern "C" int scream_icp_p2p_range(const float* src, const float* ref, const in
             const int rc = scream_nn_search(q, ref_m, src_row0, a.act_len, ref_row0, ref_len, ones, n_pairs, max_src_len, max_ref_len,
                                             src_rows_total, ref_rows_total, max_corr_dist * max_corr_dist, ref_prep, keys, idx, dmin, valid, stream);
             if (rc != 0) return rc;
-            icp_partials_kernel<<<chunks, dim3(256), 0, st>>>(a, q, ref_m, ref_row0, idx, valid, dmin, it);
+            icp_partials_kernel<<<chunks, dim3(256), 0, st>>>(a, q, ref_m, ref_row0, idx, valid, it);
         } else {
             icp_iter_kernel<<<chunks, dim3(256), 0, st>>>(a, src_m, ref_row0, reinterpret_cast<const scream_internal::GridParam*>(grid.params),
                                                           grid.start, grid.sorted_prep, grid.sorted_idx, max_corr_dist * max_corr_dist, it);
