@@ -235,31 +235,45 @@ int scream_coor_head(const float* X, const float* W, const float* b, float* out,
 
 /* ---- Whole forward pass of PointTransformer over a packed batch (A1-A6).
  * Replaces models/pointnet.py:38-60 for B pairs at once (the reference asserts B == 1, :39-40). */
+/* scream_model_t.gemm_split alone selects the forward's schedule.  Each value reads exactly the fields of its row; a model that
+ * does not match its row is refused with SCREAM_EINVAL before the first launch (the pointers never select a schedule):
+ *
+ *   gemm_split            | self layers (stem, stem_tgt, cross.2j)    | cross layers (cross.2j+1.layer) | scream_model_t (n_cross > 0)
+ *   ----------------------+-------------------------------------------+---------------------------------+-----------------------------
+ *   0 (fp32)              | wqkv, wm, w1, w2; tail NULL               | wq, wkv, wm, w1, w2; tail NULL  | --
+ *   SCREAM_SPLIT_BF3      | wqkv, tail                                | wq, tail                        | wkv_cross
+ *   SCREAM_SPLIT_H2 / H1  | proj, tail (cross.2j: with Wq_next,       | tail                            | proj_cross
+ *                         |             tail_next_q = 1)              |                                 |
+ *
+ * tail_next_q is 1 on the cross-stage self layers of the fp16 splits and 0 everywhere else.  Fields outside a row are not read.
+ *   fp32:  row-major features; scream_gemm_qkv_f32, scream_kv_finalize, scream_attn_apply and three scream_gemm_f32 per layer;
+ *          the cross layers project their queries (wq, ELU1) and the target side (wkv) per layer.
+ *   BF3:   fragment-major features (SCREAM_ACT_FRAG); scream_gemm_qkv_split_f32, scream_kv_finalize_image and
+ *          scream_layer_tail_f32 per layer; the target side of ALL cross layers in one launch after the stem (wkv_cross); the cross
+ *          layers' queries on scream_gemm_split_f32 (wq, ELU1).
+ *   fp16:  as BF3 with the projections on scream_proj_qkv_f32 (proj, proj_cross) and the cross layers' queries written by the
+ *          tail of the self layer in front (tail_next_q). */
 typedef struct {
-    /* Weight matrices are fp32 [N,K] when scream_model_t.gemm_split == 0 and scream_pack_w_split images of them
-     * (the pointers are then really const void*) when it is SCREAM_SPLIT_H2 / SCREAM_SPLIT_BF3. */
+    /* fp32 [N,K] when gemm_split == 0, scream_pack_w_split images (the pointers are then really const void*) on SCREAM_SPLIT_BF3 */
     const float* wqkv; /* [768,256]: q_proj | k_proj[0:128] | v_proj[0:128] | k_proj[128:256] | v_proj[128:256] */
     const float* wq;   /* rows [0,256) of wqkv as their own matrix (cross layers project q and k/v from different clouds) */
-    const float* wkv;  /* rows [256,768) of wqkv as their own matrix */
-    const float* wm;   /* merge [256,256] */
-    const float* w1;   /* mlp.0 [1024,256] */
-    const float* w2;   /* mlp.2 [256,1024] */
+    const float* wkv;  /* fp32 only: rows [256,768) of wqkv as their own matrix */
+    const float* wm;   /* fp32 only: merge [256,256] */
+    const float* w1;   /* fp32 only: mlp.0 [1024,256] */
+    const float* w2;   /* fp32 only: mlp.2 [256,1024] */
     const float* g1; const float* b1; /* norm1 */
     const float* g2; const float* b2; /* norm2 */
-    /* gemm_split != 0 only; may be NULL.  scream_pack_tail image of (wm, w1, w2) for the same split: the forward then runs
-     * attention apply, merge + norm1 and the FFN + norm2 as ONE launch per block (scream_layer_tail_f32) and ignores wm, w1, w2. */
+    /* gemm_split != 0: scream_pack_tail image of (wm, w1, w2) for the same split -- attention apply, merge + norm1 and the
+     * FFN + norm2 as ONE launch per block (scream_layer_tail_f32).  NULL on fp32. */
     const void* tail;
-    /* SCREAM_SPLIT_H2 only: power-of-two exponents (scream_amd/scales.py).  e_xq / e_xkv: the block input on the query side
-     * and on the key/value side (different clouds in a cross layer), bounded by the LayerNorm that produced it; e_wqkv, e_wq,
-     * e_wkv, e_wm_g, e_w1_g, e_w2_g: of the packed matrices above (the *_g ones only when wm / w1 / w2 run as separate GEMMs,
-     * with e_att / e_m1 / e_h of tail_exps as their input exponents); tail_exps: of the fused tail and its image. */
-    int32_t e_xq, e_xkv, e_wqkv, e_wq, e_wkv, e_wm_g, e_w1_g, e_w2_g;
+    /* fp16 splits only: power-of-two exponents (scream_amd/scales.py).  e_xq / e_xkv: the block input on the query side and on
+     * the key/value side (different clouds in a cross layer), bounded by the LayerNorm that produced it; e_wqkv, e_wq: of the
+     * matrices above as packed; tail_exps: of the layer tail and its image. */
+    int32_t e_xq, e_xkv, e_wqkv, e_wq;
     int32_t e_k, e_v; /* of K' = elu(k) + 1 and of V in the projection's K^T V epilogue */
     scream_tail_exps_t tail_exps;
     int32_t tail_next_q; /* the tail image carries the NEXT layer's query projection (scream_pack_tail, Wq_next) */
-    /* fused-tail models on the fp16 splits only; may be NULL.  scream_pack_proj image of wqkv (exponent e_wqkv): the q/k/v
-     * projection of a self layer then runs on scream_proj_qkv_f32 and ignores wqkv. */
-    const void* proj;
+    const void* proj;    /* fp16 splits, self layers: scream_pack_proj image of wqkv (n_q = 256, exponent e_wqkv) */
 } scream_layer_t;
 
 typedef struct {
@@ -276,20 +290,18 @@ typedef struct {
      * (models/pointnet.py:113-118,143-145): HOST array of n_self layers applied to the SECOND clouds (stem_dem) while
      * layers_host[0..n_self) (stem_dsm) are applied to the first clouds only. */
     const scream_layer_t* stem_tgt_layers_host;
-    /* 0: fp32 weights, fp32-input MFMA GEMMs (scream_gemm_f32).  SCREAM_SPLIT_H2 / SCREAM_SPLIT_BF3: every weight MATRIX
-     * above (wqkv/wq/wkv/wm/w1/w2, c0_w, c2_w) is a scream_pack_w_split image and the GEMMs run on scream_gemm_split_f32 --
-     * same fp32 results to rounding (tests/test_gpu_parity.py holds all three to the same tolerances). */
+    /* 0, SCREAM_SPLIT_BF3, SCREAM_SPLIT_H2 or SCREAM_SPLIT_H1: the arithmetic AND the schedule (the table above scream_layer_t).
+     * gemm_split != 0: c0_w and c2_w are scream_pack_w_split images and the coordinate MLP runs on scream_gemm_split_f32 -- same
+     * fp32 results to rounding (tests/test_gpu_parity.py holds fp32, BF3 and H2 to the same tolerances). */
     int32_t gemm_split;
-    /* SCREAM_SPLIT_H2 only: exponents of the coordinate MLP's two GEMMs (input: the last LayerNorm2 / relu(c0 . + b0)) */
+    /* fp16 splits only: exponents of the coordinate MLP's two GEMMs (input: the last LayerNorm2 / relu(c0 . + b0)) */
     int32_t e_c0x, e_c0w, e_c2x, e_c2w;
-    /* Fused-tail models only; may be NULL.  scream_pack_w_split image of the n_cross cross layers' wkv matrices stacked
-     * ([512 n_cross, 256]; exponent e_wkv_cross): the forward then projects the frozen target features for ALL cross layers in
-     * one launch right after the stem (and finalises their K^T V images in one) instead of once per layer, and ignores the
-     * cross layers' wkv / e_wkv. */
+    /* SCREAM_SPLIT_BF3 with n_cross > 0: scream_pack_w_split image of the n_cross cross layers' key/value matrices (rows
+     * [256,768) of their wqkv) stacked, [512 n_cross, 256].  The target features are frozen after the stem, so they are
+     * projected for ALL cross layers in one launch (and their K^T V images finalised in one). */
     const float* wkv_cross;
-    int32_t e_wkv_cross, e_k_cross, e_v_cross; /* e_k / e_v: the smallest over the cross layers */
-    /* may be NULL: scream_pack_proj image of the same stacked matrix (n_q = 0, exponent e_wkv_cross): the batched target-side
-     * projection then runs on scream_proj_qkv_f32 (wkv_cross may then be NULL) */
+    int32_t e_wkv_cross, e_k_cross, e_v_cross; /* fp16 splits: of proj_cross; e_k / e_v the smallest over the cross layers */
+    /* fp16 splits with n_cross > 0: scream_pack_proj image of the same stacked matrix (n_q = 0, exponent e_wkv_cross) */
     const void* proj_cross;
 } scream_model_t;
 
@@ -305,12 +317,11 @@ typedef struct {
     const int32_t* cloud_len;  /* [2B] */
 } scream_batch_t;
 
-/* Bytes of scratch scream_forward needs for this batch geometry.  fused_tail != 0: every layer carries a tail image (the
- * default of the split backends) -- 3 KB per row (two feature buffers and Q'); otherwise the attention output, LayerNorm1
- * output and FFN hidden buffers of the unfused chain are carved as well (9 KB per row).  n_cross_batched: scream_model_t.n_cross
- * when wkv_cross is set (partials and images of every cross layer's target-side K^T V live side by side), else 0. */
+/* Bytes of scratch scream_forward needs for this batch geometry and this model (its gemm_split and n_cross).  gemm_split != 0:
+ * 3 KB per row (two feature buffers and Q') plus the partials and images of every cross layer's target-side K^T V side by side;
+ * fp32: the attention output, LayerNorm1 output and FFN hidden buffers of its launch-per-step chain as well (9 KB per row). */
 int64_t scream_forward_workspace_bytes(int64_t rows_src, int64_t rows_total, int32_t n_pairs,
-                                       int32_t max_chunks, int32_t fused_tail, int32_t n_cross_batched);
+                                       int32_t max_chunks, int32_t gemm_split, int32_t n_cross);
 
 /* src_pred [rows_src,3] (padding rows hold don't-care values).  If feats_out != NULL the final
  * source features [rows_src,256] are copied there (test hook).  trace: NULL, or a handle from

@@ -24,10 +24,10 @@ struct Workspace {
     int64_t bytes;
 };
 
-// fused: every layer runs its tail as one launch -- the attention output, LayerNorm1 output and FFN hidden buffers of the
-// unfused chain (6 KB per row) are then not carved (3 KB per row remain: two feature buffers and Q'); the coordinate MLP's
-// two intermediates go into Q' and the idle feature buffer.
-Workspace carve(void* base, int64_t rows_src, int64_t rows_total, int32_t n_pairs, int32_t max_chunks, bool fused, int32_t n_cross_batched) {
+// split != 0: every layer runs its tail as one launch -- the attention output, LayerNorm1 output and FFN hidden buffers of the
+// fp32 chain (6 KB per row) are then not carved (3 KB per row remain: two feature buffers and Q'); the coordinate MLP's two
+// intermediates go into Q' and the idle feature buffer.  The target side of all n_cross cross layers is projected at once.
+Workspace carve(void* base, int64_t rows_src, int64_t rows_total, int32_t n_pairs, int32_t max_chunks, int split, int32_t n_cross) {
     Workspace w;
     float* p = reinterpret_cast<float*>(base);
     auto take = [&](int64_t n) {
@@ -35,12 +35,13 @@ Workspace carve(void* base, int64_t rows_src, int64_t rows_total, int32_t n_pair
         p += (n + 63) / 64 * 64;  // keep every buffer 256-byte aligned
         return r;
     };
+    const int64_t n_cross_batched = split ? n_cross : 0;
     w.x0 = take(rows_total * D);
     w.x1 = take(rows_total * D);
     w.q = take(rows_total * D);
-    w.att = fused ? nullptr : take(rows_total * D);
-    w.m1 = fused ? nullptr : take(rows_total * D);
-    w.hid = fused ? nullptr : take(rows_total * 4 * D);
+    w.att = split ? nullptr : take(rows_total * D);
+    w.m1 = split ? nullptr : take(rows_total * D);
+    w.hid = split ? nullptr : take(rows_total * 4 * D);
     w.kvp = take(rows_total / SCREAM_ROW_TILE * SCREAM_NHEAD * KV_ELEMS);  // one K^T V partial per 128-row tile and head
     w.kv = take((int64_t)2 * n_pairs * SCREAM_NHEAD * KV_ELEMS);
     w.kvimg = reinterpret_cast<char*>(take((int64_t)2 * n_pairs * scream_kv_image_bytes() / 4));
@@ -91,11 +92,36 @@ enum { TR_TAIL_FUSED = 7, TR_EMBED = 100, TR_KV_REDUCE = 101, TR_ATTN_APPLY = 10
 struct Ctx {
     void* st;
     Trace* tr;
-    int split;    // scream_model_t.gemm_split: 0 = fp32 weights, else the weights are packed operand planes, GEMMs on the split kernel
-    bool frag;    // every layer has a fused-tail image: the features travel FRAGMENT-major between the kernels (SCREAM_ACT_FRAG)
+    // scream_model_t.gemm_split, which alone selects the schedule.  0: fp32 weights, row-major features, one launch per step.
+    // Else: packed operand planes, features FRAGMENT-major between the kernels (SCREAM_ACT_FRAG), one-launch layer tails.
+    int split;
+    bool fp16() const { return split == SCREAM_SPLIT_H2 || split == SCREAM_SPLIT_H1; }
 };
 
-// a_exp / w_exp: SCREAM_SPLIT_H2's operand exponents (ignored otherwise)
+bool valid_split(int s) { return s == 0 || s == SCREAM_SPLIT_H1 || s == SCREAM_SPLIT_H2 || s == SCREAM_SPLIT_BF3; }
+
+// One layer against the table of include/scream_hip.h (scream_layer_t): what the schedule of `c.split` reads is there, and what
+// would select another schedule -- a tail image on fp32, a next-layer query projection where none is run -- is not.
+bool layer_ok(const Ctx& c, const scream_layer_t& L, bool cross, bool cross_stage_self) {
+    if ((L.tail != nullptr) != (c.split != 0)) return false;
+    if ((L.tail_next_q != 0) != (c.fp16() && cross_stage_self)) return false;
+    if (c.fp16()) return cross || L.proj;
+    if (c.split) return cross ? L.wq != nullptr : L.wqkv != nullptr;
+    return L.wm && L.w1 && L.w2 && (cross ? L.wq && L.wkv : L.wqkv != nullptr);
+}
+
+bool model_ok(const Ctx& c, const scream_model_t& m) {
+    for (int i = 0; i < m.n_self; ++i) {
+        if (!layer_ok(c, m.layers_host[i], false, false)) return false;
+        if (m.stem_tgt_layers_host && !layer_ok(c, m.stem_tgt_layers_host[i], false, false)) return false;
+    }
+    for (int i = 0; i < 2 * m.n_cross; ++i)
+        if (!layer_ok(c, m.layers_host[m.n_self + i], i % 2 == 1, i % 2 == 0)) return false;
+    if (m.n_cross == 0 || c.split == 0) return true;
+    return c.fp16() ? m.proj_cross != nullptr : m.wkv_cross != nullptr;
+}
+
+// a_exp / w_exp: the fp16 splits' operand exponents (ignored otherwise)
 int gemm(const Ctx& c, const float* A, int64_t lda, const float* W, float* C, int64_t ldc, int64_t M, int N, int K,
          int epi, int n_act, const float* bias, const float* res, const float* g, const float* b, int a_exp, int w_exp,
          int layout = 0) {
@@ -105,70 +131,71 @@ int gemm(const Ctx& c, const float* A, int64_t lda, const float* W, float* C, in
     return scream_gemm_f32(A, lda, W, C, ldc, M, N, K, epi, n_act, bias, res, D, g, b, c.st);
 }
 
-// proj: the ring kernel's image of the same matrix (fused-tail models on an fp16 split; NULL: the 8-wave GEMM)
+// The q/k/v projection with the K^T V reduction in its epilogue.  W: the matrix as fp32 or as scream_pack_w_split planes
+// (fp32, bf16 x 3); proj: its scream_pack_proj image (fp16 splits, the ring kernel).
 int gemm_qkv(const Ctx& c, const float* A, const float* W, const void* proj, float* Q, int64_t M, int N, int n_q, const scream_batch_t& b,
              int64_t row_base, float* kvp, int a_exp, int w_exp, int k_exp, int v_exp) {
     Scope sc(c.tr, 5, M, N, D, c.st);
-    if (proj && c.frag && (c.split == SCREAM_SPLIT_H2 || c.split == SCREAM_SPLIT_H1))
+    if (c.fp16())
         return scream_proj_qkv_f32(A, proj, Q, M, N, n_q, b.tile_cloud, b.cloud_row0, b.cloud_len, row_base, kvp, c.split, a_exp, w_exp,
                                    k_exp, v_exp, c.st);
     if (c.split)
         return scream_gemm_qkv_split_f32(A, D, W, Q, D, M, N, D, n_q, b.tile_cloud, b.cloud_row0, b.cloud_len, row_base, kvp,
-                                         c.frag ? (SCREAM_LAYOUT_A_FRAG | (n_q ? SCREAM_LAYOUT_C_FRAG : 0)) : 0, c.split, a_exp,
-                                         w_exp, k_exp, v_exp, c.st);
+                                         SCREAM_LAYOUT_A_FRAG | (n_q ? SCREAM_LAYOUT_C_FRAG : 0), c.split, a_exp, w_exp, k_exp, v_exp,
+                                         c.st);
     return scream_gemm_qkv_f32(A, D, W, Q, D, M, N, D, n_q, b.tile_cloud, b.cloud_row0, b.cloud_len, row_base, kvp, c.st);
 }
 
-// merge + norm1 + FFN + norm2 (models/transformer.py:83-88); x is the block input (residual of BOTH norms).
-// x / y already point at packed row `row0`; the scratch buffers are indexed by packed row as well.
-int mha_tail(const Ctx& c, const scream_layer_t& L, const Workspace& w, const float* x, float* y, int64_t row0,
-             int64_t rows) {
+// fp32 only: attention apply, then merge + norm1 + FFN + norm2 (models/transformer.py:83-88) as one launch each; x is the block
+// input (residual of BOTH norms).  x / y already point at packed row `row0`; the scratch buffers are indexed by packed row as
+// well; the keys' cloud of query tile t is tile_cloud[t] + kv_cloud_offset.
+int apply_and_tail_f32(const Ctx& c, const scream_layer_t& L, const scream_batch_t& b, const Workspace& w, const float* x, float* y,
+                       int64_t row0, int64_t rows, int32_t kv_cloud_offset) {
     float* att = w.att + row0 * D;
     float* m1 = w.m1 + row0 * D;
     float* hid = w.hid + row0 * 4 * D;
-    const scream_tail_exps_t& e = L.tail_exps;  // the operands of the three GEMMs are the fused tail's: att, m1, hidden
-    TRY(gemm(c, att, D, L.wm, m1, D, rows, D, D, SCREAM_EPI_RES_LN, 0, nullptr, x, L.g1, L.b1, e.e_att, L.e_wm_g));
-    TRY(gemm(c, m1, D, L.w1, hid, 4 * D, rows, 4 * D, D, SCREAM_EPI_RELU, 0, nullptr, nullptr, nullptr, nullptr, e.e_m1, L.e_w1_g));
-    TRY(gemm(c, hid, 4 * D, L.w2, y, D, rows, D, 4 * D, SCREAM_EPI_RES_LN, 0, nullptr, x, L.g2, L.b2, e.e_h, L.e_w2_g));
+    {
+        Scope sc(c.tr, TR_ATTN_APPLY, rows, 0, 0, c.st);
+        TRY(scream_attn_apply(w.q + row0 * D, D, w.kv, b.tile_cloud + row0 / SCREAM_ROW_TILE, kv_cloud_offset, b.cloud_len, att, D, rows,
+                              c.st));
+    }
+    TRY(gemm(c, att, D, L.wm, m1, D, rows, D, D, SCREAM_EPI_RES_LN, 0, nullptr, x, L.g1, L.b1, 0, 0));
+    TRY(gemm(c, m1, D, L.w1, hid, 4 * D, rows, 4 * D, D, SCREAM_EPI_RELU, 0, nullptr, nullptr, nullptr, nullptr, 0, 0));
+    TRY(gemm(c, hid, 4 * D, L.w2, y, D, rows, D, 4 * D, SCREAM_EPI_RES_LN, 0, nullptr, x, L.g2, L.b2, 0, 0));
     return 0;
 }
 
 // Self attention over packed rows [row0, row0 + rows) whose clouds are [cloud_begin, cloud_begin + n_clouds)
 // (transformer.py:74-90 with q = k = v).  x / y are the full feature buffers (row 0 = packed row 0).
 // The q/k/v projection reduces K^T V in its epilogue, so K' and V never reach HBM.
-// next_q: the tail image carries the next (cross) layer's query projection -- Q' of that layer is written over this layer's (w.q)
+// L.tail_next_q: the tail image carries the next (cross) layer's query projection -- Q' of that layer is written over this layer's (w.q)
 int mha_self(const Ctx& c, const scream_layer_t& L, const scream_batch_t& b, const Workspace& w, const float* x,
-             float* y, int64_t row0, int64_t rows, int32_t cloud_begin, int32_t n_clouds, bool next_q = false) {
+             float* y, int64_t row0, int64_t rows, int32_t cloud_begin, int32_t n_clouds) {
     const float* xr = x + row0 * D;
     float* qr = w.q + row0 * D;
     float* kvp = w.kvp + row0 / SCREAM_ROW_TILE * SCREAM_NHEAD * KV_ELEMS;
     TRY(gemm_qkv(c, xr, L.wqkv, L.proj, qr, rows, 3 * D, D, b, row0, kvp, L.e_xq, L.e_wqkv, L.e_k, L.e_v));
-    if (c.frag) {  // apply + merge + norm1 + FFN + norm2 in one launch
+    if (c.split) {  // apply + merge + norm1 + FFN + norm2 in one launch
         {
             Scope sc(c.tr, TR_KV_REDUCE, rows, 0, 0, c.st);
             TRY(scream_kv_finalize_image(kvp, b.cloud_row0, b.cloud_len, row0, cloud_begin, n_clouds, w.kvimg, 1, 0, 0, c.split, c.st));
         }
         // merge (256) + FFN up and down (2 x 1024) (+ the next layer's query projection, 256) output columns per row
-        Scope sc(c.tr, TR_TAIL_FUSED, rows, (next_q ? 10 : 9) * D, D, c.st);
+        Scope sc(c.tr, TR_TAIL_FUSED, rows, (L.tail_next_q ? 10 : 9) * D, D, c.st);
         return scream_layer_tail_f32(qr, w.kvimg, b.tile_cloud + row0 / SCREAM_ROW_TILE, 0, b.cloud_len, xr, L.tail, L.g1,
-                                     L.b1, L.g2, L.b2, y + row0 * D, next_q ? qr : nullptr, rows, c.split, &L.tail_exps, c.st);
+                                     L.b1, L.g2, L.b2, y + row0 * D, L.tail_next_q ? qr : nullptr, rows, c.split, &L.tail_exps, c.st);
     }
     {
         Scope sc(c.tr, TR_KV_REDUCE, rows, 0, 0, c.st);
         TRY(scream_kv_finalize(kvp, b.cloud_row0, b.cloud_len, row0, cloud_begin, n_clouds, w.kv, c.st));
     }
-    {
-        Scope sc(c.tr, TR_ATTN_APPLY, rows, 0, 0, c.st);
-        TRY(scream_attn_apply(qr, D, w.kv, b.tile_cloud + row0 / SCREAM_ROW_TILE, 0, b.cloud_len, w.att + row0 * D, D, rows,
-                              c.st));
-    }
-    return mha_tail(c, L, w, xr, y + row0 * D, row0, rows);
+    return apply_and_tail_f32(c, L, b, w, xr, y + row0 * D, row0, rows, 0);
 }
 
-// The target side of EVERY cross layer at once (fused-tail models with scream_model_t.wkv_cross): the target features are
-// frozen after the stem (models/pointnet.py:53-57), so the n_cross key/value projections read the same rows -- one GEMM with
-// N = 512 n_cross (12 n_cross column tiles per 256-row tile instead of n_cross launches of two: the persistent grid's partial
-// last round shrinks from 15 % to under 2 %) and one finalize launch for all n_cross x n_pairs K^T V images.
+// Split schedules: the target side of EVERY cross layer at once.  The target features are frozen after the stem
+// (models/pointnet.py:53-57), so the n_cross key/value projections read the same rows -- one launch with N = 512 n_cross
+// (12 n_cross column tiles per 256-row tile instead of n_cross launches of two: the persistent grid's partial last round shrinks
+// from 15 % to under 2 %) and one finalize launch for all n_cross x n_pairs K^T V images.
 int cross_kv_all(const Ctx& c, const scream_model_t& m, const scream_batch_t& b, const Workspace& w, const float* x_tgt) {
     const int64_t rs = b.rows_src, rt = b.rows_total - b.rows_src;
     const scream_layer_t& L0 = m.layers_host[m.n_self + 1];  // every cross layer sees the same target features: one e_xkv
@@ -182,46 +209,32 @@ int cross_kv_all(const Ctx& c, const scream_model_t& m, const scream_batch_t& b,
 }
 
 // Cross attention: queries from the source rows, keys/values from the frozen target rows (transformer.py:130).
-// kvimg_layer != NULL: this layer's target-side K^T V images were already built by cross_kv_all (image of target cloud j at
-// kvimg_layer + j * scream_kv_image_bytes()).
-// q_ready: Q' (w.q) was written by the layer tail of the self layer in front (scream_layer_t.tail_next_q)
+// Split schedules: kvimg_layer holds this layer's target-side K^T V images, built by cross_kv_all (image of target cloud j at
+// kvimg_layer + j * scream_kv_image_bytes()); on the fp16 splits Q' (w.q) was written by the layer tail of the self layer in front.
 int mha_cross(const Ctx& c, const scream_layer_t& L, const scream_batch_t& b, const Workspace& w, const float* x_src,
-              const float* x_tgt, float* y, const char* kvimg_layer, bool q_ready = false) {
+              const float* x_tgt, float* y, const char* kvimg_layer) {
     const int64_t rs = b.rows_src, rt = b.rows_total - b.rows_src;
-    if (!q_ready)
+    if (!c.fp16())
         TRY(gemm(c, x_src, D, L.wq, w.q, D, rs, D, D, SCREAM_EPI_ELU1, D, nullptr, nullptr, nullptr, nullptr, L.e_xq, L.e_wq,
-                 c.frag ? (SCREAM_LAYOUT_A_FRAG | SCREAM_LAYOUT_C_FRAG) : 0));
-    if (c.frag && kvimg_layer) {
+                 c.split ? (SCREAM_LAYOUT_A_FRAG | SCREAM_LAYOUT_C_FRAG) : 0));
+    if (c.split) {
         Scope sc(c.tr, TR_TAIL_FUSED, rs, 9 * D, D, c.st);
         // tile_cloud holds source cloud i for the source tiles; its target cloud's image is entry i of this layer's block
         return scream_layer_tail_f32(w.q, kvimg_layer, b.tile_cloud, 0, b.cloud_len + b.n_pairs, x_src, L.tail, L.g1, L.b1, L.g2,
                                      L.b2, y, nullptr, rs, c.split, &L.tail_exps, c.st);
     }
-    TRY(gemm_qkv(c, x_tgt, L.wkv, nullptr, nullptr, rt, 2 * D, 0, b, rs, w.kvp, L.e_xkv, L.e_wkv, L.e_k, L.e_v));
-    if (c.frag) {
-        {
-            Scope sc(c.tr, TR_KV_REDUCE, rt, 0, 0, c.st);
-            TRY(scream_kv_finalize_image(w.kvp, b.cloud_row0, b.cloud_len, rs, b.n_pairs, b.n_pairs, w.kvimg, 1, 0, 0, c.split, c.st));
-        }
-        Scope sc(c.tr, TR_TAIL_FUSED, rs, 9 * D, D, c.st);
-        return scream_layer_tail_f32(w.q, w.kvimg, b.tile_cloud, b.n_pairs, b.cloud_len, x_src, L.tail, L.g1, L.b1, L.g2, L.b2,
-                                     y, nullptr, rs, c.split, &L.tail_exps, c.st);
-    }
+    TRY(gemm_qkv(c, x_tgt, L.wkv, nullptr, nullptr, rt, 2 * D, 0, b, rs, w.kvp, 0, 0, 0, 0));
     {
         Scope sc(c.tr, TR_KV_REDUCE, rt, 0, 0, c.st);
         TRY(scream_kv_finalize(w.kvp, b.cloud_row0, b.cloud_len, rs, b.n_pairs, b.n_pairs, w.kv, c.st));
     }
-    {
-        Scope sc(c.tr, TR_ATTN_APPLY, rs, 0, 0, c.st);
-        TRY(scream_attn_apply(w.q, D, w.kv, b.tile_cloud, b.n_pairs, b.cloud_len, w.att, D, rs, c.st));
-    }
-    return mha_tail(c, L, w, x_src, y, 0, rs);
+    return apply_and_tail_f32(c, L, b, w, x_src, y, 0, rs, b.n_pairs);
 }
 
 }  // namespace
 
-extern "C" const char* scream_version(void) { return "scream_hip gfx950 abi20"; }
-extern "C" int scream_abi_version(void) { return 20; }
+extern "C" const char* scream_version(void) { return "scream_hip gfx950 abi21"; }
+extern "C" int scream_abi_version(void) { return 21; }
 
 extern "C" void* scream_trace_create(int32_t capacity) {
     if (capacity <= 0) return nullptr;
@@ -279,9 +292,9 @@ extern "C" int scream_trace_read_starts(void* trace, int32_t max_records, float*
 }
 
 extern "C" int64_t scream_forward_workspace_bytes(int64_t rows_src, int64_t rows_total, int32_t n_pairs,
-                                                  int32_t max_chunks, int32_t fused_tail, int32_t n_cross_batched) {
-    if (rows_src < 0 || rows_total < rows_src || n_pairs < 0 || max_chunks < 0 || n_cross_batched < 0) return SCREAM_EINVAL;
-    return carve(nullptr, rows_src, rows_total, n_pairs, max_chunks, fused_tail != 0, n_cross_batched).bytes + 256;
+                                                  int32_t max_chunks, int32_t gemm_split, int32_t n_cross) {
+    if (rows_src < 0 || rows_total < rows_src || n_pairs < 0 || max_chunks < 0 || !valid_split(gemm_split) || n_cross < 0) return SCREAM_EINVAL;
+    return carve(nullptr, rows_src, rows_total, n_pairs, max_chunks, gemm_split, n_cross).bytes + 256;
 }
 
 extern "C" int scream_forward(const scream_model_t* model, const scream_batch_t* batch, void* workspace,
@@ -289,29 +302,20 @@ extern "C" int scream_forward(const scream_model_t* model, const scream_batch_t*
     SCREAM_REQUIRE(model && batch && workspace && src_pred, SCREAM_EINVAL);
     const scream_model_t& m = *model;
     const scream_batch_t& b = *batch;
-    SCREAM_REQUIRE(m.layers_host && m.n_self >= 0 && m.n_cross >= 0 &&
-                       (m.gemm_split == 0 || m.gemm_split == SCREAM_SPLIT_H1 || m.gemm_split == SCREAM_SPLIT_H2 || m.gemm_split == SCREAM_SPLIT_BF3),
-                   SCREAM_EINVAL);
+    SCREAM_REQUIRE(m.layers_host && m.n_self >= 0 && m.n_cross >= 0 && valid_split(m.gemm_split), SCREAM_EINVAL);
     SCREAM_REQUIRE(b.n_pairs > 0 && b.rows_src > 0 && b.rows_total > b.rows_src && b.max_chunks > 0, SCREAM_EINVAL);
     SCREAM_REQUIRE(b.rows_src % SCREAM_ROW_TILE == 0 && b.rows_total % SCREAM_ROW_TILE == 0, SCREAM_EUNSUPPORTED);
     SCREAM_REQUIRE(b.xyz && b.center && b.tile_cloud && b.cloud_row0 && b.cloud_len, SCREAM_EINVAL);
-    // fragment-major features between the kernels iff EVERY layer carries a fused-tail image (all or none)
-    int n_layers = m.n_self + 2 * m.n_cross, n_tail = 0;
-    for (int i = 0; i < n_layers; ++i) n_tail += m.layers_host[i].tail != nullptr;
-    if (m.stem_tgt_layers_host)
-        for (int i = 0; i < m.n_self; ++i, ++n_layers) n_tail += m.stem_tgt_layers_host[i].tail != nullptr;
-    SCREAM_REQUIRE(n_tail == 0 || (n_tail == n_layers && m.gemm_split != 0), SCREAM_EINVAL);
+    const Ctx c{stream, reinterpret_cast<Trace*>(trace), m.gemm_split};
+    SCREAM_REQUIRE(model_ok(c, m), SCREAM_EINVAL);  // before the first launch: gemm_split selects the schedule, the pointers never do
     uintptr_t base = (reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255;
-    const bool batched_kv = n_tail > 0 && m.wkv_cross != nullptr && m.n_cross > 0;
-    const Workspace w = carve(reinterpret_cast<void*>(base), b.rows_src, b.rows_total, b.n_pairs, b.max_chunks, n_tail > 0,
-                              batched_kv ? m.n_cross : 0);
+    const Workspace w = carve(reinterpret_cast<void*>(base), b.rows_src, b.rows_total, b.n_pairs, b.max_chunks, c.split, m.n_cross);
     SCREAM_REQUIRE((int64_t)(base - reinterpret_cast<uintptr_t>(workspace)) + w.bytes <= workspace_bytes, SCREAM_EINVAL);
-    const Ctx c{stream, reinterpret_cast<Trace*>(trace), m.gemm_split, n_tail > 0};
 
     const int64_t rs = b.rows_src, ra = b.rows_total;
     {
         Scope sc(c.tr, TR_EMBED, ra, 0, 0, stream);
-        if (c.frag)  // straight into the layout the projections and the layer tail read
+        if (c.split)  // straight into the layout the projections and the layer tail read
             TRY(scream_pe_embed_ln_frag(b.xyz, b.tile_cloud, b.center, m.dim_t, m.emb_w, m.emb_b, m.pre_g, m.pre_b, w.x0, ra, stream));
         else
             TRY(scream_pe_embed_ln(b.xyz, b.tile_cloud, b.center, m.dim_t, m.emb_w, m.emb_b, m.pre_g, m.pre_b, w.x0, ra, stream));
@@ -330,30 +334,28 @@ extern "C" int scream_forward(const scream_model_t* model, const scream_batch_t*
         nxt = t;
     }
     const float* x_tgt = cur + rs * D;  // frozen from here on: the cross stage only writes rows [0, rs)
-    if (batched_kv) TRY(cross_kv_all(c, m, b, w, x_tgt));
+    if (c.split && m.n_cross > 0) TRY(cross_kv_all(c, m, b, w, x_tgt));
     for (int i = 0; i < 2 * m.n_cross; ++i) {  // pointnet.py:53-57
         const scream_layer_t& L = m.layers_host[m.n_self + i];
-        if (i % 2 == 0) {
-            TRY(mha_self(c, L, b, w, cur, nxt, 0, rs, 0, b.n_pairs, c.frag && L.tail_next_q));
-        } else {
-            const bool q_ready = c.frag && m.layers_host[m.n_self + i - 1].tail_next_q;
-            TRY(mha_cross(c, L, b, w, cur, x_tgt, nxt, batched_kv ? w.kvimg_cross + (i / 2) * w.kvimg_cross_stride : nullptr, q_ready));
-        }
+        if (i % 2 == 0)
+            TRY(mha_self(c, L, b, w, cur, nxt, 0, rs, 0, b.n_pairs));
+        else
+            TRY(mha_cross(c, L, b, w, cur, x_tgt, nxt, c.split ? w.kvimg_cross + (i / 2) * w.kvimg_cross_stride : nullptr));
         float* t = cur;
         cur = nxt;
         nxt = t;
     }
     // coor_mlp, pointnet.py:27-33,60
-    float* c_mid = c.frag ? w.q : w.m1;   // (fused: Q' and the idle feature buffer are dead by now)
-    float* c_out = c.frag ? nxt : w.att;
+    float* c_mid = c.split ? w.q : w.m1;   // (split: Q' and the idle feature buffer are dead by now)
+    float* c_out = c.split ? nxt : w.att;
     TRY(gemm(c, cur, D, m.c0_w, c_mid, D, rs, D, D, SCREAM_EPI_BIAS_RELU, 0, m.c0_b, nullptr, nullptr, nullptr, m.e_c0x, m.e_c0w,
-             c.frag ? SCREAM_LAYOUT_A_FRAG : 0));  // the output (and everything behind it) is row-major
+             c.split ? SCREAM_LAYOUT_A_FRAG : 0));  // the output (and everything behind it) is row-major
     TRY(gemm(c, c_mid, D, m.c2_w, c_out, D, rs, D, D, SCREAM_EPI_BIAS_RELU, 0, m.c2_b, nullptr, nullptr, nullptr, m.e_c2x, m.e_c2w));
     {
         Scope sc(c.tr, TR_COOR_HEAD, rs, 0, 0, stream);
         TRY(scream_coor_head(c_out, m.c4_w, m.c4_b, src_pred, rs, stream));
     }
-    if (feats_out && c.frag) {
+    if (feats_out && c.split) {
         TRY(scream_act_layout(cur, feats_out, rs, 0, stream));
     } else if (feats_out) {
         hipError_t e = hipMemcpyAsync(feats_out, cur, (size_t)rs * D * sizeof(float), hipMemcpyDeviceToDevice,

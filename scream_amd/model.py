@@ -22,6 +22,13 @@ from .render import RegistrationRender
 D_MODEL = 256
 NHEAD = 8
 
+# The forward's A/B switches of rounds 2-4 were measured, decided and removed: each arithmetic has one schedule.  A script that
+# still sets one to "0" would time the same forward twice and call it an A/B -- refuse it here.
+for _retired in ("SCREAM_FUSED_TAIL", "SCREAM_BATCHED_CROSS_KV", "SCREAM_FUSE_NEXT_Q", "SCREAM_RING_PROJ"):
+    if os.environ.get(_retired) == "0":
+        raise ValueError("%s=0 no longer selects anything: the switch was removed and every forward runs the schedule it used to "
+                         "default to; unset it" % _retired)
+
 
 class _MHAParams(nn.Module):
     """Parameter holder with the names of models/transformer.py:47-72."""
@@ -60,9 +67,9 @@ def pe_dim_t(d_model: int = D_MODEL) -> torch.Tensor:
 class _Pack:
     """One backend's kernel-layout image of the weights (PointTransformer._pack_weights)."""
 
-    def __init__(self, backend, sig, mt, layers, keep, fused, n_cross_batched, event, streams):
+    def __init__(self, backend, sig, mt, layers, keep, event, streams):
         self.backend, self.sig, self.mt, self.layers, self.keep = backend, sig, mt, layers, keep
-        self.fused, self.n_cross_batched, self.event, self.streams = fused, n_cross_batched, event, streams
+        self.event, self.streams = event, streams
 
 
 class PointTransformer(nn.Module):
@@ -126,31 +133,13 @@ class PointTransformer(nn.Module):
     def train_backend(self, value: str) -> None:
         self.__dict__["_train_backend"] = self._check_train_backend(value)
 
-    # split backends only: attention apply, merge + LayerNorm1 and the FFN + LayerNorm2 as one launch per block
-    # (csrc/tail_split.hip); SCREAM_FUSED_TAIL=0 falls back to attn_apply + three GEMM launches (same arithmetic, the
-    # intermediate activations then go through HBM)
-    fused_tail = os.environ.get("SCREAM_FUSED_TAIL", "1") != "0"
-
-    # fused tail only: project the frozen target features for ALL cross layers in one launch after the stem (and finalise their
-    # K^T V images in one) instead of once per cross layer; SCREAM_BATCHED_CROSS_KV=0 keeps the per-layer launches
-    batched_cross_kv = os.environ.get("SCREAM_BATCHED_CROSS_KV", "1") != "0"
-
-    # fused tail on an fp16 split only: the layer tail of every cross-stage SELF layer also projects the queries of the cross
-    # layer behind it (eight more ring stages at the end of every tile; csrc/tail_split.hip, NQ) -- six launches fewer per forward;
-    # SCREAM_FUSE_NEXT_Q=0 keeps the separate projection launches
-    fuse_next_q = os.environ.get("SCREAM_FUSE_NEXT_Q", "1") != "0"
-
-    # fused tail on an fp16 split only: the q/k/v projections (and the batched target-side key/value projection) on the RING kernel
-    # (csrc/proj_ring.hip, round 4: 64 rows per wave, epilogues riding under the next chunk's matrix instructions, no partial last
-    # round) instead of the 8-wave GEMM; SCREAM_RING_PROJ=0 keeps the GEMM (same arithmetic per product; K^T V partials summed
-    # from two halves instead of four quarters)
-    ring_proj = os.environ.get("SCREAM_RING_PROJ", "1") != "0"
-
-    def _fused_cfg(self, split) -> bool:
-        return bool(split and self.fused_tail)
+    # bench.py reads these two; every split forward runs the one-launch layer tail, and on the fp16 splits that tail projects
+    # the next cross layer's queries (include/scream_hip.h: one schedule per gemm_split).  Constants, not switches.
+    fused_tail = True
+    fuse_next_q = True
 
     def _signature(self):
-        return (self.fused_tail, self.batched_cross_kv, self.fuse_next_q, self.ring_proj) + tuple((p.data_ptr(), p._version) for p in self.parameters())
+        return tuple((p.data_ptr(), p._version) for p in self.parameters())
 
     def _layer_inputs(self):
         """(in_q, in_kv) per layer of _layer_modules() [+ per layer of _stem_tgt_modules()] and the coordinate MLP's input:
@@ -176,7 +165,7 @@ class PointTransformer(nn.Module):
 
     def _pack_weights(self, backend: Optional[str] = None) -> "_Pack":
         """The weights in the kernel layout of `backend` (default: self.gemm_backend), cached PER BACKEND and rebuilt when a
-        parameter or a fusion switch changes.  A caller that wants another arithmetic for one call (evaluate_kitti's
+        parameter changes.  A caller that wants another arithmetic for one call (evaluate_kitti's
         autocast mirror) names it here instead of toggling the module attribute: no repacking on the way in and out,
         and forwards of the other backend that are still queued keep their images.
         "h2" whose weights have no fp16 exponent in range (scales.ScaleRangeError: a LayerNorm gain or weight row so large
@@ -219,35 +208,48 @@ class PointTransformer(nn.Module):
 
         split = {"h2": _lib.SPLIT_H2, "x3": _lib.SPLIT_BF3, "f32": 0, "h1": _lib.SPLIT_H1}[backend]
         fp16_split = split in (_lib.SPLIT_H2, _lib.SPLIT_H1)  # the splits that carry power-of-two operand exponents
+        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32)
 
         def dev_mat(t):  # a weight MATRIX: fp32 [N,K], or its operand planes for the split GEMM; returns (pointer, exponent)
             if not split:
                 return dev_f32(t), 0
-            pw = ops.pack_w(t.detach().to(device=dev, dtype=torch.float32), split)
+            pw = ops.pack_w(f32(t), split)
             keep.append(pw.data)
             return pw.data_ptr(), pw.w_exp
 
+        def dev_proj(t, n_q):  # the ring projection's stage image of [q | k/v ...] rows (fp16 splits); returns (pointer, exponent)
+            pp = ops.pack_proj(f32(t), n_q, split)
+            keep.append(pp.data)
+            return pp.data_ptr(), pp.w_exp
+
+        # Each backend's image holds exactly what its schedule reads (include/scream_hip.h, scream_layer_t); every other
+        # pointer stays NULL, and scream_forward refuses a model that does not match its gemm_split.
         mods = self._layer_modules()
         tgt_mods = self._stem_tgt_modules() or []
         ins, tgt_ins, coor_in = self._layer_inputs()
         layers = (_lib.LayerT * len(mods))()
         tgt_layers = (_lib.LayerT * max(len(tgt_mods), 1))()
         ns = self.self_layer_num
-        # the cross layer behind every cross-stage self layer, when its query projection rides in that layer's tail
-        next_cross = {id(mods[i]): i + 1 for i in range(ns, len(mods) - 1, 2)} if (fp16_split and self.fused_tail and self.fuse_next_q) else {}
-        for L, m, (in_q, in_kv) in list(zip(layers, mods, ins)) + list(zip(tgt_layers, tgt_mods, tgt_ins)):
+        is_cross = [i >= ns and (i - ns) % 2 == 1 for i in range(len(mods))] + [False] * len(tgt_mods)
+        # fp16 splits: the cross layer behind every cross-stage self layer; its query projection rides in that layer's tail
+        next_cross = {id(mods[i]): i + 1 for i in range(ns, len(mods) - 1, 2)} if fp16_split else {}
+        for L, m, (in_q, in_kv), cross in zip(list(layers) + list(tgt_layers), mods + tgt_mods, ins + tgt_ins, is_cross):
             # [q | k heads 0-3 | v heads 0-3 | k heads 4-7 | v heads 4-7]: a 256-wide GEMM tile then holds K and V of
             # four heads for the same tokens, which is what the fused K^T V epilogue needs (include/scream_hip.h)
             k, v = m.k_proj.weight, m.v_proj.weight
             wkv = torch.cat([k[:128], v[:128], k[128:], v[128:]], dim=0)
-            L.wqkv, L.e_wqkv = dev_mat(torch.cat([m.q_proj.weight, wkv], dim=0))
-            L.proj = None
-            if fp16_split and self.fused_tail and self.ring_proj:  # the same matrix as the ring kernel's stage image, same exponent
-                pp = ops.pack_proj(torch.cat([m.q_proj.weight, wkv], dim=0).detach().to(device=dev, dtype=torch.float32), 256, split, L.e_wqkv)
-                keep.append(pp.data)
-                L.proj = pp.data_ptr()
-            L.wq, L.e_wq = dev_mat(m.q_proj.weight)
-            L.wkv, L.e_wkv = dev_mat(wkv)
+            wqkv = torch.cat([m.q_proj.weight, wkv], dim=0)
+            if fp16_split:
+                if not cross:
+                    L.proj, L.e_wqkv = dev_proj(wqkv, 256)
+            elif split:
+                if cross:
+                    L.wq, L.e_wq = dev_mat(m.q_proj.weight)
+                else:
+                    L.wqkv, L.e_wqkv = dev_mat(wqkv)
+            else:
+                L.wqkv, L.wq, L.wkv = dev_f32(wqkv), dev_f32(m.q_proj.weight), dev_f32(wkv)
+                L.wm, L.w1, L.w2 = dev_f32(m.merge.weight), dev_f32(m.mlp[0].weight), dev_f32(m.mlp[2].weight)
             ex = scales.layer_exps(m, in_q, in_kv) if fp16_split else {}
             L.e_xq, L.e_xkv, L.e_k, L.e_v = ex.get("e_xq", 0), ex.get("e_xkv", 0), ex.get("e_k", 0), ex.get("e_v", 0)
             wq_next = None
@@ -256,19 +258,12 @@ class PointTransformer(nn.Module):
                 wq_next = mods[nxt].q_proj.weight
                 ex.update(e_y=scales.exp_for(scales.ln_bound(*ins[nxt][0])), e_wq=scales.w_exp(wq_next))
             L.tail_exps = ops.tail_exps(**ex)
-            L.tail = None
             L.tail_next_q = int(wq_next is not None)
-            if split and self.fused_tail:  # one launch for everything behind the projections (scream_layer_tail_f32)
-                f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32)
+            if split:  # one launch for everything behind the projections (scream_layer_tail_f32)
                 img = ops.pack_tail(f32(m.merge.weight), f32(m.mlp[0].weight), f32(m.mlp[2].weight), split, L.tail_exps,
                                     Wq_next=None if wq_next is None else f32(wq_next))
                 keep.append(img.data)
                 L.tail = img.data_ptr()
-                L.wm, L.w1, L.w2 = None, None, None
-            else:  # separate GEMMs: packed with the same exponents the bounds were derived with
-                L.wm, L.e_wm_g = dev_mat(m.merge.weight)
-                L.w1, L.e_w1_g = dev_mat(m.mlp[0].weight)
-                L.w2, L.e_w2_g = dev_mat(m.mlp[2].weight)
             L.g1, L.b1 = dev_f32(m.norm1.weight), dev_f32(m.norm1.bias)
             L.g2, L.b2 = dev_f32(m.norm2.weight), dev_f32(m.norm2.bias)
         mt = _lib.ModelT()
@@ -284,17 +279,15 @@ class PointTransformer(nn.Module):
         (mt.c0_w, mt.e_c0w), mt.c0_b = dev_mat(c0w), dev_f32(self.coor_mlp[0].bias)
         (mt.c2_w, mt.e_c2w), mt.c2_b = dev_mat(c2w), dev_f32(self.coor_mlp[2].bias)
         mt.c4_w, mt.c4_b = dev_f32(self.coor_mlp[4].weight[:, :, 0]), dev_f32(self.coor_mlp[4].bias)
-        mt.wkv_cross, mt.proj_cross = None, None
-        if self._fused_cfg(split) and self.batched_cross_kv and self.cross_layer_num > 0:
-            # the cross layers' key/value projections of the (frozen) target features as ONE GEMM, models/pointnet.py:53-57
+        if split and self.cross_layer_num > 0:
+            # the cross layers' key/value projections of the (frozen) target features as ONE launch, models/pointnet.py:53-57
             cross = [m for i, m in enumerate(self.cross) if i % 2 == 1]
             stack = torch.cat([torch.cat([c.layer.k_proj.weight[:128], c.layer.v_proj.weight[:128], c.layer.k_proj.weight[128:],
                                           c.layer.v_proj.weight[128:]], dim=0) for c in cross], dim=0)
-            mt.wkv_cross, mt.e_wkv_cross = dev_mat(stack)
-            if fp16_split and self.ring_proj:
-                pp = ops.pack_proj(stack.detach().to(device=dev, dtype=torch.float32), 0, split, mt.e_wkv_cross)
-                keep.append(pp.data)
-                mt.proj_cross = pp.data_ptr()
+            if fp16_split:
+                mt.proj_cross, mt.e_wkv_cross = dev_proj(stack, 0)
+            else:
+                mt.wkv_cross, mt.e_wkv_cross = dev_mat(stack)
             cross_L = [layers[self.self_layer_num + 2 * j + 1] for j in range(self.cross_layer_num)]
             mt.e_k_cross, mt.e_v_cross = min(L.e_k for L in cross_L), min(L.e_v for L in cross_L)  # one launch: the tightest
         if fp16_split:  # coor_mlp (models/pointnet.py:27-33): LayerNorm2 output -> Conv1d + bias, relu -> Conv1d
@@ -304,8 +297,7 @@ class PointTransformer(nn.Module):
         # scream_amd/lanes.py) must order its first use of these buffers behind them (forward_packed waits once per stream)
         event = torch.cuda.Event()
         event.record(torch.cuda.current_stream(dev))
-        return _Pack(backend, sig, mt, (layers, tgt_layers), keep, self._fused_cfg(split), self.cross_layer_num if mt.wkv_cross else 0,
-                     event, {torch.cuda.current_stream(dev).cuda_stream})
+        return _Pack(backend, sig, mt, (layers, tgt_layers), keep, event, {torch.cuda.current_stream(dev).cuda_stream})
 
     # ------------------------------------------------------------------ batched entry
     def forward_packed(self, batch: PackedBatch, return_feats: bool = False, trace=None, backend: Optional[str] = None):
@@ -318,8 +310,8 @@ class PointTransformer(nn.Module):
         if ops._stream() not in pk.streams:  # first forward of this stream since the weights were packed
             torch.cuda.current_stream(dev).wait_event(pk.event)
             pk.streams.add(ops._stream())
-        need = lib.scream_forward_workspace_bytes(batch.rows_src, batch.rows_total, batch.n_pairs, batch.max_chunks, int(pk.fused),
-                                                  pk.n_cross_batched)
+        need = lib.scream_forward_workspace_bytes(batch.rows_src, batch.rows_total, batch.n_pairs, batch.max_chunks, mt.gemm_split,
+                                                  mt.n_cross)
         # one scratch buffer per stream: concurrent lanes (scream_amd/lanes.py) run forwards of the same model side by side
         if self._ws is None:
             self._ws = {}

@@ -260,7 +260,7 @@ def test_refusals_return_their_status_and_launch_nothing():
     assert (out_idx == -1).all() and (out_xyz == 1.0).all()
     lib = _lib.load()
     assert lib.scream_dsm_workspace_bytes(-1, 1, 0) == -1 and lib.scream_dsm_workspace_bytes(4, 1, 5) == -1
-    assert lib.scream_abi_version() == 20
+    assert lib.scream_abi_version() == 21
 
 
 def test_a_cloud_whose_rows_leave_the_arrays_is_skipped_on_the_device():

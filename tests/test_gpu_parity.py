@@ -440,46 +440,6 @@ def test_batched_key_value_projection_of_several_layers_equals_one_launch_per_la
         assert torch.equal(ops.kv_finalize_image(part, crow0, clen, base, 0, 3, 3, split=SPL), img_all[l])
 
 
-@pytest.mark.parametrize("backend", ["h2", "x3"])
-def test_forward_batched_cross_key_values_equals_per_layer_launches(golden, backend):
-    """The forward projects the target features for all cross layers in one launch after the stem (net.batched_cross_kv,
-    default) instead of once per cross layer: same arithmetic.  bf16 x 3: bit for bit.  fp16 x 2: the stacked matrix carries ONE
-    power-of-two exponent (its largest element's) where each layer's own matrix carries its own, so the weights' second planes
-    round differently -- fp32-rounding-level agreement, and both reproduce the reference's outputs."""
-    g = golden("e2e")
-    for seed, ns, nc, n, m, explicit in g["cases"]:
-        if int(nc) == 0:
-            continue
-        center = dev(g["center_%d" % seed]) if explicit else None
-        outs = {}
-        for batched in (True, False):
-            net = build_net(int(seed), int(ns), int(nc), backend)
-            net.batched_cross_kv = batched
-            outs[batched] = net(dev(g["src_%d" % seed]), dev(g["tgt_%d" % seed]), center, 1.0, False, False, None)[0]
-            np.testing.assert_allclose(outs[batched].cpu().numpy(), g["out_%d" % seed], rtol=2e-4, atol=5e-5, err_msg="case seed=%d" % seed)
-        if backend == "x3":
-            assert torch.equal(outs[True], outs[False])
-        else:
-            torch.testing.assert_close(outs[True], outs[False], rtol=2e-5, atol=2e-5)
-
-
-def test_forward_on_the_ring_projection_equals_the_gemm_projection(golden):
-    """The forward projects q/k/v on the ring kernel (net.ring_proj, default on the fp16 splits with the fused tail; csrc/proj_ring.hip)
-    or on the 8-wave GEMM (SCREAM_RING_PROJ=0 / net.ring_proj = False): the same products per element -- Q' is bit-identical -- with the
-    K^T V partial of a 128-row tile added up from two 64-row halves instead of four 32-row quarters: fp32-rounding-level agreement of
-    the outputs, and both reproduce the reference's."""
-    g = golden("e2e")
-    for seed, ns, nc, n, m, explicit in g["cases"]:
-        center = dev(g["center_%d" % seed]) if explicit else None
-        outs = {}
-        for ring in (True, False):
-            net = build_net(int(seed), int(ns), int(nc), "h2")
-            net.ring_proj = ring
-            outs[ring] = net(dev(g["src_%d" % seed]), dev(g["tgt_%d" % seed]), center, 1.0, False, False, None)[0]
-            np.testing.assert_allclose(outs[ring].cpu().numpy(), g["out_%d" % seed], rtol=2e-4, atol=5e-5, err_msg="case seed=%d" % seed)
-        torch.testing.assert_close(outs[True], outs[False], rtol=2e-5, atol=2e-5)
-
-
 # ----------------------------------------------------------------- A1-A6 whole forward pass
 @pytest.mark.parametrize("backend", BACKENDS)
 def test_forward_vs_reference_golden(golden, backend):
@@ -491,25 +451,6 @@ def test_forward_vs_reference_golden(golden, backend):
         assert imgs is None and tr is None and src_.shape == (1, n, 3)
         np.testing.assert_allclose(src_.cpu().numpy(), g["out_%d" % seed], rtol=2e-4, atol=5e-5,
                                    err_msg="case seed=%d" % seed)
-
-
-@pytest.mark.parametrize("backend", ["h2", "x3"])
-def test_forward_unfused_tail_vs_reference_golden(golden, backend):
-    """Each split forward has one default path (projection GEMM with fused K^T V + one-launch layer tail) and one fallback:
-    the unfused tail (SCREAM_FUSED_TAIL=0 / net.fused_tail = False: attention apply + merge GEMM + FFN-up + FFN-down launches,
-    row-major activations, the 9 KB-per-row workspace).  Same arithmetic and operand exponents, different kernels and
-    summation orders: it reproduces the reference's outputs to the default path's tolerance and agrees with the default
-    path to fp32 rounding."""
-    g = golden("e2e")
-    for seed, ns, nc, n, m, explicit in g["cases"]:
-        center = dev(g["center_%d" % seed]) if explicit else None
-        outs = {}
-        for name in ("default", "no_fused_tail"):
-            net = build_net(int(seed), int(ns), int(nc), backend)
-            net.fused_tail = name == "default"
-            outs[name] = net(dev(g["src_%d" % seed]), dev(g["tgt_%d" % seed]), center, 1.0, False, False, None)[0]
-        np.testing.assert_allclose(outs["no_fused_tail"].cpu().numpy(), g["out_%d" % seed], rtol=2e-4, atol=5e-5, err_msg="case seed=%d" % seed)
-        torch.testing.assert_close(outs["no_fused_tail"], outs["default"], rtol=2e-5, atol=2e-5)
 
 
 @pytest.mark.parametrize("backend", BACKENDS)
@@ -1012,23 +953,98 @@ def test_layer_tail_with_the_next_layers_query_projection():
         ops.layer_tail(None, kvi, tc, 0, clen, xf, plain, g1, b1, g2, b2)  # Q is required: refused on the host, before any launch
 
 
-def test_forward_with_and_without_the_fused_query_projection(golden):
-    """PointTransformer.fuse_next_q: the cross-stage self layers' tails also project the next layer's queries (six launches fewer).
-    Same products either way; the two forwards agree to fp32 rounding and both stay on the reference golden."""
-    from scream_amd.model import PointTransformer
-    sd = make_state_dict(0, 256, 2, 2)
-    g_ = torch.Generator().manual_seed(2)
-    src, tgt = torch.rand(700, 3, generator=g_) - 0.5, torch.rand(900, 3, generator=g_) - 0.5
-    outs = {}
-    for on in (True, False):
-        net = PointTransformer(256, 2, 2)
-        net.load_state_dict(sd)
-        net = net.to("cuda:0").eval()
-        net.fuse_next_q = on
-        outs[on] = net.forward_batch([dev(src)], [dev(tgt)])[0].cpu()
-        layers = net._pack_weights().layers[0]
-        assert [int(L.tail_next_q) for L in layers] == ([0, 0, 1, 0, 1, 0] if on else [0] * 6)
-    torch.testing.assert_close(outs[True], outs[False], rtol=2e-5, atol=2e-6)
+# ------------------------------------------------------- one schedule per arithmetic (include/scream_hip.h, scream_layer_t)
+MATRICES = ("wqkv", "wq", "wkv", "wm", "w1", "w2", "tail", "proj")
+# what each gemm_split's schedule reads: (self layers, cross layers, scream_model_t)
+SCHEDULE_READS = {"f32": ({"wqkv", "wq", "wkv", "wm", "w1", "w2"}, {"wqkv", "wq", "wkv", "wm", "w1", "w2"}, set()),
+                  "x3": ({"wqkv", "tail"}, {"wq", "tail"}, {"wkv_cross"}),
+                  "h2": ({"proj", "tail"}, {"tail"}, {"proj_cross"}),
+                  "h1": ({"proj", "tail"}, {"tail"}, {"proj_cross"})}
+
+
+@pytest.mark.parametrize("backend", ["h2", "h1", "x3", "f32"])
+def test_pack_holds_exactly_what_its_schedule_reads(backend):
+    """Each arithmetic has ONE forward schedule, chosen by scream_model_t.gemm_split, and its weight image holds exactly the
+    fields that schedule reads: every other pointer is NULL.  On the fp16 splits the tails of the cross-stage self layers carry
+    the next (cross) layer's query projection, and nowhere else."""
+    from scream_amd.model import DEMTransformer, PointTransformer
+    self_set, cross_set, model_set = SCHEDULE_READS[backend]
+    g_ = torch.Generator().manual_seed(3)
+    src, tgt = dev(torch.rand(200, 3, generator=g_) - 0.5), dev(torch.rand(130, 3, generator=g_) - 0.5)
+    for cls, ns, nc in ((PointTransformer, 2, 2), (DEMTransformer, 1, 1)):
+        dem = cls is DEMTransformer
+        net = cls(256, ns, nc)
+        net.load_state_dict(make_state_dict(0, 256, ns, nc, dem=dem), strict=True)
+        net = net.to(DEV).eval()
+        net.gemm_backend = backend
+        pk = net._pack_weights()
+        assert pk.backend == backend
+        layers, tgt_layers = pk.layers
+        roles = [False] * ns + [False, True] * nc  # is a cross layer
+        assert len(layers) == len(roles)
+        rows = [(L, c) for L, c in zip(layers, roles)] + ([(L, False) for L in tgt_layers] if dem else [])
+        assert len(rows) == ns + 2 * nc + (ns if dem else 0)
+        for i, (L, cross) in enumerate(rows):
+            assert {f for f in MATRICES if getattr(L, f)} == (cross_set if cross else self_set), "layer %d" % i
+        assert {f for f in ("wkv_cross", "proj_cross") if getattr(pk.mt, f)} == model_set
+        next_q = [int(L.tail_next_q) for L in layers]
+        if backend in ("h2", "h1"):
+            assert next_q == ([0, 0, 1, 0, 1, 0] if not dem else [0, 1, 0])
+        else:
+            assert next_q == [0] * len(layers)
+        assert all(int(L.tail_next_q) == 0 for L in tgt_layers)
+        assert torch.isfinite(net.forward_batch([src], [tgt])[0]).all()
+
+
+def test_forward_refuses_a_model_that_does_not_match_its_split():
+    """scream_forward checks the model against the table of its gemm_split before the first launch: a missing image, a missing
+    next-layer query projection or a tail image on fp32 is SCREAM_EINVAL and nothing is written -- never another schedule picked
+    from whichever pointers happen to be set."""
+    import ctypes as C
+    from scream_amd import _lib
+    from scream_amd.packing import PackedBatch
+    lib = _lib.load()
+    g_ = torch.Generator().manual_seed(4)
+    batch = PackedBatch.from_pairs([dev(torch.rand(200, 3, generator=g_) - 0.5)], [dev(torch.rand(130, 3, generator=g_) - 0.5)], [None])
+    assert (batch.rows_src, batch.rows_total) == (256, 512)
+    bt = _lib.BatchT()
+    bt.n_pairs, bt.rows_src, bt.rows_total, bt.max_chunks = batch.n_pairs, batch.rows_src, batch.rows_total, batch.max_chunks
+    bt.xyz, bt.center = ops._p(batch.xyz), ops._p(batch.center)
+    bt.tile_cloud, bt.cloud_row0, bt.cloud_len = (ops._p(t, torch.int32) for t in (batch.tile_cloud, batch.cloud_row0, batch.cloud_len))
+    net = build_net(0, 1, 1)
+    packs = {b: net._pack_weights(b) for b in ("h2", "x3", "f32")}
+    assert [pk.backend for pk in packs.values()] == ["h2", "x3", "f32"]
+
+    def run(pk, breakage):
+        """scream_forward on a copy of the pack's structs after breakage(model, layers); returns (rc, src_pred)."""
+        layers = type(pk.layers[0])()
+        C.memmove(layers, pk.layers[0], C.sizeof(layers))
+        mt = _lib.ModelT()
+        C.memmove(C.byref(mt), C.byref(pk.mt), C.sizeof(mt))
+        mt.layers_host = C.cast(layers, C.POINTER(_lib.LayerT))
+        breakage(mt, layers)
+        need = lib.scream_forward_workspace_bytes(batch.rows_src, batch.rows_total, batch.n_pairs, batch.max_chunks, mt.gemm_split, mt.n_cross)
+        ws = torch.empty(need, device=DEV, dtype=torch.uint8)
+        src_pred = torch.full((batch.rows_src, 3), float("nan"), device=DEV)
+        rc = lib.scream_forward(C.byref(mt), C.byref(bt), ws.data_ptr(), ws.numel(), src_pred.data_ptr(), None, None, ops._stream())
+        torch.cuda.synchronize()
+        return rc, src_pred
+
+    def setter(where, field, value):  # where: "model" or a layer index ([stem, cross-stage self, cross])
+        return lambda mt, layers: setattr(mt if where == "model" else layers[where], field, value)
+
+    for pk in packs.values():  # the copies themselves are sound: unbroken, they run
+        rc, out = run(pk, lambda mt, layers: None)
+        assert rc == 0 and torch.isfinite(out[:200]).all()
+    some_tail = packs["h2"].layers[0][0].tail
+    broken = [("h2", setter(0, "tail", None)), ("h2", setter(2, "tail", None)), ("h2", setter(0, "proj", None)),
+              ("h2", setter(1, "proj", None)), ("h2", setter(1, "tail_next_q", 0)),
+              ("x3", setter(0, "tail", None)), ("x3", setter(2, "tail", None)), ("x3", setter("model", "wkv_cross", None)),
+              ("f32", setter(1, "tail", some_tail))]
+    for i, (b, breakage) in enumerate(broken):
+        rc, out = run(packs[b], breakage)
+        assert rc == -1, "case %d (%s): SCREAM_EINVAL expected, got %d" % (i, b, rc)
+        assert torch.isnan(out).all(), "case %d (%s): refused after a launch" % (i, b)
 
 
 def test_tail_two_stream_soak_short():

@@ -1,5 +1,5 @@
 """Training surface that needs no GPU: the train() switch of PointTransformer and the host-side checks of the backward
-entry points (include/scream_hip.h, ABI 20)."""
+entry points (include/scream_hip.h, ABI 21)."""
 import torch
 
 from scream_amd import _lib
@@ -22,7 +22,7 @@ def test_explicit_train_switches_the_forward_to_the_training_path():
 
 def test_backward_entry_points_check_their_arguments_on_the_host():
     lib = _lib.load()
-    assert _lib.ABI_VERSION == 20 and lib.scream_abi_version() == 20
+    assert _lib.ABI_VERSION == 21 and lib.scream_abi_version() == 21
     # weight gradient: one partial slab of N x K (+ N column sums) per row slice
     ws = lib.scream_wgrad_workspace_bytes(330000, 256, 256)
     assert ws > 0 and ws % ((256 * 256 + 256) * 4) == 0

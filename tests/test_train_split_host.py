@@ -58,7 +58,7 @@ def test_bad_environment_value_raises_at_the_first_train():
 
 def test_split_wgrad_entry_point_checks_its_arguments_on_the_host():
     lib = _lib.load()
-    assert _lib.ABI_VERSION == 20 and lib.scream_abi_version() == 20
+    assert _lib.ABI_VERSION == 21 and lib.scream_abi_version() == 21
     ws = lib.scream_wgrad_split_workspace_bytes(330000, 256, 256)
     assert ws > 0 and ws % ((256 * 256 + 256) * 4) == 0  # one partial slab of N x K (+ N column sums) per row slice
     assert lib.scream_wgrad_split_workspace_bytes(128, 256, 256) == (256 * 256 + 256) * 4
