@@ -603,6 +603,53 @@ int scream_dsm_extract(const float* patch, const int32_t* p_row0, const int32_t*
 int scream_dsm_dem_assemble(const float* dsm, const float* dem, const int32_t* row0, const int32_t* len, int32_t n_clouds,
                             int32_t max_len, int64_t rows_total, float* out, float* centre, void* stream);
 
+/* ---- Fixed-radius search for a batch of cloud pairs: every target point within the radius of every transformed source point
+ * (the reference's utils.get_correspondences, utils.py:94-108, as datasets/three_d_match.py:106-113 calls it at 0.03 m to find
+ * the overlap of a 3DMatch pair; csrc/radius.hip).  Pair p's source points are rows s_row0[p] .. + s_len[p] of src
+ * [src_rows_total,3], its target points rows t_row0[p] .. + t_len[p] of tgt [tgt_rows_total,3] (fp32; DEVICE int32 arrays; no
+ * 128-row alignment; the clouds must not overlap), M = T[p] its transform (DEVICE doubles, [n_pairs,16], row-major 4x4; the
+ * last row is not read).  With x a source row i and b a target row j of the same pair, every step ONE IEEE float64 operation:
+ *   a_k = ((M[k][0]*x0 + M[k][1]*x1) + M[k][2]*x2) + M[k][3]          (x converted exactly from fp32)
+ *   d_k = a_k - float64(b_k)
+ *   d2  = (d0*d0 + d1*d1) + d2*d2
+ *   R2  = radius * radius
+ *   j is a neighbour of i  iff  d2 < R2                                 (STRICT: a point exactly at the radius is not one)
+ * This is FLANN's radius rule as open3d's search_radius_vector_3d uses it, up to how each evaluates the distance: the two can
+ * differ only for points exactly at the radius (to within the rounding of d2).  Parity with open3d itself is not pinned (it
+ * is not installed here).
+ *   count[row of i] = the number of neighbours of i, before any K                                      (scream_radius_count)
+ *   pair_j[offset[row] .. offset[row] + min(count, K)) = the neighbours of i in ascending (d2, j)      (scream_radius_pairs)
+ * -- nearest first, as FLANN's sorted search returns them; equal d2 goes to the LOWEST target row (that tie rule is this
+ * library's: FLANN's order among equal distances is unspecified).  Target rows are relative to t_row0[p].  K <= 0: no limit.
+ * offset [src_rows_total + 1] (DEVICE int64) is the caller's exclusive prefix sum of min(count, K) over all source rows, with
+ * the total in its last element; pair_j holds offset[last] int32 values.  A row writes at most offset[row + 1] - offset[row]
+ * values and nothing outside 0 .. offset[last], whatever offset holds.
+ * scream_radius_count fills the workspace (the target's cell lists); scream_radius_pairs reads it: hand it the SAME inputs and
+ * the SAME workspace, untouched, as the count call.  The result is a pure function of the pair: bitwise repeatable, independent
+ * of the other pairs of the call and of the launch geometry, equal to the brute-force float64 restatement of
+ * tests/radius_ref.py.  The kernels use a per-pair uniform 3-D grid over the target (cell edge >= radius, at most 64^3 cells;
+ * the cells grow with the extent: no cloud is refused for its size) as a conservative candidate filter; the predicate above
+ * alone decides membership.  No float atomics, no host synchronisation in either call.
+ * Cost: a source row evaluates (candidates in its 27 cells) distances to count and (candidates) x (neighbours + 1) to fill --
+ * the rank of a neighbour is found by counting the smaller ones.  At 0.03 m on 0.025 m voxel clouds that is about ten
+ * neighbours; a radius under which every point neighbours every point is correct but costs t_len^2 evaluations per source row.
+ * s_len[p] = 0 writes nothing.  t_len[p] = 0 gives zero counts.  n_pairs = 0 does nothing.  Rows of count outside every pair
+ * are not written.  Non-finite coordinates or matrices are outside the contract: no fault, no hang, values unspecified.
+ * SCREAM_EINVAL: a radius that is not a positive finite number; row totals outside 0 .. 2^31 - 1, max_s_len / max_t_len (host
+ * bounds of every s_len[p] / t_len[p]) negative or beyond their totals; a workspace smaller than
+ * scream_radius_workspace_bytes(tgt_rows_total, n_pairs, max_t_len) or not 16-byte aligned.  SCREAM_EUNSUPPORTED: n_pairs > 65535.
+ * All of these are decided before any launch.  A pair whose own rows fall outside the arrays or exceed max_s_len / max_t_len is
+ * found on the device: it reads and writes nothing, the other pairs are unaffected. */
+int64_t scream_radius_workspace_bytes(int64_t tgt_rows_total, int32_t n_pairs, int32_t max_t_len);
+int scream_radius_count(const float* src, const int32_t* s_row0, const int32_t* s_len, int32_t max_s_len, int64_t src_rows_total,
+                        const float* tgt, const int32_t* t_row0, const int32_t* t_len, int32_t max_t_len, int64_t tgt_rows_total,
+                        const double* T, int32_t n_pairs, double radius, int32_t* count, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+int scream_radius_pairs(const float* src, const int32_t* s_row0, const int32_t* s_len, int32_t max_s_len, int64_t src_rows_total,
+                        const float* tgt, const int32_t* t_row0, const int32_t* t_len, int32_t max_t_len, int64_t tgt_rows_total,
+                        const double* T, int32_t n_pairs, double radius, void* workspace, int64_t workspace_bytes, int32_t K,
+                        const int64_t* offset, int32_t* pair_j, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,7 +52,7 @@ class BatchT(C.Structure):
 
 
 # name -> (restype, argtypes); every symbol include/scream_hip.h declares
-V, I32, I64, F32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+V, I32, I64, F32, F64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 SIGNATURES = {
     "scream_version": (C.c_char_p, []),
     "scream_abi_version": (C.c_int, []),
@@ -117,6 +117,9 @@ SIGNATURES = {
     "scream_dsm_workspace_bytes": (C.c_int64, [I64, I32, I32]),
     "scream_dsm_extract": (C.c_int, [V, V, V, I32, I64, V, V, V, I32, I64, I32, F32, V, V, V, I64, V]),
     "scream_dsm_dem_assemble": (C.c_int, [V, V, V, V, I32, I32, I64, V, V, V]),
+    "scream_radius_workspace_bytes": (C.c_int64, [I64, I32, I32]),
+    "scream_radius_count": (C.c_int, [V, V, V, I32, I64, V, V, V, I32, I64, V, I32, F64, V, V, I64, V]),
+    "scream_radius_pairs": (C.c_int, [V, V, V, I32, I64, V, V, V, I32, I64, V, I32, F64, V, I64, I32, V, V, V]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -444,6 +444,52 @@ def dsm_dem_assemble_packed(dsm: torch.Tensor, dem: torch.Tensor, row0: torch.Te
     return out[:rows], centre[:n_clouds]
 
 
+def _radius_args(src, s_row0, s_len, max_s_len, tgt, t_row0, t_len, max_t_len, T, radius, dummy):
+    """The seventeen leading arguments scream_radius_count and scream_radius_pairs share (an empty side: nothing is read through
+    `dummy`)."""
+    n_pairs, S, N = s_row0.shape[0], src.shape[0], tgt.shape[0]
+    if T.shape[0] != n_pairs or T.numel() != n_pairs * 16:
+        raise _lib.ScreamHipError("expected %d 4x4 transforms, got %s" % (n_pairs, tuple(T.shape)))
+    return (_p(src) if S else dummy, _p(s_row0, torch.int32), _p(s_len, torch.int32), int(max_s_len), S, _p(tgt) if N else dummy,
+            _p(t_row0, torch.int32), _p(t_len, torch.int32), int(max_t_len), N, _p(T, torch.float64), n_pairs, float(radius))
+
+
+def radius_count_packed(src: torch.Tensor, s_row0: torch.Tensor, s_len: torch.Tensor, max_s_len: int, tgt: torch.Tensor,
+                        t_row0: torch.Tensor, t_len: torch.Tensor, max_t_len: int, T: torch.Tensor,
+                        radius: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """scream_radius_count on packed rows: src [S,3] / tgt [N,3] fp32, the four int32 [B] arrays and T float64 [B,4,4] on the
+    device.  Returns (count int32 [S], workspace): count[row] = the number of target rows of the row's pair with d2 < radius^2
+    (0 for rows outside every pair); the workspace holds the targets' cell lists for radius_pairs_packed.  No host sync."""
+    n_pairs, S, N, dev = s_row0.shape[0], src.shape[0], tgt.shape[0], src.device
+    lib = _lib.load()
+    need = lib.scream_radius_workspace_bytes(N, n_pairs, int(max_t_len))
+    if need < 0:
+        raise _lib.ScreamHipError("scream_radius_workspace_bytes(%d, %d, %d): invalid argument" % (N, n_pairs, max_t_len))
+    workspace = torch.empty(max(need, 16), device=dev, dtype=torch.uint8)
+    count = torch.zeros(max(S, 1), device=dev, dtype=torch.int32)
+    args = _radius_args(src, s_row0, s_len, max_s_len, tgt, t_row0, t_len, max_t_len, T, radius, count.data_ptr())
+    check(lib.scream_radius_count(*args, _p(count, torch.int32), _p(workspace, torch.uint8), workspace.numel(), _stream()),
+          "scream_radius_count")
+    return count[:S], workspace
+
+
+def radius_pairs_packed(src: torch.Tensor, s_row0: torch.Tensor, s_len: torch.Tensor, max_s_len: int, tgt: torch.Tensor,
+                        t_row0: torch.Tensor, t_len: torch.Tensor, max_t_len: int, T: torch.Tensor, radius: float,
+                        workspace: torch.Tensor, K: int, offset: torch.Tensor, total: int) -> torch.Tensor:
+    """scream_radius_pairs: the same inputs and the workspace of the radius_count_packed call that filled it; offset int64
+    [S + 1] on the device (the exclusive prefix sum of min(count, K), K <= 0: no limit) and its last element `total` as a host
+    int.  Returns pair_j int32 [total]: per source row its neighbours' target rows (relative to the pair's first) in ascending
+    (d2, j).  No host sync."""
+    S, dev = src.shape[0], src.device
+    if offset.shape[0] != S + 1:
+        raise _lib.ScreamHipError("offset: expected %d elements, got %d" % (S + 1, offset.shape[0]))
+    pair_j = torch.empty(max(int(total), 1), device=dev, dtype=torch.int32)
+    args = _radius_args(src, s_row0, s_len, max_s_len, tgt, t_row0, t_len, max_t_len, T, radius, pair_j.data_ptr())
+    check(_lib.load().scream_radius_pairs(*args, _p(workspace, torch.uint8), workspace.numel(), int(K), _p(offset, torch.int64),
+                                          _p(pair_j, torch.int32), _stream()), "scream_radius_pairs")
+    return pair_j[:int(total)]
+
+
 def kabsch_corr(src, ref, src_row0, src_len, ref_row0, idx, valid, s, c) -> Tuple[torch.Tensor, torch.Tensor]:
     """Returns (T [n_pairs,4,4], n_corr int32 [n_pairs])."""
     n_pairs = s.shape[0]
