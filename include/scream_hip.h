@@ -650,6 +650,71 @@ int scream_radius_pairs(const float* src, const int32_t* s_row0, const int32_t* 
                         const double* T, int32_t n_pairs, double radius, void* workspace, int64_t workspace_bytes, int32_t K,
                         const int64_t* offset, int32_t* pair_j, void* stream);
 
+/* ---- Training-batch preparation: augment, normalise and pack B raw pairs in one call (the reference's augment() and unit-ball /
+ * bounding-box normalisation, datasets/three_d_match.py:129-153,175-192 and datasets/kitti.py:233-273, per item on the host
+ * there; csrc/prep.hip).  raw [raw_rows,3] holds every cloud back to back, fp32 or (raw_is_f64 != 0) float64; cloud q's rows
+ * are raw_row0[q] .. + raw_len[q] (DEVICE int32 [2 n_pairs]: the sources of pairs 0 .. n_pairs - 1, then the targets); T and
+ * perturb are DEVICE doubles [n_pairs,16], row-major 4x4 whose last rows are not read (perturb = identity: no perturbation);
+ * side [n_pairs] DEVICE int32 (0: the source is perturbed, otherwise the target); sample_id [n_pairs] DEVICE int64; cloud_row0
+ * [2 n_pairs] the packed first rows of PackedBatch.layout (every cloud padded to 128 rows).  mode 0: unit ball, 1: bounding box.
+ *
+ * Every step below is ONE IEEE float64 operation on the stated operands; fp32 input is widened first (exactly).
+ *   chunk sum: the rows of a cloud in 256-row chunks, inside a chunk s = v[0]; s += v[1]; ... in ascending row order
+ *   cloud sum: acc = chunk[0]; acc += chunk[1]; ... in ascending chunk order; a union: source chunks first, then target chunks
+ *   3x3 products: every element (x*y + x*y) + x*y in ascending inner index;
+ *   apply(R, t, x)_k = ((R[k][0]*x0 + R[k][1]*x1) + R[k][2]*x2) + t_k
+ * 1. m = (cloud sum of the perturbed side's raw cloud) / n
+ * 2. P'.R = P.R;  P'.t_k = (P.t_k + m_k) - ((P.R[k][0]*m0 + P.R[k][1]*m1) + P.R[k][2]*m2)          (the reference's C^-1 P C)
+ * 3. side 0: q_k = -((P.R[0][k]*P'.t0 + P.R[1][k]*P'.t1) + P.R[2][k]*P'.t2);  T'.R = T.R P.R^T, T'.t = apply(T.R, T.t, q)   (T P'^-1)
+ *            a = apply(P.R, P'.t, x) on source rows; a = x on target rows
+ *    side 1: T'.R = P.R T.R, T'.t = apply(P.R, P'.t, T.t)   (P' T);  a = apply(P.R, P'.t, x) on target rows; a = x on source rows
+ * 4. noise_std > 0:  a_k = a_k + noise_std * z_k on both clouds, z from Philox4x32-10 with counter (row inside the cloud,
+ *    cloud: 0 source / 1 target, sample_id low word, high word) and key (seed low word, high word); with its output w0 .. w3,
+ *    u_i = (w_i + 0.5) * 2^-32:  z_x = sqrt(-2 ln u0) * cos(2 pi u1), z_y = sqrt(-2 ln u0) * sin(2 pi u1),
+ *    z_z = sqrt(-2 ln u2) * cos(2 pi u3), 2 pi the double 6.283185307179586.  The noise of a sample depends on (seed, sample_id,
+ *    cloud, row) alone.  The device's log / sin / cos are not another library's to the last bit: with noise, outputs agree with
+ *    a host restatement to within one fp32 neighbour, and are bitwise repeatable on the device.
+ * 5. reg = apply(T'.R, T'.t, a) on source rows, a on target rows.
+ *    mode 0 (three_d_match.py:183-186): c = (union sum of reg) / (N + M);  d = reg - c;  s = 1 / sqrt(max (d0*d0 + d1*d1) + d2*d2)
+ *    mode 1 (kitti.py:268-273):         c = (lo + hi) / 2;  s = 1 / ((max_k (hi_k - lo_k)) / 2),  lo / hi the bounds of reg
+ * 6. xyz = fp32(s * (a - c)) at the cloud's packed rows, every padding row exactly zero;  rot = fp32(T'.R);
+ *    trans_k = fp32(s * ((T'.t_k - c_k) + ((T'.R[k][0]*c0 + T'.R[k][1]*c1) + T'.R[k][2]*c2)));  s, c, T_aug = T' in float64
+ * 7. center [2 n_pairs,3]: target rows zero; source row p by center_rule
+ *      0  fp32((cloud sum of the fp32 xyz rows of the source, widened) / N)      (what PackedBatch.from_pairs(None) means)
+ *      1  trans                                                                   (train_3d_match.py:172)
+ *      2  fp32(-R^T tr), k-th element -((T'.R[0][k]*tr0 + T'.R[1][k]*tr1) + T'.R[2][k]*tr2), tr the float64 trans before its
+ *         rounding                                                                (train_kitti.py:156)
+ * The result of a pair is a pure function of that pair: bitwise repeatable, independent of the other pairs of the call.  No
+ * float atomics, no host synchronisation.  Non-finite coordinates and a union of zero extent (s is not finite) are OUTSIDE the
+ * contract: values unspecified, no fault; nothing looks for them.
+ * SCREAM_EINVAL: row totals outside 0 .. 2^31 - 1, max_len (host bound of every raw_len) outside 0 .. raw_rows, a mode /
+ * center_rule outside the above, a negative or non-finite noise_std, a null pointer, a workspace smaller than
+ * scream_prep_pairs_workspace_bytes(raw_rows, n_pairs, max_len) or not 16-byte aligned.  SCREAM_EUNSUPPORTED: n_pairs > 32767.
+ * A pair whose rows leave raw / xyz or exceed max_len is found on the device: it reads and writes no row. */
+int64_t scream_prep_pairs_workspace_bytes(int64_t raw_rows, int32_t n_pairs, int32_t max_len);
+int scream_prep_pairs(const void* raw, int32_t raw_is_f64, int64_t raw_rows, const int32_t* raw_row0, const int32_t* raw_len,
+                      int32_t max_len, const double* T, const double* perturb, const int32_t* side, double noise_std, uint64_t seed,
+                      const int64_t* sample_id, int32_t mode, int32_t center_rule, const int32_t* cloud_row0, int32_t n_pairs,
+                      int64_t rows_total, float* xyz, float* center, float* rot, float* trans, double* s, double* c, double* T_aug,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- The L1 point loss of a packed batch (models/pointnet.py:93-99 and 163-167) and its gradient (csrc/prep.hip).
+ *   loss_pair[p] = (cloud sum over the source rows of pair p of (|d0| + |d1|) + |d2|) / N_p,   d_k = float64(pred_k) - g_k
+ *   loss         = fp32((loss_pair[0] + loss_pair[1] + ...) / n_pairs)
+ * with the chunk and cloud sums above, in float64.  g = target row (fp32, widened) when target [rows_src,3] is given
+ * (DEMTransformer); otherwise g_k = ((R[k][0]*x0 + R[k][1]*x1) + R[k][2]*x2) + t_k from the fp32 xyz row, rot [n_pairs,9] and
+ * trans [n_pairs,3], all widened.  cloud_row0 / cloud_len are the batch's (the first n_pairs entries are read).
+ *   dpred_k = fp32((float64(dout) * sign(d_k)) / (float64(N_p) * float64(n_pairs))),  sign(0) = 0;  padding rows zero
+ * dout: one fp32 on the DEVICE.  SCREAM_EINVAL: null pointers, n_pairs / max_len / rows_src not positive, max_len > rows_src, a
+ * workspace smaller than scream_l1_pairs_workspace_bytes(n_pairs, max_len).  A pair whose rows leave [0, rows_src) is skipped. */
+int64_t scream_l1_pairs_workspace_bytes(int32_t n_pairs, int32_t max_len);
+int scream_l1_pairs_fwd(const float* pred, const float* xyz, const float* rot, const float* trans, const float* target,
+                        const int32_t* cloud_row0, const int32_t* cloud_len, int32_t n_pairs, int32_t max_len, int64_t rows_src,
+                        double* loss_pair, float* loss, void* workspace, int64_t workspace_bytes, void* stream);
+int scream_l1_pairs_bwd(const float* dout, const float* pred, const float* xyz, const float* rot, const float* trans,
+                        const float* target, const int32_t* cloud_row0, const int32_t* cloud_len, int32_t n_pairs, int32_t max_len,
+                        int64_t rows_src, float* dpred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,6 +120,12 @@ SIGNATURES = {
     "scream_radius_workspace_bytes": (C.c_int64, [I64, I32, I32]),
     "scream_radius_count": (C.c_int, [V, V, V, I32, I64, V, V, V, I32, I64, V, I32, F64, V, V, I64, V]),
     "scream_radius_pairs": (C.c_int, [V, V, V, I32, I64, V, V, V, I32, I64, V, I32, F64, V, I64, I32, V, V, V]),
+    "scream_prep_pairs_workspace_bytes": (C.c_int64, [I64, I32, I32]),
+    "scream_prep_pairs": (C.c_int, [V, I32, I64, V, V, I32, V, V, V, F64, C.c_uint64, V, I32, I32, V, I32, I64, V, V, V, V, V, V, V,
+                                    V, I64, V]),
+    "scream_l1_pairs_workspace_bytes": (C.c_int64, [I32, I32]),
+    "scream_l1_pairs_fwd": (C.c_int, [V, V, V, V, V, V, V, I32, I32, I64, V, V, V, I64, V]),
+    "scream_l1_pairs_bwd": (C.c_int, [V, V, V, V, V, V, V, V, I32, I32, I64, V, V]),
 }
 
 _lib: Optional[C.CDLL] = None

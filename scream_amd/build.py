@@ -34,6 +34,7 @@ SOURCES = {
     "voxel.hip": ["-ffp-contract=off"],
     "dsm.hip": ["-ffp-contract=off"],
     "radius.hip": ["-ffp-contract=off"],
+    "prep.hip": ["-ffp-contract=off"],
 }
 ASM_LOADS = ("gemm_split.hip", "tail_split.hip", "proj_ring.hip")  # verified after code generation, see verify_one
 # kernels that must not touch scratch at all: a spill inside a ring stage costs a round trip per stage, and hipcc orders a scratch

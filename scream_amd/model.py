@@ -405,6 +405,12 @@ class PointTransformer(nn.Module):
         reg = (torch.matmul(rot_gt, src_pcd.permute([0, 2, 1])) + trans_gt).permute([0, 2, 1])
         return torch.mean(torch.sum(torch.abs(src_pred - reg), dim=-1), dim=1).mean(dim=0)
 
+    def loss_packed(self, pred, prepared):
+        """`loss` averaged over the pairs of a prepared batch (scream_amd/prep.py), from forward_packed_train's packed prediction:
+        one HIP launch pair forward and one backward instead of B small torch graphs."""
+        from .prep import packed_l1_loss
+        return packed_l1_loss(pred, prepared)
+
 
 class DEMTransformer(PointTransformer):
     """models/pointnet.py:103-167 (ground generation on OpenGF): the same blocks with separate stem weights for the
@@ -475,3 +481,8 @@ class DEMTransformer(PointTransformer):
     def loss(self, dem_pred, dem):
         """models/pointnet.py:162-166."""
         return torch.mean(torch.sum(torch.abs(dem_pred - dem), dim=-1), dim=1).mean(dim=0)
+
+    def loss_packed(self, pred, batch, target):
+        """`loss` averaged over the samples of a packed batch; target: the DEMs packed like the prediction, [rows_src,3]."""
+        from .prep import packed_l1_loss
+        return packed_l1_loss(pred, batch, target=target)

@@ -490,6 +490,77 @@ def radius_pairs_packed(src: torch.Tensor, s_row0: torch.Tensor, s_len: torch.Te
     return pair_j[:int(total)]
 
 
+def prep_pairs_packed(raw: torch.Tensor, raw_row0: torch.Tensor, raw_len: torch.Tensor, max_len: int, T: torch.Tensor,
+                      perturb: torch.Tensor, side: torch.Tensor, noise_std: float, seed: int, sample_id: torch.Tensor, mode: int,
+                      center_rule: int, cloud_row0: torch.Tensor, rows_total: int):
+    """scream_prep_pairs: raw [rows,3] fp32 or float64 (every cloud back to back), raw_row0 / raw_len / cloud_row0 int32 [2B]
+    (sources, then targets), T / perturb float64 [B,4,4], side int32 [B], sample_id int64 [B], all on the device.  Returns
+    (xyz fp32 [rows_total,3], center fp32 [2B,3], rot fp32 [B,3,3], trans fp32 [B,3,1], s float64 [B], c float64 [B,3],
+    T_aug float64 [B,4,4]).  No host sync."""
+    B, rows, dev = side.shape[0], raw.shape[0], raw.device
+    if raw.dtype not in (torch.float32, torch.float64):
+        raise TypeError("expected torch.float32 or torch.float64 clouds, got %s" % raw.dtype)
+    if B < 1 or raw_row0.shape[0] != 2 * B or raw_len.shape[0] != 2 * B or cloud_row0.shape[0] != 2 * B or T.numel() != 16 * B or \
+            perturb.numel() != 16 * B or sample_id.shape[0] != B:
+        raise _lib.ScreamHipError("prep_pairs_packed: the per-pair arrays do not describe %d pairs" % B)
+    lib = _lib.load()
+    need = lib.scream_prep_pairs_workspace_bytes(rows, B, int(max_len))
+    if need < 0:
+        raise _lib.ScreamHipError("scream_prep_pairs_workspace_bytes(%d, %d, %d): invalid argument" % (rows, B, max_len))
+    workspace = torch.empty(max(need, 16), device=dev, dtype=torch.uint8)
+    xyz = torch.empty(int(rows_total), 3, device=dev, dtype=torch.float32)
+    center = torch.empty(2 * B, 3, device=dev, dtype=torch.float32)
+    rot = torch.empty(B, 3, 3, device=dev, dtype=torch.float32)
+    trans = torch.empty(B, 3, 1, device=dev, dtype=torch.float32)
+    s = torch.empty(B, device=dev, dtype=torch.float64)
+    c = torch.empty(B, 3, device=dev, dtype=torch.float64)
+    T_aug = torch.empty(B, 4, 4, device=dev, dtype=torch.float64)
+    check(lib.scream_prep_pairs(_p(raw, raw.dtype), int(raw.dtype == torch.float64), rows, _p(raw_row0, torch.int32),
+                                _p(raw_len, torch.int32), int(max_len), _p(T, torch.float64), _p(perturb, torch.float64),
+                                _p(side, torch.int32), float(noise_std), int(seed) & (2 ** 64 - 1), _p(sample_id, torch.int64), int(mode),
+                                int(center_rule), _p(cloud_row0, torch.int32), B, int(rows_total), _p(xyz), _p(center), _p(rot),
+                                _p(trans), _p(s, torch.float64), _p(c, torch.float64), _p(T_aug, torch.float64),
+                                _p(workspace, torch.uint8), workspace.numel(), _stream()), "scream_prep_pairs")
+    return xyz, center, rot, trans, s, c, T_aug
+
+
+def _l1_args(pred, xyz, rot, trans, target, cloud_row0, cloud_len, n_pairs, max_len):
+    rows_src = pred.shape[0]
+    if pred.dim() != 2 or pred.shape[1] != 3:
+        raise _lib.ScreamHipError("the packed prediction is [rows_src,3], got %s" % (tuple(pred.shape),))
+    if target is not None:
+        if tuple(target.shape) != tuple(pred.shape):
+            raise _lib.ScreamHipError("the packed target must have the prediction's shape %s, got %s" % (tuple(pred.shape), tuple(target.shape)))
+    elif xyz.shape[0] < rows_src or rot.numel() != 9 * n_pairs or trans.numel() != 3 * n_pairs:
+        raise _lib.ScreamHipError("l1_pairs: xyz / rot / trans do not describe %d pairs over %d source rows" % (n_pairs, rows_src))
+    return (_p(pred), _p(xyz), _p(rot), _p(trans), _p(target), _p(cloud_row0, torch.int32), _p(cloud_len, torch.int32), int(n_pairs),
+            int(max_len), rows_src)
+
+
+def l1_pairs_fwd(pred: torch.Tensor, xyz: Optional[torch.Tensor], rot: Optional[torch.Tensor], trans: Optional[torch.Tensor],
+                 target: Optional[torch.Tensor], cloud_row0: torch.Tensor, cloud_len: torch.Tensor, n_pairs: int,
+                 max_len: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """scream_l1_pairs_fwd: (loss fp32 scalar, loss_pair float64 [B]) of the packed prediction [rows_src,3] against rot / trans
+    applied to the packed xyz, or against the packed `target` [rows_src,3] when it is given.  No host sync."""
+    lib, dev = _lib.load(), pred.device
+    workspace = torch.empty(max(lib.scream_l1_pairs_workspace_bytes(int(n_pairs), int(max_len)), 16), device=dev, dtype=torch.uint8)
+    loss_pair = torch.empty(n_pairs, device=dev, dtype=torch.float64)
+    loss = torch.empty((), device=dev, dtype=torch.float32)
+    check(lib.scream_l1_pairs_fwd(*_l1_args(pred, xyz, rot, trans, target, cloud_row0, cloud_len, n_pairs, max_len),
+                                  _p(loss_pair, torch.float64), _p(loss), _p(workspace, torch.uint8), workspace.numel(), _stream()),
+          "scream_l1_pairs_fwd")
+    return loss, loss_pair
+
+
+def l1_pairs_bwd(dout: torch.Tensor, pred: torch.Tensor, xyz, rot, trans, target, cloud_row0: torch.Tensor, cloud_len: torch.Tensor,
+                 n_pairs: int, max_len: int) -> torch.Tensor:
+    """scream_l1_pairs_bwd: dpred fp32 [rows_src,3] for the upstream gradient `dout` (one fp32 on the device)."""
+    dpred = torch.empty_like(pred)
+    check(_lib.load().scream_l1_pairs_bwd(_p(dout), *_l1_args(pred, xyz, rot, trans, target, cloud_row0, cloud_len, n_pairs, max_len),
+                                          _p(dpred), _stream()), "scream_l1_pairs_bwd")
+    return dpred
+
+
 def kabsch_corr(src, ref, src_row0, src_len, ref_row0, idx, valid, s, c) -> Tuple[torch.Tensor, torch.Tensor]:
     """Returns (T [n_pairs,4,4], n_corr int32 [n_pairs])."""
     n_pairs = s.shape[0]
