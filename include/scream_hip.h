@@ -562,6 +562,58 @@ int scream_voxel_down_sample(const float* xyz, const int32_t* row0, const int32_
                              const double* voxel, float* out_xyz, int32_t* out_len, int32_t* out_count, void* workspace,
                              int64_t workspace_bytes, void* stream);
 
+/* ---- Point-to-point ICP of RAW scans in float64 (csrc/icp_raw.hip): the pose refinement datasets/kitti.py:105-126 runs with
+ * open3d.registration_icp on the unvoxelised scans (~120 k points each, +-80 m, radius 0.2 m, start pose from the odometry).
+ * Parity with open3d itself is unpinned (it is not installed); the loop is open3d's published RegistrationICP with
+ * TransformationEstimationPointToPoint, and tests/rawicp_ref.py restates every step below in numpy.
+ * src / tgt: packed fp32 [rows,3] exactly as the .bin files hold them (metric: there is no s / c); pair p is rows
+ * src_row0[p] .. + src_len[p] and tgt_row0[p] .. + tgt_len[p]; the clouds of a batch may be packed in any order.  T float64
+ * [n_pairs,16] (row-major 4x4) holds the start poses on entry and the results on return.  Every step is ONE IEEE float64
+ * operation, in this order, without fma contraction:
+ *   transform    a_k = ((t_k0 x + t_k1 y) + t_k2 z) + t_k3 from the fp32 row
+ *   distance     d2 = (dx^2 + dy^2) + dz^2 with d = a - b (direct differences; b the fp32 target row)
+ *   selection    the nearest target row wins; equal d2 goes to the LOWEST original target row
+ *   rule         a correspondence iff d2 < r2, STRICTLY, r2 = the double product max_corr_dist * max_corr_dist (the FLANN rule)
+ *   grid         origin = min_bound - h / 2 over the target, cell edge h = max_corr_dist, cell(v) = floor((v - origin) / h) per
+ *                axis for source and target alike, a query scans cell(a - R) .. cell(a + R) per axis.  The grid only filters:
+ *                the result equals the brute-force search bit for bit
+ *   sums         count, sum d2, sum a, sum b, sum a b^T (with b widened) per evaluation.  A chunk = 256 consecutive source rows,
+ *                a row without a correspondence contributing 0.0; inside a chunk each wave of 64 rows by the butterfly
+ *                v += v[lane ^ 1], ^ 2, ^ 4, ^ 8, ^ 16, ^ 32, then the four waves as (w0 + w1) + (w2 + w3); the chunk sums of a
+ *                pair sequentially in ascending chunk order from 0.0.  No float atomics: a pair's result depends neither on its
+ *                batch nor on how the schedule was cut
+ *   evaluation   fitness = cnt / N (0 for N = 0), inlier_rmse = sqrt(sum d2 / cnt) (0 for cnt = 0)
+ *   update       cA = sum a / cnt, cB = sum b / cnt (no + 1e-6); H = sum a b^T - cA (sum b)^T; R = V diag(1, 1, det) U^T from
+ *                the float64 Jacobi SVD of csrc/svd3.h, entries (V_i0 U_j0 + V_i1 U_j1) + delta V_i2 U_j2;
+ *                t = cB - R cA with (R_i0 cA_0 + R_i1 cA_1) + R_i2 cA_2; T <- dT . T accumulated in k order
+ *   stop         after the evaluation where |d fitness| < rel_fitness and |d rmse| < rel_rmse (float64, against the previous
+ *                evaluation), or after max_iter updates.  iters = the number of updates applied
+ * An evaluation without correspondences (an empty source included) takes the identity as its update and goes on: T stays the
+ * start pose bit for bit, and iters follows the rule documented for scream_icp_p2p (1 with positive thresholds, max_iter with a
+ * zero threshold, 0 for max_iter = 0).
+ * Pair status: a pair whose target needs more than 2^21 cells on an axis, that holds a non-finite coordinate, whose rows do not
+ * fit (row0 < 0, len < 0 or > max_*_len, row0 + len > *_rows_total), or any pair of a call whose radius is not positive and
+ * finite, gets iters = -1, its T is untouched and its flag is set; the other pairs are unaffected.
+ * scream_icp_raw_range follows scream_icp_p2p_range: it enqueues iterations [it_begin, it_end) of the run (iteration `it` =
+ * search under T_it, then evaluation it: stop or update; max_iter + 1 iterations at most), it_begin == 0 also does the set-up
+ * (grid, records, status), every call of a run gets the same arguments and workspace, the per-pair stopped flags are copied to
+ * done_flags [n_pairs] (device int32, may be NULL), and nothing ever waits for the device.  fitness_rmse [n_pairs,2] float64 and
+ * iters may be NULL.  workspace: scream_icp_raw_workspace_bytes bytes, 256-byte aligned.  n_pairs <= 65535.
+ * scream_icp_raw_nn is the loop's search alone under the given T: idx int32 [src_rows_total] (-1: no target row with d2 < r2) and
+ * d2 float64 (+inf for none) at every row of every accepted pair (other rows are not written), status int32 [n_pairs] (0 / -1,
+ * may be NULL). */
+int64_t scream_icp_raw_workspace_bytes(int64_t src_rows_total, int64_t tgt_rows_total, int32_t n_pairs);
+int scream_icp_raw_range(const float* src, const float* tgt, const int32_t* src_row0, const int32_t* src_len,
+                         const int32_t* tgt_row0, const int32_t* tgt_len, int32_t n_pairs, int32_t max_src_len,
+                         int32_t max_tgt_len, int64_t src_rows_total, int64_t tgt_rows_total, double max_corr_dist,
+                         int32_t max_iter, double rel_fitness, double rel_rmse, double* T, double* fitness_rmse, int32_t* iters,
+                         int32_t it_begin, int32_t it_end, int32_t* done_flags, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+int scream_icp_raw_nn(const float* src, const float* tgt, const int32_t* src_row0, const int32_t* src_len,
+                      const int32_t* tgt_row0, const int32_t* tgt_len, int32_t n_pairs, int32_t max_src_len, int32_t max_tgt_len,
+                      int64_t src_rows_total, int64_t tgt_rows_total, double radius, const double* T, int32_t* idx, double* d2,
+                      int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- DSM extraction for a batch of OpenGF windows (the reference's process_open_gf.py:219-228: for every ground point, the
  * highest window point within the radius in the xy plane; csrc/dsm.hip).  Cloud c's window points ("patch") are rows
  * p_row0[c] .. + p_len[c] of patch [patch_rows_total,3], its ground points ("dem") rows d_row0[c] .. + d_len[c] of dem

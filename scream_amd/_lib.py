@@ -126,6 +126,9 @@ SIGNATURES = {
     "scream_l1_pairs_workspace_bytes": (C.c_int64, [I32, I32]),
     "scream_l1_pairs_fwd": (C.c_int, [V, V, V, V, V, V, V, I32, I32, I64, V, V, V, I64, V]),
     "scream_l1_pairs_bwd": (C.c_int, [V, V, V, V, V, V, V, V, I32, I32, I64, V, V]),
+    "scream_icp_raw_workspace_bytes": (C.c_int64, [I64, I64, I32]),
+    "scream_icp_raw_range": (C.c_int, [V, V, V, V, V, V, I32, I32, I32, I64, I64, F64, I32, F64, F64, V, V, V, I32, I32, V, V, I64, V]),
+    "scream_icp_raw_nn": (C.c_int, [V, V, V, V, V, V, I32, I32, I32, I64, I64, F64, V, V, V, V, V, I64, V]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -35,11 +35,16 @@ SOURCES = {
     "dsm.hip": ["-ffp-contract=off"],
     "radius.hip": ["-ffp-contract=off"],
     "prep.hip": ["-ffp-contract=off"],
+    # every step of the raw-scan ICP is one IEEE float64 operation in a documented order (the file header)
+    "icp_raw.hip": ["-ffp-contract=off"],
 }
 ASM_LOADS = ("gemm_split.hip", "tail_split.hip", "proj_ring.hip")  # verified after code generation, see verify_one
 # kernels that must not touch scratch at all: a spill inside a ring stage costs a round trip per stage, and hipcc orders a scratch
 # reload against the LDS-DMA in flight with vmcnt(0) -- the ring would drain once per stage (the layer tail's history)
 NO_SCRATCH = {"proj_ring.hip": ("proj_ring_kernel",), "tail_split.hip": ("tail_kernelINS_7SplitH2", "tail_kernelINS_7SplitH1")}
+# kernels outside ASM_LOADS that must not touch scratch either: the raw-scan ICP search keeps its eight stepped binary searches
+# and its best candidate in registers (a spill would sit inside the dependent-load chain that bounds it)
+NO_SCRATCH_PLAIN = {"icp_raw.hip": ("raw_search_kernel", "raw_nn_kernel")}
 
 
 def _hipcc() -> str:
@@ -115,8 +120,34 @@ def build(force: bool = False, verbose: bool = False, out: str = None) -> str:
                                    % (src, name, hz[0][3], hz[0][2], hz[0][1]))
         return src
 
+    def verify_no_scratch(src):
+        """The kernels of NO_SCRATCH_PLAIN in the code the build ships (same flags, assembly instead of an object)."""
+        asm = os.path.join(objdir, src.replace(".hip", ".s"))
+        cmd = common + SOURCES[src] + ["-S", "--cuda-device-only", os.path.join(CSRC, src), "-o", asm]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("hipcc -S failed for %s:\n%s" % (src, r.stderr))
+        text = open(asm).read()
+        for kernel in NO_SCRATCH_PLAIN[src]:
+            at = text.find(".amdhsa_kernel")
+            found = False
+            while at >= 0:
+                end = text.find(".end_amdhsa_kernel", at)
+                block = text[at:end]
+                if kernel in block.split("\n", 1)[0]:
+                    found = True
+                    size = [l.split()[-1] for l in block.splitlines() if ".amdhsa_private_segment_fixed_size" in l]
+                    if size != ["0"]:
+                        raise RuntimeError("%s: %s uses %s bytes of scratch per lane" % (src, kernel, size))
+                at = text.find(".amdhsa_kernel", end)
+            if not found:
+                raise RuntimeError("%s: kernel %s not found in the generated assembly" % (src, kernel))
+        return src
+
     with ThreadPoolExecutor(max_workers=4) as ex:
-        checks = [ex.submit(verify_one, src) for src in ASM_LOADS] if os.environ.get("SCREAM_BUILD_VERIFY", "1") != "0" else []
+        verify = os.environ.get("SCREAM_BUILD_VERIFY", "1") != "0"
+        checks = [ex.submit(verify_one, src) for src in ASM_LOADS] if verify else []
+        checks += [ex.submit(verify_no_scratch, src) for src in NO_SCRATCH_PLAIN] if verify else []
         objs = list(ex.map(compile_one, SOURCES.items()))
         for c in checks:
             c.result()
