@@ -21,6 +21,24 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// ---- host helpers of the ops on packed clouds (the rows of many clouds back to back, row0 / len per cloud)
+static inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
+// blocks of 256 threads that cover the longest cloud of a call
+static inline unsigned row_blocks(int32_t max_len) { return (unsigned)(((int64_t)max_len + 255) / 256); }
+// what a caller may declare about one packed array: int32 row indices, no cloud longer than the array
+static inline bool rows_ok(int64_t rows, int32_t max_len) { return rows >= 0 && rows <= INT32_MAX && max_len >= 0 && max_len <= rows; }
+// A workspace handed out front to back, every piece at a multiple of 256 bytes.  Carved from a null base it only measures:
+// `used` afterwards is the size that the same sequence of take() calls needs.
+struct Carver {
+    void* base;
+    int64_t used = 0;
+    template <class T> T* take(int64_t count) {
+        T* r = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + (uintptr_t)used);
+        used += align256(count * (int64_t)sizeof(T));
+        return r;
+    }
+};
+
 // Row index inside a 32x32 MFMA accumulator tile held by lane (lane>>5 = half) in register reg.
 // (cdna_hip_programming.md section 3: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * half.)
 __device__ __forceinline__ int mfma32_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }

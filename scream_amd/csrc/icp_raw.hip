@@ -65,19 +65,18 @@ inline int64_t raw_workspace_bytes(int64_t src_rows, int64_t tgt_rows, int32_t n
            align256(chunks_cap(src_rows, n_pairs) * RI_NP * 8) + align256(tgt_rows * 16) + workspace_bytes(tgt_rows, n_pairs);
 }
 inline RawCarve raw_carve(void* workspace, int64_t src_rows, int64_t tgt_rows, int32_t n_pairs) {
-    char* w = reinterpret_cast<char*>(workspace);
-    auto take = [&](int64_t bytes) { char* r = w; w += align256(bytes); return r; };
+    Carver w{workspace};
     RawCarve c;
-    c.voxel = reinterpret_cast<double*>(take((int64_t)n_pairs * 8));
-    c.status = reinterpret_cast<int32_t*>(take((int64_t)n_pairs * 4));
-    c.done = reinterpret_cast<int32_t*>(take((int64_t)n_pairs * 4));
-    c.chunk0 = reinterpret_cast<int32_t*>(take((int64_t)n_pairs * 4));
-    c.src_ok = reinterpret_cast<int32_t*>(take((int64_t)n_pairs * 4));
-    c.n_src = reinterpret_cast<int32_t*>(take((int64_t)n_pairs * 4));
-    c.state = reinterpret_cast<double*>(take((int64_t)n_pairs * 16));
-    c.part = reinterpret_cast<double*>(take(chunks_cap(src_rows, n_pairs) * RI_NP * 8));
-    c.rec = reinterpret_cast<f32x4*>(take(tgt_rows * 16));
-    c.sort_ws = w;
+    c.voxel = w.take<double>(n_pairs);
+    c.status = w.take<int32_t>(n_pairs);
+    c.done = w.take<int32_t>(n_pairs);
+    c.chunk0 = w.take<int32_t>(n_pairs);
+    c.src_ok = w.take<int32_t>(n_pairs);
+    c.n_src = w.take<int32_t>(n_pairs);
+    c.state = w.take<double>(2 * (int64_t)n_pairs);
+    c.part = w.take<double>(chunks_cap(src_rows, n_pairs) * RI_NP);
+    c.rec = w.take<f32x4>(tgt_rows);
+    c.sort_ws = w.take<char>(0);
     return c;
 }
 

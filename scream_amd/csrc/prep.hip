@@ -37,7 +37,6 @@ namespace {
 constexpr int PREP_CHUNK = 256;
 constexpr int ROW_TILE = 128;  // a packed cloud is zero padded to this (scream_amd/packing.py)
 
-inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
 inline int32_t n_chunks(int32_t max_len) { return (int32_t)(((int64_t)max_len + PREP_CHUNK - 1) / PREP_CHUNK); }
 
 struct PrepWs {

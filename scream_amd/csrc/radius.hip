@@ -12,33 +12,17 @@
 // tests/radius_ref.py.  No floating-point atomics; the integer atomics below (cell counts, scatter cursors) only decide the
 // order of the records INSIDE a cell, which no result depends on.
 //
-// The grid is a candidate filter only.  Per pair, a uniform 3-D grid over the exact fp32 bounds of its TARGET cloud:
-//   cell edge h = max(R * RAD_EDGE_SLACK, largest extent / side), at most side^3 <= RAD_MAX_SIDE^3 cells per pair (side is
-//   fixed per call from max_t_len: about RAD_CELLS_PER_ROW cells per row of the call's largest target) -- a large extent makes
-//   the cells larger, never refuses the cloud;
-//   cell_k(v) = clamp(floor((v - origin_k) * (1 / h)), 0, n_k - 1), evaluated in float64 for source AND target coordinates
-//   (a target's fp32 coordinate is converted exactly), every step monotone non-decreasing in v.
-// A query at a scans, per axis, the cells  cell(a - R) .. cell(a + R)  (both sums rounded to float64).  Conservative because:
-//   a neighbour has d2 < R2.  Every addend of d2 is non-negative and rounding is monotone, so fl(d_k * d_k) <= d2 < fl(R * R),
-//   hence d_k^2 < R^2 in real numbers (d_k^2 >= R^2 would round to >= fl(R * R)), hence |fl(a_k - b_k)| < R, hence
-//   |a_k - b_k| < R in real numbers (|a_k - b_k| >= R would round to >= R, R being a float64).  So a_k - R < b_k < a_k + R.
-//   b_k is itself a float64 and rounding is monotone, so fl(a_k + R) >= b_k >= fl(a_k - R).  cell() is the SAME monotone
-//   function for both clouds, so cell(fl(a_k - R)) <= cell(b_k) <= cell(fl(a_k + R)) whatever the rounding inside cell() itself:
-//   |a_k - b_k| < R puts b within the scanned cells.  That is why the source's cell must not come from a different (say
-//   fp32) expression than the target's: two functions that round differently may disagree about a point on a cell border.
-//   The scanned range is at most three cells per axis, i.e. b lies within one cell of a: h >= R (1 + 2^-10), so a + R and a - R
-//   differ by less than 2 - 2^-10 cell edges, and the float64 roundings of the sums and inside cell() move an unclamped value
-//   (|value| <= side + 2 <= 66 near the grid; everything beyond clamps to the same border cell) by less than 2^-40.  The nine
-//   (y, z) runs below rely on that.
-//   The clamp keeps a query outside the target's bounding box on the border cells: beyond reach its runs hold nobody who passes
-//   the predicate, just outside it still meets the border cells' points.
+// The grid is a candidate filter only: cell_grid.h (D = 3, over the TARGET cloud) builds it and states why a query that scans
+// cell(lo) .. cell(hi)  per axis with lo <= b_k <= hi for every neighbour b loses nobody.  The step that is this op's own: a query
+// at a scans  cell(a - R) .. cell(a + R)  (both sums rounded to float64).  A neighbour has d2 < R2.  Every addend of d2 is
+// non-negative and rounding is monotone, so fl(d_k * d_k) <= d2 < fl(R * R), hence d_k^2 < R^2 in real numbers (d_k^2 >= R^2
+// would round to >= fl(R * R)), hence |fl(a_k - b_k)| < R, hence |a_k - b_k| < R in real numbers (|a_k - b_k| >= R would round
+// to >= R, R being a float64).  So a_k - R < b_k < a_k + R; b_k is itself a float64 and rounding is monotone, so
+// fl(a_k + R) >= b_k >= fl(a_k - R).  The scanned range is at most three cells per axis (cell_grid.h); the nine (y, z) runs
+// below rely on that.  At most side^3 <= RAD_MAX_SIDE^3 cells per pair, side fixed per call from max_t_len: about
+// RAD_CELLS_PER_ROW cells per row of the call's largest target.
 //
-//   plan     one block per pair: rows checked against the arrays, fp32 bounds of the target, grid origin / edge / dimensions
-//   count    one thread per target row: integer atomic on its cell's counter (the counters are zeroed by a memset node)
-//   scan     one block per pair: exclusive scan of the counters in place (cell order (z * ny + y) * nx + x, so the cells of one
-//            (y, z) that a query touches are ONE contiguous run of records)
-//   scatter  one thread per target row: record {x, y, z, row} at the cell's cursor; afterwards the counter of cell c holds the
-//            END of cell c, i.e. the start of cell c + 1
+//   grid     cell_grid_enqueue: zero, plan, count, scan, scatter
 //   query    one thread per source row: the eighteen cell-start loads of its nine runs go out together (into LDS, so the run
 //            loops are not unrolled), then the candidates four at a time.  The count launch and the fill launch enumerate through
 //            the same for_each_candidate / dist2, so they cannot disagree.
@@ -50,6 +34,7 @@
 // cannot fault or hang.
 #include <math.h>
 
+#include "cell_grid.h"
 #include "common.h"
 
 namespace {
@@ -60,176 +45,13 @@ constexpr int RAD_CELLS_PER_ROW = 8;  // indoor clouds are surfaces: most cells 
 constexpr double RAD_EDGE_SLACK = 1.0 + 1.0 / 1024.0;      // cell edge >= R * this: a query scans at most 3 cells per axis
 constexpr int RAD_BLOCK = 256;
 
-struct RadPlan {
-    double o[3], inv_h;
-    int32_t n[3];
-    int32_t s_row0, s_len;  // all four 0 for a pair whose rows are outside the arrays: such a pair reads and writes nothing
-    int32_t t_row0, t_len;
-    int32_t pad;
-};
-static_assert(sizeof(RadPlan) == 64, "plan layout");
-
-inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
+using RadPlan = GridPlan<3>;  // binned: the target; querying: the source
 
 // cells per axis of every pair of a call
 inline int grid_side(int32_t max_t_len) {
     int s = RAD_MIN_SIDE;
     while (s < RAD_MAX_SIDE && (int64_t)s * s * s < (int64_t)RAD_CELLS_PER_ROW * max_t_len) s *= 2;
     return s;
-}
-
-struct Carve {
-    RadPlan* plan;
-    int32_t* cells;  // [n_pairs][side^3]
-    f32x4* recs;     // [t_rows] records in cell order, per pair from its own first target row
-    int64_t cell_bytes;
-};
-inline int64_t workspace_bytes(int64_t t_rows, int32_t n_pairs, int32_t max_t_len) {
-    const int64_t side = grid_side(max_t_len);
-    return align256((int64_t)n_pairs * (int64_t)sizeof(RadPlan)) + align256((int64_t)n_pairs * side * side * side * 4) +
-           align256(t_rows * 16);
-}
-inline Carve carve(void* workspace, int64_t t_rows, int32_t n_pairs, int32_t max_t_len) {
-    char* w = reinterpret_cast<char*>(workspace);
-    auto take = [&](int64_t bytes) { char* r = w; w += align256(bytes); return r; };
-    const int64_t side = grid_side(max_t_len);
-    Carve c;
-    c.cell_bytes = (int64_t)n_pairs * side * side * side * 4;
-    c.plan = reinterpret_cast<RadPlan*>(take((int64_t)n_pairs * (int64_t)sizeof(RadPlan)));
-    c.cells = reinterpret_cast<int32_t*>(take(c.cell_bytes));
-    c.recs = reinterpret_cast<f32x4*>(take(t_rows * 16));
-    return c;
-}
-
-// floor(v) clamped to [0, n - 1]; NaN -> 0.  Monotone non-decreasing in v.
-__device__ __forceinline__ int clamp_cell(double v, int n) {
-    double c = floor(v);
-    c = c >= 0.0 ? c : 0.0;
-    c = c <= (double)(n - 1) ? c : (double)(n - 1);
-    return (int)c;
-}
-// THE cell coordinate, of source and target points alike
-__device__ __forceinline__ int cell_of(const RadPlan& p, int k, double v) { return clamp_cell((v - p.o[k]) * p.inv_h, p.n[k]); }
-
-// grid n_pairs, block 256
-__global__ __launch_bounds__(256) void radius_plan_kernel(const float* __restrict__ tgt, const int32_t* __restrict__ s_row0,
-                                                         const int32_t* __restrict__ s_len, const int32_t* __restrict__ t_row0,
-                                                         const int32_t* __restrict__ t_len, int32_t max_s_len, int32_t max_t_len,
-                                                         int64_t s_rows, int64_t t_rows, double R, int side,
-                                                         RadPlan* __restrict__ plan) {
-    __shared__ float red[6][4];
-    const int c = blockIdx.x, t = threadIdx.x;
-    const int64_t sr = s_row0[c], sn = s_len[c], tr = t_row0[c], tn = t_len[c];
-    const bool ok = sr >= 0 && sn >= 0 && sn <= max_s_len && sr + sn <= s_rows && tr >= 0 && tn >= 0 && tn <= max_t_len &&
-                    tr + tn <= t_rows;
-    const int n = ok ? (int)tn : 0;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = t; i < n; i += 256)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float v = tgt[(tr + i) * 3 + k];
-            lo[k] = fminf(lo[k], v);
-            hi[k] = fmaxf(hi[k], v);
-        }
-    for (int m = 1; m < 64; m <<= 1)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = fminf(lo[k], __shfl_xor(lo[k], m));
-            hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], m));
-        }
-    if ((t & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            red[k][t >> 6] = lo[k];
-            red[3 + k][t >> 6] = hi[k];
-        }
-    __syncthreads();
-    if (t != 0) return;
-    for (int w = 1; w < 4; ++w)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = fminf(lo[k], red[k][w]);
-            hi[k] = fmaxf(hi[k], red[3 + k][w]);
-        }
-    RadPlan p = {};
-    p.s_row0 = ok ? (int32_t)sr : 0;
-    p.s_len = ok ? (int32_t)sn : 0;
-    p.t_row0 = ok ? (int32_t)tr : 0;
-    p.t_len = n;
-    p.n[0] = p.n[1] = p.n[2] = 1;
-    p.inv_h = 0.0;
-    if (n > 0) {
-        double e[3], h = R * RAD_EDGE_SLACK;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            e[k] = (double)hi[k] - (double)lo[k];  // exact
-            h = fmax(h, e[k] / (double)side);
-            p.o[k] = (double)lo[k];
-        }
-        p.inv_h = 1.0 / h;
-        // the largest coordinate has the largest cell (cell_of is monotone): no target lies beyond n[k] even without the clamp
-#pragma unroll
-        for (int k = 0; k < 3; ++k) p.n[k] = clamp_cell(e[k] * p.inv_h, side) + 1;
-    }
-    plan[c] = p;
-}
-
-__device__ __forceinline__ int cell_index(const RadPlan& p, float x, float y, float z) {
-    const int cx = cell_of(p, 0, (double)x), cy = cell_of(p, 1, (double)y), cz = cell_of(p, 2, (double)z);
-    return (cz * p.n[1] + cy) * p.n[0] + cx;
-}
-
-// grid (ceil(max_t_len / 256), n_pairs)
-__global__ __launch_bounds__(256) void radius_cell_count_kernel(const float* __restrict__ tgt, const RadPlan* __restrict__ plan,
-                                                               int64_t cells_per_pair, int32_t* __restrict__ cells) {
-    const RadPlan& p = plan[blockIdx.y];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= p.t_len) return;
-    const int64_t row = (int64_t)p.t_row0 + i;
-    atomicAdd(&cells[(int64_t)blockIdx.y * cells_per_pair + cell_index(p, tgt[row * 3 + 0], tgt[row * 3 + 1], tgt[row * 3 + 2])], 1);
-}
-
-// grid n_pairs, block 1024: in-place exclusive scan of the pair's nx * ny * nz counters
-__global__ __launch_bounds__(1024) void radius_scan_kernel(const RadPlan* __restrict__ plan, int64_t cells_per_pair,
-                                                          int32_t* __restrict__ cells) {
-    __shared__ int32_t part[1024];
-    const RadPlan& p = plan[blockIdx.x];
-    const int t = threadIdx.x;
-    int32_t* c = cells + (int64_t)blockIdx.x * cells_per_pair;
-    const int n = p.n[0] * p.n[1] * p.n[2], chunk = (n + 1023) / 1024;
-    const int b = min(n, t * chunk), e = min(n, b + chunk);
-    int32_t s = 0;
-    for (int i = b; i < e; ++i) s += c[i];
-    part[t] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int32_t v = t >= off ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int32_t run = part[t] - s;
-    for (int i = b; i < e; ++i) {
-        const int32_t v = c[i];
-        c[i] = run;
-        run += v;
-    }
-}
-
-// grid (ceil(max_t_len / 256), n_pairs): afterwards cells[c] = end of cell c
-__global__ __launch_bounds__(256) void radius_scatter_kernel(const float* __restrict__ tgt, const RadPlan* __restrict__ plan,
-                                                            int64_t cells_per_pair, int32_t* __restrict__ cells,
-                                                            f32x4* __restrict__ recs) {
-    const RadPlan& p = plan[blockIdx.y];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= p.t_len) return;
-    const int64_t row = (int64_t)p.t_row0 + i;
-    const float x = tgt[row * 3 + 0], y = tgt[row * 3 + 1], z = tgt[row * 3 + 2];
-    const int pos = atomicAdd(&cells[(int64_t)blockIdx.y * cells_per_pair + cell_index(p, x, y, z)], 1);
-    if (pos >= 0 && pos < p.t_len) {  // always, for counters that match the rows
-        f32x4 r = {x, y, z, __int_as_float(i)};
-        recs[(int64_t)p.t_row0 + pos] = r;
-    }
 }
 
 // ---- the query side: everything the count launch and the fill launch share
@@ -244,13 +66,13 @@ struct Query {
 __device__ __forceinline__ bool make_query(const RadPlan& p, const float* __restrict__ src, const double* __restrict__ T,
                                            const int32_t* __restrict__ cells, const f32x4* __restrict__ recs, double R, int i,
                                            int* lds, Query& q) {
-    if (i >= p.s_len) return false;
-    const int64_t row = (int64_t)p.s_row0 + i;
+    if (i >= p.q_len) return false;
+    const int64_t row = (int64_t)p.q_row0 + i;
     const double x0 = (double)src[row * 3 + 0], x1 = (double)src[row * 3 + 1], x2 = (double)src[row * 3 + 2];
     const double* M = T + (int64_t)blockIdx.y * 16;
 #pragma unroll
     for (int k = 0; k < 3; ++k) q.a[k] = ((M[k * 4 + 0] * x0 + M[k * 4 + 1] * x1) + M[k * 4 + 2] * x2) + M[k * 4 + 3];
-    q.rec = recs + p.t_row0;
+    q.rec = recs + p.b_row0;
     q.run = lds + threadIdx.x;
     int c0[3], c1[3];
 #pragma unroll
@@ -268,7 +90,7 @@ __device__ __forceinline__ bool make_query(const RadPlan& p, const float* __rest
         const int first = base + c0[0], last = base + c1[0];
         const int b = first > 0 ? cells[first - 1] : 0, e = cells[last];
         jb[r] = in ? max(b, 0) : 0;
-        je[r] = in ? min(e, p.t_len) : 0;
+        je[r] = in ? min(e, p.b_len) : 0;
     }
 #pragma unroll
     for (int r = 0; r < 9; ++r) {
@@ -317,7 +139,7 @@ __global__ __launch_bounds__(RAD_BLOCK) void radius_count_kernel(const float* __
     const double R2 = R * R;
     int32_t n = 0;
     for_each_candidate(q, [&](double d2, int) { n += d2 < R2 ? 1 : 0; });
-    count[(int64_t)p.s_row0 + i] = n;
+    count[(int64_t)p.q_row0 + i] = n;
 }
 
 // grid (ceil(max_s_len / 256), n_pairs)
@@ -332,7 +154,7 @@ __global__ __launch_bounds__(RAD_BLOCK) void radius_fill_kernel(const float* __r
     Query q;
     if (!make_query(p, src, T, cells + (int64_t)blockIdx.y * cells_per_pair, recs, R, i, lds, q)) return;
     const double R2 = R * R;
-    const int64_t row = (int64_t)p.s_row0 + i;
+    const int64_t row = (int64_t)p.q_row0 + i;
     // what the caller reserved for this row, inside what it reserved in all: no store leaves pair_j whatever offset[] holds
     const int64_t total = offset[s_rows], o0 = offset[row], o1 = offset[row + 1];
     if (!(o0 >= 0 && o0 <= o1 && o1 <= total)) return;
@@ -347,9 +169,6 @@ __global__ __launch_bounds__(RAD_BLOCK) void radius_fill_kernel(const float* __r
     });
 }
 
-inline unsigned row_blocks(int32_t max_len) { return (unsigned)(((int64_t)max_len + 255) / 256); }
-inline bool rows_ok(int64_t rows, int32_t max_len) { return rows >= 0 && rows <= INT32_MAX && max_len >= 0 && max_len <= rows; }
-
 // everything both entry points refuse, decided before any launch
 inline int check_call(const void* src, const int32_t* s_row0, const int32_t* s_len, int32_t max_s_len, int64_t s_rows, const void* tgt,
                       const int32_t* t_row0, const int32_t* t_len, int32_t max_t_len, int64_t t_rows, const double* T, int32_t n_pairs,
@@ -359,7 +178,7 @@ inline int check_call(const void* src, const int32_t* s_row0, const int32_t* s_l
     if (n_pairs == 0) return 1;  // nothing to do
     SCREAM_REQUIRE(n_pairs <= 65535, SCREAM_EUNSUPPORTED);
     SCREAM_REQUIRE(src && s_row0 && s_len && tgt && t_row0 && t_len && T && out && workspace, SCREAM_EINVAL);
-    SCREAM_REQUIRE(workspace_bytes_given >= workspace_bytes(t_rows, n_pairs, max_t_len), SCREAM_EINVAL);
+    SCREAM_REQUIRE(workspace_bytes_given >= grid_carve<3>(nullptr, t_rows, n_pairs, grid_side(max_t_len)).bytes, SCREAM_EINVAL);
     SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, SCREAM_EINVAL);
     return 0;
 }
@@ -368,7 +187,7 @@ inline int check_call(const void* src, const int32_t* s_row0, const int32_t* s_l
 
 extern "C" int64_t scream_radius_workspace_bytes(int64_t tgt_rows_total, int32_t n_pairs, int32_t max_t_len) {
     if (n_pairs < 0 || !rows_ok(tgt_rows_total, max_t_len)) return SCREAM_EINVAL;
-    return workspace_bytes(tgt_rows_total, n_pairs, max_t_len);
+    return grid_carve<3>(nullptr, tgt_rows_total, n_pairs, grid_side(max_t_len)).bytes;
 }
 
 extern "C" int scream_radius_count(const float* src, const int32_t* s_row0, const int32_t* s_len, int32_t max_s_len,
@@ -378,26 +197,14 @@ extern "C" int scream_radius_count(const float* src, const int32_t* s_row0, cons
     const int rc = check_call(src, s_row0, s_len, max_s_len, src_rows_total, tgt, t_row0, t_len, max_t_len, tgt_rows_total, T, n_pairs,
                               radius, count, workspace, workspace_bytes_given);
     if (rc != 0) return rc < 0 ? rc : 0;
-    const Carve cv = carve(workspace, tgt_rows_total, n_pairs, max_t_len);
     const int side = grid_side(max_t_len);
-    const int64_t cpp = (int64_t)side * side * side;
+    const GridWs<3> ws = grid_carve<3>(workspace, tgt_rows_total, n_pairs, side);
     hipStream_t st = as_stream(stream);
-    const hipError_t e = hipMemsetAsync(cv.cells, 0, (size_t)cv.cell_bytes, st);
-    if (e != hipSuccess) return (int)e;
-    radius_plan_kernel<<<dim3(n_pairs), dim3(256), 0, st>>>(tgt, s_row0, s_len, t_row0, t_len, max_s_len, max_t_len, src_rows_total,
-                                                             tgt_rows_total, radius, side, cv.plan);
-    SCREAM_LAUNCH_CHECK();
-    if (max_t_len > 0) {
-        const dim3 per_row(row_blocks(max_t_len), n_pairs);
-        radius_cell_count_kernel<<<per_row, dim3(256), 0, st>>>(tgt, cv.plan, cpp, cv.cells);
-        SCREAM_LAUNCH_CHECK();
-        radius_scan_kernel<<<dim3(n_pairs), dim3(1024), 0, st>>>(cv.plan, cpp, cv.cells);
-        SCREAM_LAUNCH_CHECK();
-        radius_scatter_kernel<<<per_row, dim3(256), 0, st>>>(tgt, cv.plan, cpp, cv.cells, cv.recs);
-        SCREAM_LAUNCH_CHECK();
-    }
+    const int grid_rc = cell_grid_enqueue<3>(tgt, t_row0, t_len, max_t_len, tgt_rows_total, s_row0, s_len, max_s_len, src_rows_total, n_pairs,
+                                             radius, RAD_EDGE_SLACK, side, ws, st);
+    if (grid_rc != 0) return grid_rc;
     if (max_s_len > 0) {
-        radius_count_kernel<<<dim3(row_blocks(max_s_len), n_pairs), dim3(RAD_BLOCK), 0, st>>>(src, T, cv.plan, cpp, cv.cells, cv.recs,
+        radius_count_kernel<<<dim3(row_blocks(max_s_len), n_pairs), dim3(RAD_BLOCK), 0, st>>>(src, T, ws.plan, ws.cells_per_pair, ws.cells, ws.recs,
                                                                                                radius, count);
         SCREAM_LAUNCH_CHECK();
     }
@@ -414,10 +221,9 @@ extern "C" int scream_radius_pairs(const float* src, const int32_t* s_row0, cons
     if (rc != 0) return rc < 0 ? rc : 0;
     SCREAM_REQUIRE(offset, SCREAM_EINVAL);
     if (max_s_len == 0) return 0;
-    const Carve cv = carve(workspace, tgt_rows_total, n_pairs, max_t_len);
-    const int side = grid_side(max_t_len);
+    const GridWs<3> ws = grid_carve<3>(workspace, tgt_rows_total, n_pairs, grid_side(max_t_len));
     radius_fill_kernel<<<dim3(row_blocks(max_s_len), n_pairs), dim3(RAD_BLOCK), 0, as_stream(stream)>>>(
-        src, T, cv.plan, (int64_t)side * side * side, cv.cells, cv.recs, radius, K, offset, src_rows_total, pair_j);
+        src, T, ws.plan, ws.cells_per_pair, ws.cells, ws.recs, radius, K, offset, src_rows_total, pair_j);
     SCREAM_LAUNCH_CHECK();
     return 0;
 }

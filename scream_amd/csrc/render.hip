@@ -314,7 +314,6 @@ __global__ __launch_bounds__(256) void render_bwd_reduce_kernel(const float* __r
     dsrc[row * 3 + 2] = c;
 }
 
-int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
 int64_t range_bytes(int32_t n_pairs, int32_t V) { return align256((int64_t)n_pairs * V * 2 * 4); }
 int64_t key_bytes(int32_t n_pairs, int32_t V, int32_t w) { return (int64_t)n_pairs * V * 2 * w * w * 8; }
 int64_t partial_bytes(int32_t V, int64_t src_rows_total) { return (int64_t)V * src_rows_total * 3 * 4; }

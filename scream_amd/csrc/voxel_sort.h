@@ -38,24 +38,22 @@ struct Carve {
     int32_t* heads;    // per block
 };
 
-inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
 inline int64_t blocks_cap(int64_t rows, int32_t n_clouds) { return rows / VX_TILE + n_clouds + 1; }
 inline int64_t workspace_bytes(int64_t rows, int32_t n_clouds) {
     return align256((int64_t)n_clouds * (int64_t)sizeof(CloudPlan)) + 2 * align256(rows * 8) + 3 * align256(rows * 4) +
            align256(blocks_cap(rows, n_clouds) * 256 * 4) + align256(blocks_cap(rows, n_clouds) * 4);
 }
 inline Carve carve(void* workspace, int64_t rows, int32_t n_clouds) {
-    char* w = reinterpret_cast<char*>(workspace);
-    auto take = [&](int64_t bytes) { char* r = w; w += align256(bytes); return r; };
+    Carver w{workspace};
     Carve c;
-    c.plan = reinterpret_cast<CloudPlan*>(take((int64_t)n_clouds * (int64_t)sizeof(CloudPlan)));
-    c.keys[0] = reinterpret_cast<uint64_t*>(take(rows * 8));
-    c.keys[1] = reinterpret_cast<uint64_t*>(take(rows * 8));
-    c.rows[0] = reinterpret_cast<int32_t*>(take(rows * 4));
-    c.rows[1] = reinterpret_cast<int32_t*>(take(rows * 4));
-    c.start = reinterpret_cast<int32_t*>(take(rows * 4));
-    c.counts = reinterpret_cast<uint32_t*>(take(blocks_cap(rows, n_clouds) * 256 * 4));
-    c.heads = reinterpret_cast<int32_t*>(take(blocks_cap(rows, n_clouds) * 4));
+    c.plan = w.take<CloudPlan>(n_clouds);
+    c.keys[0] = w.take<uint64_t>(rows);
+    c.keys[1] = w.take<uint64_t>(rows);
+    c.rows[0] = w.take<int32_t>(rows);
+    c.rows[1] = w.take<int32_t>(rows);
+    c.start = w.take<int32_t>(rows);
+    c.counts = w.take<uint32_t>(blocks_cap(rows, n_clouds) * 256);
+    c.heads = w.take<int32_t>(blocks_cap(rows, n_clouds));
     return c;
 }
 

@@ -18,34 +18,10 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .clouds import PackedPairs, check_clouds, check_radius
 from .voxel import voxel_down_sample_batch
 
 __all__ = ["extract_dsm", "extract_dsm_batch", "make_dsm_dem", "make_dsm_dem_batch", "tile_windows", "window_mask"]
-
-
-def _check_clouds(clouds: Sequence[torch.Tensor], what: str) -> None:
-    for i, c in enumerate(clouds):
-        if not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] != 3:
-            raise _lib.ScreamHipError("%s %d: expected a [N,3] tensor, got %s" % (what, i, tuple(getattr(c, "shape", ()))))
-        if not c.is_cuda:
-            raise _lib.ScreamHipError("extract_dsm needs tensors on the MI355X (%s %d is on %s); there is no CPU path" % (what, i, c.device))
-        if c.dtype != torch.float32:
-            raise _lib.ScreamHipError("%s %d: expected torch.float32, got %s" % (what, i, c.dtype))
-
-
-def _pack(clouds: Sequence[torch.Tensor]) -> Tuple[torch.Tensor, List[int], List[int]]:
-    lens = [int(c.shape[0]) for c in clouds]
-    row0 = [0] * len(clouds)
-    for i in range(1, len(clouds)):
-        row0[i] = row0[i - 1] + lens[i - 1]
-    return torch.cat([c.detach() for c in clouds], dim=0).contiguous(), row0, lens
-
-
-def _check_radius(radius: float) -> float:
-    radius = float(radius)
-    if not radius > 0 or radius == float("inf"):
-        raise _lib.ScreamHipError("extract_dsm: the radius must be a positive finite number, got %r" % radius)
-    return radius
 
 
 def extract_dsm_batch(patches: Sequence[torch.Tensor], dems: Sequence[torch.Tensor], radius: float = 0.8, return_index: bool = False):
@@ -56,20 +32,20 @@ def extract_dsm_batch(patches: Sequence[torch.Tensor], dems: Sequence[torch.Tens
     patches, dems = list(patches), list(dems)
     if len(patches) != len(dems):
         raise _lib.ScreamHipError("%d patches for %d dems" % (len(patches), len(dems)))
-    _check_clouds(patches, "patch")
-    _check_clouds(dems, "dem")
-    radius = _check_radius(radius)
+    check_clouds(patches, "patch", op="extract_dsm")
+    check_clouds(dems, "dem", op="extract_dsm")
+    radius = check_radius(radius, "extract_dsm: the radius")
     if not patches:
         return ([], []) if return_index else []
-    dev = dems[0].device
-    patch, p_row0, p_len = _pack(patches)
-    dem, d_row0, d_len = _pack(dems)
-    meta = torch.tensor([p_row0, p_len, d_row0, d_len], dtype=torch.int32).to(dev)
-    out, idx = ops.dsm_extract_packed(patch, meta[0], meta[1], max(p_len), dem, meta[2], meta[3], max(d_len), radius)
-    pts = [out[r:r + n].clone() for r, n in zip(d_row0, d_len)]
-    if not return_index:
-        return pts
-    return pts, [idx[r:r + n].clone() for r, n in zip(d_row0, d_len)]
+    pk = PackedPairs(patches, dems, dems[0].device)
+    out, idx = _extract(pk, radius)
+    return (pk.split_tgt(out), pk.split_tgt(idx)) if return_index else pk.split_tgt(out)
+
+
+def _extract(pk: PackedPairs, radius: float):
+    """The packed call: the patches are the pairs' sources, the dems their targets."""
+    m = pk.meta
+    return ops.dsm_extract_packed(pk.src, m[0], m[1], pk.max_s_len, pk.tgt, m[2], m[3], pk.max_t_len, radius)
 
 
 def extract_dsm(patch: torch.Tensor, dem: torch.Tensor, radius: float = 0.8, return_index: bool = False):
@@ -102,7 +78,7 @@ def make_dsm_dem_batch(patches_raw: Sequence, classes: Sequence, resolution: flo
     patches_raw, classes = list(patches_raw), list(classes)
     if len(patches_raw) != len(classes):
         raise _lib.ScreamHipError("%d windows for %d class arrays" % (len(patches_raw), len(classes)))
-    radius = _check_radius(radius)
+    radius = check_radius(radius, "make_dsm_dem: the radius")
     B = len(patches_raw)
     if B == 0:
         return [], []
@@ -115,13 +91,10 @@ def make_dsm_dem_batch(patches_raw: Sequence, classes: Sequence, resolution: flo
             raise _lib.ScreamHipError("expected xyz [N,3] and class [N], got %s and %s" % (tuple(w.shape), tuple(c.shape)))
         clouds.append((w, w[c == ground_class]))
     down = voxel_down_sample_batch([w for w, _ in clouds] + [g for _, g in clouds], float(resolution))
-    patches, dems = down[:B], down[B:]
-    patch, p_row0, p_len = _pack(patches)
-    dem, row0, lens = _pack(dems)
-    meta = torch.tensor([p_row0, p_len, row0, lens], dtype=torch.int32).to(dev)
-    dsm, _ = ops.dsm_extract_packed(patch, meta[0], meta[1], max(p_len), dem, meta[2], meta[3], max(lens), radius)
-    out, centre = ops.dsm_dem_assemble_packed(dsm, dem, meta[2], meta[3], max(lens))
-    return [out[r:r + n].clone() for r, n in zip(row0, lens)], [centre[i:i + 1].clone() for i in range(B)]
+    pk = PackedPairs(down[:B], down[B:], dev)
+    dsm, _ = _extract(pk, radius)
+    out, centre = ops.dsm_dem_assemble_packed(dsm, pk.tgt, pk.meta[2], pk.meta[3], pk.max_t_len)
+    return pk.split_tgt(out), [centre[i:i + 1].clone() for i in range(B)]
 
 
 def make_dsm_dem(patch_raw, cls, resolution: float = 1.0, radius: float = 0.8, ground_class: int = 1,

@@ -38,6 +38,15 @@ def _p(t: Optional[torch.Tensor], dtype=torch.float32) -> Optional[int]:
     return t.data_ptr()
 
 
+def _workspace(lib_fn, name: str, *args, device, floor: int = 16) -> torch.Tensor:
+    """Scratch for one call: the uint8 tensor of the size that the library's own `*_workspace_bytes(*args)` asks for (at least
+    `floor` bytes, so that it always has an address); a negative size is the library refusing the arguments."""
+    need = lib_fn(*args)
+    if need < 0:
+        raise _lib.ScreamHipError("%s(%s): invalid argument" % (name, ", ".join(str(a) for a in args)))
+    return torch.empty(max(need, floor), device=device, dtype=torch.uint8)
+
+
 def gemm_f32(A: torch.Tensor, W: torch.Tensor, epilogue: int = EPI_NONE, n_act: int = 0,
              bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
              gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
@@ -354,10 +363,8 @@ def nn_search(query: torch.Tensor, ref: torch.Tensor, q_row0, q_len, r_row0, r_l
 
 def render_workspace(n_pairs: int, n_views: int, w: int, src_rows_total: int, device) -> torch.Tensor:
     """Scratch of render_depth; render_depth_bwd needs the forward's, untouched (it begins with the depth ranges)."""
-    need = _lib.load().scream_render_workspace_bytes(n_pairs, n_views, w, src_rows_total)
-    if need < 0:
-        raise _lib.ScreamHipError("scream_render_workspace_bytes(%d, %d, %d, %d): invalid argument" % (n_pairs, n_views, w, src_rows_total))
-    return torch.empty(max(need, 16), device=device, dtype=torch.uint8)
+    return _workspace(_lib.load().scream_render_workspace_bytes, "scream_render_workspace_bytes", n_pairs, n_views, w, src_rows_total,
+                      device=device)
 
 
 def render_depth(src: torch.Tensor, s_row0, s_len, tgt: torch.Tensor, t_row0, t_len, max_s_len: int, max_t_len: int,
@@ -396,10 +403,7 @@ def voxel_down_sample_packed(xyz: torch.Tensor, row0: torch.Tensor, length: torc
     Returns (out_xyz [rows,3], out_len int32 [B], out_count int32 [rows] or None), all on the device: cloud c's voxels are rows
     row0[c] .. + out_len[c] of out_xyz (the rows behind are not written), out_len[c] = -1 for a refused cloud.  No host sync."""
     n_clouds, rows, dev = row0.shape[0], xyz.shape[0], xyz.device
-    need = _lib.load().scream_voxel_workspace_bytes(rows, n_clouds)
-    if need < 0:
-        raise _lib.ScreamHipError("scream_voxel_workspace_bytes(%d, %d): invalid argument" % (rows, n_clouds))
-    workspace = torch.empty(max(need, 16), device=dev, dtype=torch.uint8)
+    workspace = _workspace(_lib.load().scream_voxel_workspace_bytes, "scream_voxel_workspace_bytes", rows, n_clouds, device=dev)
     out_xyz = torch.empty(max(rows, 1), 3, device=dev, dtype=torch.float32)
     out_len = torch.empty(max(n_clouds, 1), device=dev, dtype=torch.int32)
     out_count = torch.empty(max(rows, 1), device=dev, dtype=torch.int32) if want_counts else None
@@ -417,10 +421,7 @@ def dsm_extract_packed(patch: torch.Tensor, p_row0: torch.Tensor, p_len: torch.T
     (out_xyz [D,3], out_idx int32 [D]) on the device; rows of dem outside every cloud are not written.  No host sync."""
     n_clouds, P, D, dev = p_row0.shape[0], patch.shape[0], dem.shape[0], dem.device
     lib = _lib.load()
-    need = lib.scream_dsm_workspace_bytes(P, n_clouds, int(max_p_len))
-    if need < 0:
-        raise _lib.ScreamHipError("scream_dsm_workspace_bytes(%d, %d, %d): invalid argument" % (P, n_clouds, max_p_len))
-    workspace = torch.empty(max(need, 16), device=dev, dtype=torch.uint8)
+    workspace = _workspace(lib.scream_dsm_workspace_bytes, "scream_dsm_workspace_bytes", P, n_clouds, int(max_p_len), device=dev)
     out_xyz = torch.empty(max(D, 1), 3, device=dev, dtype=torch.float32)
     out_idx = torch.empty(max(D, 1), device=dev, dtype=torch.int32)
     patch_p = _p(patch) if P else _p(workspace, torch.uint8)  # a batch of empty windows: nothing is read through it
@@ -462,10 +463,7 @@ def radius_count_packed(src: torch.Tensor, s_row0: torch.Tensor, s_len: torch.Te
     (0 for rows outside every pair); the workspace holds the targets' cell lists for radius_pairs_packed.  No host sync."""
     n_pairs, S, N, dev = s_row0.shape[0], src.shape[0], tgt.shape[0], src.device
     lib = _lib.load()
-    need = lib.scream_radius_workspace_bytes(N, n_pairs, int(max_t_len))
-    if need < 0:
-        raise _lib.ScreamHipError("scream_radius_workspace_bytes(%d, %d, %d): invalid argument" % (N, n_pairs, max_t_len))
-    workspace = torch.empty(max(need, 16), device=dev, dtype=torch.uint8)
+    workspace = _workspace(lib.scream_radius_workspace_bytes, "scream_radius_workspace_bytes", N, n_pairs, int(max_t_len), device=dev)
     count = torch.zeros(max(S, 1), device=dev, dtype=torch.int32)
     args = _radius_args(src, s_row0, s_len, max_s_len, tgt, t_row0, t_len, max_t_len, T, radius, count.data_ptr())
     check(lib.scream_radius_count(*args, _p(count, torch.int32), _p(workspace, torch.uint8), workspace.numel(), _stream()),
@@ -504,10 +502,7 @@ def prep_pairs_packed(raw: torch.Tensor, raw_row0: torch.Tensor, raw_len: torch.
             perturb.numel() != 16 * B or sample_id.shape[0] != B:
         raise _lib.ScreamHipError("prep_pairs_packed: the per-pair arrays do not describe %d pairs" % B)
     lib = _lib.load()
-    need = lib.scream_prep_pairs_workspace_bytes(rows, B, int(max_len))
-    if need < 0:
-        raise _lib.ScreamHipError("scream_prep_pairs_workspace_bytes(%d, %d, %d): invalid argument" % (rows, B, max_len))
-    workspace = torch.empty(max(need, 16), device=dev, dtype=torch.uint8)
+    workspace = _workspace(lib.scream_prep_pairs_workspace_bytes, "scream_prep_pairs_workspace_bytes", rows, B, int(max_len), device=dev)
     xyz = torch.empty(int(rows_total), 3, device=dev, dtype=torch.float32)
     center = torch.empty(2 * B, 3, device=dev, dtype=torch.float32)
     rot = torch.empty(B, 3, 3, device=dev, dtype=torch.float32)
@@ -543,7 +538,7 @@ def l1_pairs_fwd(pred: torch.Tensor, xyz: Optional[torch.Tensor], rot: Optional[
     """scream_l1_pairs_fwd: (loss fp32 scalar, loss_pair float64 [B]) of the packed prediction [rows_src,3] against rot / trans
     applied to the packed xyz, or against the packed `target` [rows_src,3] when it is given.  No host sync."""
     lib, dev = _lib.load(), pred.device
-    workspace = torch.empty(max(lib.scream_l1_pairs_workspace_bytes(int(n_pairs), int(max_len)), 16), device=dev, dtype=torch.uint8)
+    workspace = _workspace(lib.scream_l1_pairs_workspace_bytes, "scream_l1_pairs_workspace_bytes", int(n_pairs), int(max_len), device=dev)
     loss_pair = torch.empty(n_pairs, device=dev, dtype=torch.float64)
     loss = torch.empty((), device=dev, dtype=torch.float32)
     check(lib.scream_l1_pairs_fwd(*_l1_args(pred, xyz, rot, trans, target, cloud_row0, cloud_len, n_pairs, max_len),
@@ -610,61 +605,99 @@ def icp_p2p(src, ref, src_row0, src_len, ref_row0, ref_len, s, c, T_init, max_sr
     T = T_init.detach().clone().contiguous().float()
     fr = torch.empty(n_pairs, 2, device=dev, dtype=torch.float32)
     iters = torch.empty(n_pairs, device=dev, dtype=torch.int32)
-    need = lib.scream_icp_workspace_bytes(src.shape[0], ref.shape[0], n_pairs)
-    ws = torch.empty(need, device=dev, dtype=torch.uint8)
+    ws = _icp_workspace(lib, src, ref, n_pairs)
     check(lib.scream_icp_p2p(_p(src), _p(ref), _p(src_row0, torch.int32), _p(src_len, torch.int32),
                              _p(ref_row0, torch.int32), _p(ref_len, torch.int32), _p(s), _p(c), n_pairs, max_src_len,
                              max_ref_len, src.shape[0], ref.shape[0], float(max_corr_dist), int(max_iter),
                              float(rel_fitness), float(rel_rmse), _p(T), _p(fr), _p(iters, torch.int32),
-                             ws.data_ptr(), need, _stream()), "scream_icp_p2p")
+                             ws.data_ptr(), ws.numel(), _stream()), "scream_icp_p2p")
     return T, fr, iters
+
+
+def _icp_workspace(lib, src, ref, n_pairs: int) -> torch.Tensor:
+    return _workspace(lib.scream_icp_workspace_bytes, "scream_icp_workspace_bytes", src.shape[0], ref.shape[0], n_pairs, device=src.device)
+
+
+def icp_raw_workspace(src_rows: int, tgt_rows: int, n_pairs: int, device) -> torch.Tensor:
+    """Scratch of scream_icp_raw_range / scream_icp_raw_nn (scream_amd/rawicp.py)."""
+    return _workspace(_lib.load().scream_icp_raw_workspace_bytes, "scream_icp_raw_workspace_bytes", src_rows, tgt_rows, n_pairs,
+                      device=device, floor=256)
 
 
 ICP_ASYNC_ITERS = 64  # schedules up to this many iterations are enqueued whole (icp_p2p); longer ones in pieces (IcpRun)
 
 
-class IcpRun:
-    """A LONG ICP schedule (KITTI: up to 1000 iterations, evaluate_kitti.py:64-70) enqueued in pieces, so that launching stops
-    once every pair has stopped WITHOUT the host ever waiting inside the C ABI (scream_icp_p2p_range): ``advance(n)`` enqueues the
-    next n launches on the current stream and, behind them, a copy of the per-pair stopped flags into pinned memory + an event;
-    ``all_stopped()`` waits for THAT event only (the caller calls it when it collects the batch, i.e. after the following batches
-    were enqueued) and reads the flags.  ``T`` holds the refined transform of every pair whose flag is set; ``finish()`` enqueues
-    what is left of the schedule.  Results are those of icp_p2p whatever the piece sizes (tests/test_gpu_evaluate.py)."""
+class PiecewiseRun:
+    """A LONG schedule of per-pair steps enqueued in pieces, so that launching stops once every pair has stopped WITHOUT the host
+    ever waiting inside the C ABI: ``advance(k)`` enqueues the next k steps on the current stream (the subclass's ``_enqueue(begin,
+    end)``, one C call) and, behind them, a copy of the per-pair stopped flags into pinned memory + an event; ``all_stopped()``
+    waits for THAT event only, not for the stream's later work, and reads the flags.  A pair's result does not depend on the piece
+    sizes (tests/test_gpu_evaluate.py, tests/test_gpu_rawicp.py)."""
+
+    def __init__(self, n: int, steps: int, dev, skip_empty: bool = False):
+        """n pairs, `steps` steps at most; skip_empty: a run of no pairs enqueues nothing (else the library sees n = 0)."""
+        self.n, self.steps, self.next_it = n, steps, 0
+        self._dev, self._skip = dev, skip_empty and n == 0
+        self.flags = torch.zeros(max(n, 1), device=dev, dtype=torch.int32)[:n]
+        self.flags_host = torch.zeros(max(n, 1), dtype=torch.int32, pin_memory=True)[:n]
+        self.event = None
+
+    @property
+    def steps_left(self) -> int:
+        return self.steps - self.next_it
+
+    def advance(self, k: int) -> None:
+        end = min(self.next_it + int(k), self.steps)
+        if self._skip:
+            self.next_it = self.steps
+            return
+        self._enqueue(self.next_it, end)
+        self.next_it = end
+        self.flags_host.copy_(self.flags, non_blocking=True)
+        self.event = torch.cuda.Event()
+        self.event.record(torch.cuda.current_stream(self._dev))
+
+    def all_stopped(self) -> bool:
+        if self._skip:
+            return True
+        self.event.synchronize()
+        return self.steps_left == 0 or bool(self.flags_host.all())
+
+    def run(self, piece: int = 32):
+        """Enqueue pieces until every pair has stopped: after each piece the host waits for that piece's flags (its event, not the
+        stream) and enqueues the next one only if a pair still runs, so no more than ceil(steps taken / piece) pieces are launched."""
+        if piece < 1:
+            raise ValueError("piece must be at least 1")
+        self.advance(piece)
+        while not self.all_stopped():
+            self.advance(piece)
+        return self
+
+
+class IcpRun(PiecewiseRun):
+    """scream_icp_p2p_range in pieces (KITTI: up to 1000 iterations, evaluate_kitti.py:64-70): a step is one launch, max_iter + 2 of
+    them.  The caller calls ``all_stopped()`` when it collects the batch, i.e. after the following batches were enqueued.  ``T``
+    holds the refined transform of every pair whose flag is set.  Results are those of icp_p2p whatever the piece sizes."""
 
     def __init__(self, src, ref, src_row0, src_len, ref_row0, ref_len, s, c, T_init, max_src_len: int, max_ref_len: int,
                  max_corr_dist: float, max_iter: int, rel_fitness: float = 1e-6, rel_rmse: float = 1e-6):
         self.lib = _lib.load()
         n = s.shape[0]
         dev = src.device
-        self.n, self.max_iter, self.next_it = n, int(max_iter), 0
+        self.max_iter = int(max_iter)
+        super().__init__(n, self.max_iter + 2, dev)
         self.T = T_init.detach().clone().contiguous().float()
         self.fr = torch.empty(n, 2, device=dev, dtype=torch.float32)
         self.iters = torch.empty(n, device=dev, dtype=torch.int32)
-        self.flags = torch.zeros(n, device=dev, dtype=torch.int32)
-        self.flags_host = torch.zeros(n, dtype=torch.int32, pin_memory=True)
-        need = self.lib.scream_icp_workspace_bytes(src.shape[0], ref.shape[0], n)
-        self.ws = torch.empty(need, device=dev, dtype=torch.uint8)
+        self.ws = _icp_workspace(self.lib, src, ref, n)
         self._keep = (src, ref, src_row0, src_len, ref_row0, ref_len, s, c)
         self._args = (_p(src), _p(ref), _p(src_row0, torch.int32), _p(src_len, torch.int32), _p(ref_row0, torch.int32),
                       _p(ref_len, torch.int32), _p(s), _p(c), n, int(max_src_len), int(max_ref_len), src.shape[0], ref.shape[0],
                       float(max_corr_dist), int(max_iter), float(rel_fitness), float(rel_rmse), _p(self.T), _p(self.fr),
                       _p(self.iters, torch.int32))
-        self.event = None
 
-    @property
-    def launches_left(self) -> int:
-        return self.max_iter + 2 - self.next_it
+    launches_left = PiecewiseRun.steps_left
 
-    def advance(self, n_launches: int) -> None:
-        end = min(self.next_it + int(n_launches), self.max_iter + 2)
-        check(self.lib.scream_icp_p2p_range(*self._args, self.next_it, end, _p(self.flags, torch.int32), self.ws.data_ptr(),
-                                            self.ws.numel(), _stream()), "scream_icp_p2p_range")
-        self.next_it = end
-        self.flags_host.copy_(self.flags, non_blocking=True)
-        self.event = torch.cuda.Event()
-        self.event.record(torch.cuda.current_stream(self.T.device))
-
-    def all_stopped(self) -> bool:
-        """Waits for the flags of the last advance() (not for the stream's later work) and reads them."""
-        self.event.synchronize()
-        return self.launches_left == 0 or bool(self.flags_host.all())
+    def _enqueue(self, begin: int, end: int) -> None:
+        check(self.lib.scream_icp_p2p_range(*self._args, begin, end, _p(self.flags, torch.int32), self.ws.data_ptr(), self.ws.numel(),
+                                            _stream()), "scream_icp_p2p_range")

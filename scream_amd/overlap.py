@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .dsm import _pack
+from .clouds import PackedPairs, check_clouds, check_radius, pose_stack
 from .voxel import voxel_down_sample_batch
 
 __all__ = ["radius_count_batch", "radius_pairs_batch", "overlap_batch", "prepare_3dmatch_batch", "select_outputs",
@@ -32,76 +32,43 @@ SETS = {"train": "3DMatch_train", "val": "3DMatch_val", "test_3dmatch": "3DMatch
 ZERO_SET = "3DZeroMatch_test"
 
 
-def _check_clouds(clouds: Sequence[torch.Tensor], what: str) -> None:
-    for i, c in enumerate(clouds):
-        if not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] != 3:
-            raise _lib.ScreamHipError("%s %d: expected a [N,3] tensor, got %s" % (what, i, tuple(getattr(c, "shape", ()))))
-        if not c.is_cuda:
-            raise _lib.ScreamHipError("the radius search needs tensors on the MI355X (%s %d is on %s); there is no CPU path" % (what, i, c.device))
-        if c.dtype != torch.float32:
-            raise _lib.ScreamHipError("%s %d: expected torch.float32, got %s" % (what, i, c.dtype))
-
-
-def _check_radius(radius: float) -> float:
-    radius = float(radius)
-    if not radius > 0 or radius == float("inf"):
-        raise _lib.ScreamHipError("the radius must be a positive finite number, got %r" % radius)
-    return radius
-
-
-def _transforms(Ts, n: int, dev) -> torch.Tensor:
-    """A sequence of 4x4 transforms (numpy or tensors; taken as float64, nothing is rounded) -> float64 [n,4,4] on the device."""
-    mats = []
-    for i, T in enumerate(Ts):
-        m = T.detach().cpu().numpy() if isinstance(T, torch.Tensor) else np.asarray(T)
-        if m.shape != (4, 4):
-            raise _lib.ScreamHipError("transform %d: expected a 4x4 matrix, got %s" % (i, m.shape))
-        mats.append(m.astype(np.float64))
-    if len(mats) != n:
-        raise _lib.ScreamHipError("%d transforms for %d pairs" % (len(mats), n))
-    return torch.from_numpy(np.stack(mats, axis=0)).to(dev).contiguous()
-
-
-class _Packed:
-    """The clouds of a call packed back to back, as the C ABI reads them."""
+class _RadiusCall(PackedPairs):
+    """A call's checked clouds packed, with its transforms and radius, as scream_radius_count / _pairs read them."""
 
     def __init__(self, srcs, tgts, Ts, radius):
-        self.srcs, self.tgts = list(srcs), list(tgts)
-        if len(self.srcs) != len(self.tgts):
-            raise _lib.ScreamHipError("%d sources for %d targets" % (len(self.srcs), len(self.tgts)))
-        _check_clouds(self.srcs, "source")
-        _check_clouds(self.tgts, "target")
-        self.radius = _check_radius(radius)
-        self.B = len(self.srcs)
-        self.dev = self.srcs[0].device if self.B else None
-        self.T = _transforms(Ts, self.B, self.dev) if self.B else None
+        srcs, tgts = list(srcs), list(tgts)
+        if len(srcs) != len(tgts):
+            raise _lib.ScreamHipError("%d sources for %d targets" % (len(srcs), len(tgts)))
+        check_clouds(srcs, "source", op="the radius search")
+        check_clouds(tgts, "target", op="the radius search")
+        self.radius = check_radius(radius)
+        self.B = len(srcs)
         if not self.B:
             return
-        self.src, self.s_row0, self.s_len = _pack(self.srcs)
-        self.tgt, self.t_row0, self.t_len = _pack(self.tgts)
-        self.meta = torch.tensor([self.s_row0, self.s_len, self.t_row0, self.t_len], dtype=torch.int32).to(self.dev)
+        super().__init__(srcs, tgts, srcs[0].device)
+        self.T = pose_stack(Ts, self.B, self.dev)
 
     def args(self):
         m = self.meta
-        return (self.src, m[0], m[1], max(self.s_len), self.tgt, m[2], m[3], max(self.t_len), self.T, self.radius)
+        return (self.src, m[0], m[1], self.max_s_len, self.tgt, m[2], m[3], self.max_t_len, self.T, self.radius)
 
     def count(self):
         return ops.radius_count_packed(*self.args())
 
     def bounds(self) -> torch.Tensor:
         """int64 [B + 1] on the device: the first source row of every pair, and the total."""
-        return torch.tensor(self.s_row0 + [self.s_row0[-1] + self.s_len[-1]], dtype=torch.int64).to(self.dev)
+        return torch.tensor(self.s_row0 + [self.s_rows], dtype=torch.int64).to(self.dev)
 
 
 def radius_count_batch(srcs: Sequence[torch.Tensor], tgts: Sequence[torch.Tensor], Ts, radius: float) -> List[torch.Tensor]:
     """For every pair (src [N_i,3], tgt [M_i,3]; fp32 on the GPU, N_i, M_i >= 0; T_i a float64 4x4, numpy or tensor): the int32
     [N_i] number of target points within `radius` of every transformed source point.  The pairs are packed and share every
     launch; nothing is copied back to the host."""
-    pk = _Packed(srcs, tgts, Ts, radius)
+    pk = _RadiusCall(srcs, tgts, Ts, radius)
     if not pk.B:
         return []
     count, _ = pk.count()
-    return [count[r:r + n].clone() for r, n in zip(pk.s_row0, pk.s_len)]
+    return pk.split_src(count)
 
 
 def radius_pairs_batch(srcs: Sequence[torch.Tensor], tgts: Sequence[torch.Tensor], Ts, radius: float,
@@ -109,7 +76,7 @@ def radius_pairs_batch(srcs: Sequence[torch.Tensor], tgts: Sequence[torch.Tensor
     """For every pair the int64 [n_i,2] rows (i, j): target point j lies within `radius` of transformed source point i.  Rows in
     ascending i, the neighbours of one i in ascending (d2, j) -- nearest first, equal distances to the lowest j -- and at most K
     of them (None: all).  One count launch, a prefix sum, ONE host read (the per-pair totals) and the fill launch."""
-    pk = _Packed(srcs, tgts, Ts, radius)
+    pk = _RadiusCall(srcs, tgts, Ts, radius)
     if K is not None and int(K) < 1:
         raise _lib.ScreamHipError("K must be None or at least 1, got %r" % (K,))
     if not pk.B:
@@ -144,7 +111,7 @@ def overlap_batch(srcs: Sequence[torch.Tensor], tgts: Sequence[torch.Tensor], Ts
     """(masks, n_overlap): per pair the boolean [N_i] mask of the source points that have a target point within `radius` once
     transformed -- the set ``src_overlap_ind`` of datasets/three_d_match.py:113 -- and its size as a Python int (one host copy
     per batch)."""
-    pk = _Packed(srcs, tgts, Ts, radius)
+    pk = _RadiusCall(srcs, tgts, Ts, radius)
     if not pk.B:
         return [], []
     count, _ = pk.count()
@@ -152,7 +119,7 @@ def overlap_batch(srcs: Sequence[torch.Tensor], tgts: Sequence[torch.Tensor], Ts
     run = torch.zeros(count.shape[0] + 1, device=pk.dev, dtype=torch.int64)
     torch.cumsum(mask.to(torch.int64), dim=0, out=run[1:])
     ends = run[pk.bounds()].cpu().tolist()
-    return [mask[r:r + n].clone() for r, n in zip(pk.s_row0, pk.s_len)], [ends[p + 1] - ends[p] for p in range(pk.B)]
+    return pk.split_src(mask), [ends[p + 1] - ends[p] for p in range(pk.B)]
 
 
 def _f32(a) -> np.ndarray:

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .clouds import check_clouds, pose_stack
 from .packing import PackedBatch
 
 __all__ = ["sample_perturbations", "prepare_pairs", "PreparedPairs", "prepare_3dmatch_train", "prepare_3dmatch_val",
@@ -73,18 +74,6 @@ class PreparedPairs:
     T_aug: torch.Tensor   # float64 [B,4,4]  registers the augmented metric source onto the augmented metric target
 
 
-def _matrices(M, B: int, what: str, dev) -> torch.Tensor:
-    """B 4x4 matrices (a numpy array, a sequence of arrays, or a tensor; one that is on the device already stays there) ->
-    float64 [16 B] on the device."""
-    if not isinstance(M, (torch.Tensor, np.ndarray)):
-        M = np.stack([m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m) for m in M], axis=0)
-    if tuple(M.shape) != (B, 4, 4):
-        raise _lib.ScreamHipError("%s: expected %d 4x4 matrices, got %s" % (what, B, tuple(M.shape)))
-    if isinstance(M, np.ndarray):
-        M = torch.from_numpy(np.array(M, dtype=np.float64))  # a copy: from_numpy wants a writable array
-    return M.detach().to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
-
-
 def prepare_pairs(srcs: Sequence[torch.Tensor], tgts: Sequence[torch.Tensor], T, *, mode: str, center: str, perturb=None, side=None,
                   noise_std: float = 0.0, seed: int = 0, sample_ids=None) -> PreparedPairs:
     """B raw pairs (srcs[i] [N_i,3], tgts[i] [M_i,3] on the GPU, all float32 or all float64, metric frame; T the float64 4x4
@@ -106,21 +95,15 @@ def prepare_pairs(srcs: Sequence[torch.Tensor], tgts: Sequence[torch.Tensor], T,
     if center not in CENTER_RULES:
         raise ValueError("center must be one of %s, got %r" % (sorted(CENTER_RULES), center))
     clouds = srcs + tgts
-    dev, dtype = clouds[0].device, clouds[0].dtype
-    for i, cl in enumerate(clouds):
-        if not isinstance(cl, torch.Tensor) or cl.dim() != 2 or cl.shape[1] != 3:
-            raise _lib.ScreamHipError("cloud %d: expected a [N,3] tensor, got %s" % (i, tuple(getattr(cl, "shape", ()))))
-        if not cl.is_cuda:
-            raise _lib.ScreamHipError("batch preparation needs tensors on the MI355X (cloud %d is on %s); there is no CPU path" % (i, cl.device))
-        if cl.dtype != dtype or dtype not in (torch.float32, torch.float64):
-            raise _lib.ScreamHipError("cloud %d: the clouds must be all float32 or all float64, got %s" % (i, cl.dtype))
+    check_clouds(clouds, "cloud", (torch.float32, torch.float64), op="batch preparation")
+    dev = clouds[0].device
     src_len, tgt_len = [int(t.shape[0]) for t in srcs], [int(t.shape[0]) for t in tgts]
     lens, row0, rows_src, rows_total, tile_cloud, max_chunks = PackedBatch.layout(src_len, tgt_len)
     raw_row0 = np.concatenate([[0], np.cumsum(lens.astype(np.int64))[:-1]])
     if int(lens.astype(np.int64).sum()) >= 2 ** 31:
         raise ValueError("batch too large for int32 row indices")
-    Tm = _matrices(T, B, "T", dev)
-    Pm = _matrices(np.broadcast_to(np.eye(4), (B, 4, 4)) if perturb is None else perturb, B, "perturb", dev)
+    Tm = pose_stack(T, B, dev, "T").reshape(-1)
+    Pm = pose_stack(np.broadcast_to(np.eye(4), (B, 4, 4)) if perturb is None else perturb, B, dev, "perturb").reshape(-1)
     sd = np.zeros(B, dtype=np.int64) if side is None else np.asarray(side, dtype=np.int64).reshape(-1)
     ids = np.arange(B, dtype=np.int64) if sample_ids is None else np.asarray(sample_ids, dtype=np.int64).reshape(-1)
     if sd.shape[0] != B or ids.shape[0] != B:

@@ -16,7 +16,8 @@ from typing import List, Sequence, Union
 
 import torch
 
-from . import _lib, ops
+from . import ops
+from .clouds import check_clouds, check_radius, pack_clouds
 
 __all__ = ["voxel_down_sample", "voxel_down_sample_batch"]
 
@@ -33,21 +34,11 @@ def voxel_down_sample_batch(clouds: Sequence[torch.Tensor], voxel: Union[float, 
         raise ValueError("%d voxel sizes for %d clouds" % (len(voxels), B))
     if B == 0:
         return ([], []) if return_counts else []
-    for i, (c, v) in enumerate(zip(clouds, voxels)):
-        if not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] != 3:
-            raise ValueError("cloud %d: expected a [N,3] tensor, got %s" % (i, tuple(getattr(c, "shape", ()))))
-        if not c.is_cuda:
-            raise _lib.ScreamHipError("voxel_down_sample needs tensors on the MI355X (cloud %d is on %s); there is no CPU path" % (i, c.device))
-        if c.dtype != torch.float32:
-            raise TypeError("cloud %d: expected torch.float32, got %s" % (i, c.dtype))
-        if not v > 0 or v == float("inf"):
-            raise ValueError("cloud %d: voxel size must be a positive finite number, got %r" % (i, v))
+    check_clouds(clouds, "cloud", op="voxel_down_sample", builtin_errors=True)
+    for i, v in enumerate(voxels):
+        check_radius(v, "cloud %d: voxel size" % i, ValueError)
     dev = clouds[0].device
-    lens = [int(c.shape[0]) for c in clouds]
-    row0 = [0] * B
-    for i in range(1, B):
-        row0[i] = row0[i - 1] + lens[i - 1]
-    xyz = torch.cat([c.detach() for c in clouds], dim=0).contiguous()
+    xyz, row0, lens = pack_clouds(clouds)
     meta = torch.tensor([row0, lens], dtype=torch.int32).to(dev)
     vox = torch.tensor(voxels, dtype=torch.float64).to(dev)
     out, out_len, out_cnt = ops.voxel_down_sample_packed(xyz, meta[0], meta[1], max(lens), vox, want_counts=return_counts)

@@ -306,6 +306,36 @@ def test_a_cloud_whose_rows_leave_the_arrays_is_skipped_on_the_device():
         assert (out[30:60] == -77.0).all() and (centre[1] == 0.0).all()
 
 
+def test_a_dirty_workspace_changes_nothing():
+    """The call zeroes the grid's counters itself (csrc/cell_grid.h) and reads nothing else of the workspace before writing it:
+    a workspace full of 0xFF and one full of 0x00 give the same bits, those of the reference.  Two clouds of 300 and 70 patch
+    rows (two blocks and a part of one) and 130 and 5 ground rows."""
+    lib = _lib.load()
+    rng = np.random.default_rng(17)
+    patch = rng.uniform(0, 6, size=(370, 3)).astype(np.float32)
+    dem = rng.uniform(-2, 8, size=(135, 3)).astype(np.float32)  # about half of the ground points lie beyond the patch's reach
+    want = [DR.dsm_ref(patch[:300], dem[:130]), DR.dsm_ref(patch[300:], dem[130:])]
+    assert all((w[1] >= 0).any() and (w[1] < 0).any() for w in want)
+    tp, td = torch.from_numpy(patch).to(DEV), torch.from_numpy(dem).to(DEV)
+    m = torch.tensor([[0, 300], [300, 70], [0, 130], [130, 5]], dtype=torch.int32).to(DEV)
+    need = lib.scream_dsm_workspace_bytes(370, 2, 300)
+    assert need > 0
+    got = []
+    for fill in (0xFF, 0x00):
+        ws = torch.full((need,), fill, device=DEV, dtype=torch.uint8)
+        out_xyz = torch.full((135, 3), -77.0, device=DEV)
+        out_idx = torch.full((135,), -77, device=DEV, dtype=torch.int32)
+        rc = lib.scream_dsm_extract(tp.data_ptr(), m[0].data_ptr(), m[1].data_ptr(), 300, 370, td.data_ptr(), m[2].data_ptr(),
+                                    m[3].data_ptr(), 130, 135, 2, C.c_float(0.8), out_xyz.data_ptr(), out_idx.data_ptr(), ws.data_ptr(),
+                                    ws.numel(), torch.cuda.current_stream().cuda_stream)
+        assert rc == 0
+        got.append((out_xyz.cpu().numpy(), out_idx.cpu().numpy()))
+    same(got[0], got[1], "0xFF against 0x00")
+    for xyz, idx in got:
+        same((xyz[:130], idx[:130]), want[0], "cloud 0")
+        same((xyz[130:], idx[130:]), want[1], "cloud 1")
+
+
 def test_wrong_dtype_device_shape_or_radius_raise():
     good = torch.zeros(5, 3, device=DEV)
     for bad in (torch.zeros(5, 3, device=DEV, dtype=torch.float64), torch.zeros(5, 3), torch.zeros(5, 2, device=DEV),

@@ -286,6 +286,55 @@ def test_a_pair_whose_rows_leave_the_arrays_is_skipped_on_the_device():
         assert np.array_equal(c[0:30], want[0]) and np.array_equal(c[60:90], want[2]) and (c[30:60] == -77).all(), what
 
 
+def test_a_dirty_workspace_changes_nothing():
+    """The count call zeroes the grid's counters itself (csrc/cell_grid.h) and reads nothing else of the workspace before writing
+    it: a workspace full of 0xFF and one full of 0x00 give the same counts and, through the fill launch, the same pairs -- those
+    of the reference.  Two pairs of 300 and 70 target rows (two blocks and a part of one) and 130 and 5 source rows."""
+    lib = _lib.load()
+    rng = np.random.default_rng(19)
+    tgt = rng.uniform(0, 0.4, size=(370, 3)).astype(np.float32)
+    src = rng.uniform(0, 0.4, size=(135, 3)).astype(np.float32)
+    refs = [RR.radius_ref(src[:130], tgt[:300], np.eye(4), 0.06), RR.radius_ref(src[130:], tgt[300:], np.eye(4), 0.06)]
+    want_count = np.concatenate([r[0] for r in refs])
+    want_j = np.concatenate([r[1][:, 1] for r in refs])
+    assert all((r[0] > 0).any() and (r[0] == 0).any() for r in refs)
+    ts, tt = torch.from_numpy(src).to(DEV), torch.from_numpy(tgt).to(DEV)
+    T = torch.eye(4, dtype=torch.float64).reshape(1, 16).repeat(2, 1).contiguous().to(DEV)
+    m = torch.tensor([[0, 130], [130, 5], [0, 300], [300, 70]], dtype=torch.int32).to(DEV)
+    need = lib.scream_radius_workspace_bytes(370, 2, 300)
+    assert need > 0
+    stream = torch.cuda.current_stream().cuda_stream
+    got = []
+    for fill in (0xFF, 0x00):
+        ws = torch.full((need,), fill, device=DEV, dtype=torch.uint8)
+        count = torch.full((135,), -77, device=DEV, dtype=torch.int32)
+        head = (ts.data_ptr(), m[0].data_ptr(), m[1].data_ptr(), 130, 135, tt.data_ptr(), m[2].data_ptr(), m[3].data_ptr(), 300, 370,
+                T.data_ptr(), 2, C.c_double(0.06))
+        assert lib.scream_radius_count(*head, count.data_ptr(), ws.data_ptr(), ws.numel(), stream) == 0
+        offset = torch.zeros(136, device=DEV, dtype=torch.int64)
+        torch.cumsum(count.to(torch.int64), dim=0, out=offset[1:])
+        pair_j = torch.full((135 * 300,), -77, device=DEV, dtype=torch.int32)  # room for whatever the counts say
+        assert lib.scream_radius_pairs(*head, ws.data_ptr(), ws.numel(), 0, offset.data_ptr(), pair_j.data_ptr(), stream) == 0
+        got.append((count.cpu().numpy(), pair_j[:int(offset[-1])].cpu().numpy().astype(np.int64)))
+    assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
+    for count, pair_j in got:
+        assert np.array_equal(count, want_count) and np.array_equal(pair_j, want_j)
+
+
+def test_targets_of_257_rows_on_a_plane_and_on_a_line():
+    """A grid of n = (k, k, 1) and one of n = (k, 1, 1) cells, two blocks of target rows each (256 + 1); the sources lie at N(0, 0.02)
+    of target points, on both sides of the 0.03 radius."""
+    rng = np.random.default_rng(51)
+    line = np.stack([rng.uniform(0, 2, size=257), np.full(257, 0.5), np.full(257, -0.5)], axis=1).astype(np.float32)
+    plane = np.stack([rng.uniform(0, 2, size=257), rng.uniform(0, 2, size=257), np.full(257, 1.0)], axis=1).astype(np.float32)
+    tgts = [plane, line]
+    srcs = [(t[rng.integers(0, 257, size=200)] + rng.normal(0, 0.02, size=(200, 3))).astype(np.float32) for t in tgts]
+    for want in check_batch(srcs, tgts, [np.eye(4)] * 2, 0.03, what="257 rows"):
+        assert (want[0] > 0).sum() > 50 and (want[0] == 0).sum() > 50
+    for s, t in zip(srcs, tgts):  # and each alone
+        check_batch([s], [t], [np.eye(4)], 0.03, what="257 rows alone")
+
+
 def test_wrong_dtype_device_shape_or_radius_raise():
     good = torch.zeros(5, 3, device=DEV)
     eye = [np.eye(4)]

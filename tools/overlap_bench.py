@@ -8,7 +8,7 @@ Data: seeded synthetic 3DMatch pairs (scream_amd.synthetic.make_3dmatch_pair) vo
 25 000 points, the size of a PREDATOR fragment at its 0.025 m voxel.  Radius 0.03 m, the reference's overlap radius.
 
 Timed, HIP events around the calls, median / min / max of --runs after --warmup:
-  count    ops.radius_count_packed on packed rows (memset, plan, cell count, scan, scatter, query; workspace allocation included)
+  count    ops.radius_count_packed on packed rows (plan, cell count, scan, scatter, query; workspace allocation included)
            at 1 pair and at 32 pairs per call
   pairs    the public radius_pairs_batch (count, prefix sum, one host read, fill, slicing) at the same two sizes
   prepare  the public prepare_3dmatch_batch (overlap, src[~mask], the 3 B clouds down-sampled at 0.0625 m) at the same two sizes
