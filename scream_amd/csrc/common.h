@@ -102,6 +102,53 @@ __device__ __forceinline__ float elu1s(float t, const Elu1Consts& k) {
     const float e = __builtin_fmaf(r, lo * LN2, r);
     return fmaxf(__builtin_fmaf(t, k.c, 1.0f), e);
 }
+// elu1s of TWO independent elements in place (element i of a and of b), cut into four steps of four instructions that a caller
+// spreads over four gaps between matrix instructions (proj_ring.hip): the same eight instructions per element on the same
+// operands -- bit for bit elu1s -- but no instruction reads the result of the one in front of it, each step holds at most one
+// v_exp_f32, and a step's results are consumed a gap later.  The state between the steps is four registers; the element itself
+// turns into 1 + t c in step 2 / 3, once nothing reads t any more.
+struct Elu1Pair {
+    float r[2], l[2];  // hi, then exp2(hi) clamped | the rounding term, then lo, then lo ln 2, then the exponential branch
+};
+// An empty statement that hipcc neither moves nor looks through: what it is given has been computed where it stands.  (Left
+// alone hipcc SINKS a computation whose only reader stands in a conditional block into that block -- all of a query chunk's
+// elu + 1 landed behind one matrix instruction, in front of the chunk's stores.)
+__device__ __forceinline__ void keep_here(float& x) { asm volatile("" : "+v"(x)); }
+__device__ __forceinline__ void keep_here(float& x, float& y) { asm volatile("" : "+v"(x), "+v"(y)); }
+__device__ __forceinline__ void keep_here(float& x, float& y, float& z) { asm volatile("" : "+v"(x), "+v"(y), "+v"(z)); }
+__device__ __forceinline__ void keep_here(float& x, float& y, float& z, float& w) { asm volatile("" : "+v"(x), "+v"(y), "+v"(z), "+v"(w)); }
+__device__ __forceinline__ void elu1s_pair(int step, f32x16& a, f32x16& b, int i, Elu1Pair& s, const Elu1Consts& k) {
+    const float LN2 = 0.693147182464599609375f;
+    if (step == 0) {
+        s.r[0] = a[i] * k.cl2e;
+        s.r[1] = b[i] * k.cl2e;
+        s.l[0] = __builtin_fmaf(a[i], k.cl2e, -s.r[0]);
+        s.l[1] = __builtin_fmaf(b[i], k.cl2e, -s.r[1]);
+        keep_here(s.l[0], s.l[1]);
+    } else if (step == 1) {
+        s.r[0] = __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(s.r[0]), 0.0f, 1.0f);  // folds into v_exp_f32 ... clamp
+        s.l[0] = __builtin_fmaf(a[i], k.cl2e_lo, s.l[0]);
+        s.l[1] = __builtin_fmaf(b[i], k.cl2e_lo, s.l[1]);
+        s.l[0] = s.l[0] * LN2;
+        keep_here(s.r[0], s.l[0], s.l[1]);
+    } else if (step == 2) {
+        s.r[1] = __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(s.r[1]), 0.0f, 1.0f);
+        s.l[1] = s.l[1] * LN2;
+        s.l[0] = __builtin_fmaf(s.r[0], s.l[0], s.r[0]);
+        float p = __builtin_fmaf(a[i], k.c, 1.0f);
+        keep_here(s.r[1], s.l[1], s.l[0], p);
+        a[i] = p;
+    } else {
+        s.l[1] = __builtin_fmaf(s.r[1], s.l[1], s.r[1]);
+        // (v_max_f32 spelled out: behind keep_here hipcc no longer knows its operands to be canonical and would put a v_max x, x in
+        // front of each)
+        float pa, pb = __builtin_fmaf(b[i], k.c, 1.0f);
+        asm volatile("v_max_f32 %0, %1, %2" : "=v"(pa) : "v"(a[i]), "v"(s.l[0]));
+        asm volatile("v_max_f32 %0, %1, %2" : "=v"(pb) : "v"(pb), "v"(s.l[1]));
+        a[i] = pa;
+        b[i] = pb;
+    }
+}
 __device__ __forceinline__ float elu1(float x) {
     return elu1s(x, Elu1Consts{1.0f, 1.44269502162933349609375f, 1.925963033500011e-08f});
 }

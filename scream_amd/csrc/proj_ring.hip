@@ -19,6 +19,15 @@
 //         [head][33][32] that scream_kv_finalize_image sums per cloud.  K' and V never exist in memory.
 //     In the 8-wave GEMM a query tile's epilogue (a third of its time) ran with the matrix pipe idle -- its block-wide k-loop
 //     barriers keep both waves of a SIMD in lockstep.
+//     WHERE a ride's instructions stand is decided here, not by hipcc: a ride is cut into pieces of about four vector
+//     instructions, at most one v_exp_f32 among them, one piece behind each of a stage's 96 matrix instructions, with a
+//     sched_barrier(0) on both sides of every matrix instruction; its dependent chains run two elements in lock-step and a
+//     result is read a gap after it was made (common.h: elu1s_pair, split.h: split1s_pair_here).  Behind a 32-cycle matrix
+//     instruction about five vector instructions issue for free; a longer run makes the matrix pipe wait, and with one wave
+//     per SIMD so does a chain that waits for its own results.  (Scheduled by hipcc -- sched_group_barrier slots, "up to six
+//     behind each" -- the rides filled the first gaps of a group and left 886 of 1 187 empty, and a query chunk's whole
+//     elu + 1, 260 instructions, was SUNK into the conditional block of its stores, behind ONE matrix instruction.  Placing them by
+//     hand took 12 % off the kernel's cycles, 5-6 % off its time: profiles/r05_proj_rides_ab.txt; tests/test_proj_ring_rides_host.py holds the generated code to it.)
 //     (Built first with LDS-DMA "touches" -- one dword per 128-byte line of the NEXT tile's rows, one instruction per stage -- to have
 //     the rows in the L2 before the tile boundary reads them: 3-5 % SLOWER and 3.7 x the HBM fetch traffic by the counters, the
 //     narrow loads are fetched line by line and do not stay; removed -- profiles/r04_ring_proj_prefetch_experiment.txt.)
@@ -30,7 +39,8 @@
 // Stage sequence per 256-row tile (= image order): Q chunk 0 .. 7 (absent for a key/value-only call), then per layer of the
 // call and head h: K_h, V_h.  Vector-memory discipline: the ring's barrier waits with a COUNTED vmcnt that leaves the pieces
 // issued during the previous stage in flight; every store of a stage is issued before that stage's pieces (a counted wait is
-// only sound if what it leaves in flight are loads: stores retire out of order against loads); the only register loads are the
+// only sound if what it leaves in flight are loads: stores retire out of order against loads) -- a ride's stores stand in
+// groups 0 .. Q_WIN = 12 of a stage's 16, its pieces in groups 13 .. 15, still more than a stage ahead of their use; the only register loads are the
 // x rows at a tile boundary, plain loads that hipcc waits for with vmcnt(0).
 #include <type_traits>
 
@@ -69,7 +79,10 @@ __global__ __launch_bounds__(TT, 1) void proj_ring_kernel(ProjArgs pa) {
     constexpr int STAGE = stage_bytes<SP>();
     constexpr int PIECES = wave_pieces<SP>();   // LDS-DMA weight pieces per wave and stage
     constexpr int INFLIGHT = PIECES;            // what a ring wait leaves in flight: the pieces issued during the previous stage
-    constexpr int NV = 6;                       // ride slots behind every MFMA
+    constexpr int GM = 2 * SP::NPROD;           // matrix instructions of a group = gaps that a ride can fill
+    constexpr int Q_WIN = 12;                   // a query chunk's elu + 1 rides in groups 0 .. Q_WIN - 1, its stores go out in group Q_WIN
+    constexpr int PIECE_STRIDE = (15 - Q_WIN) * GM / PIECES;  // one weight piece per so many gaps of groups Q_WIN + 1 .. 15
+    static_assert(PIECE_STRIDE >= 1, "the groups behind the stores hold the stage's pieces");
     __shared__ __attribute__((aligned(16))) char smem[T_SLOTS * STAGE + P_SLAB_BYTES];  // the ONLY LDS object
     float* slabs = reinterpret_cast<float*>(smem + T_SLOTS * STAGE);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -168,55 +181,48 @@ __global__ __launch_bounds__(TT, 1) void proj_ring_kernel(ProjArgs pa) {
     float* part_pend = nullptr;  // where the pending head's partial goes
     bool part_pend_ok = false;
 
-    // one MFMA group: 16-deep step g of both row groups against the same weight fragment
-    // KIND 0: acc^T += W . x^T (lane = row, registers = features); KIND 1: acc += x . W^T (lane = feature, registers = rows)
-    auto group = [&](auto kind, f32x16 (&a)[2], const V (&w)[NP], int g, bool zero) __attribute__((always_inline)) {
-        constexpr int KIND = decltype(kind)::value;
-        f32x16 z;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) z[e] = 0.f;
-#pragma unroll
-        for (int rg = 0; rg < 2; ++rg) {
-            if (KIND == 0) SP::products(a[rg], w, xp[rg][g], zero ? z : a[rg]);
-            else SP::products(a[rg], xp[rg][g], w, zero ? z : a[rg]);
-        }
-        // first MFMA, then the prefetch reads of the next fragments (one per plane), then the other MFMAs with NV ride slots each
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, NP, 0);
-#pragma unroll
-        for (int i = 0; i < 2 * SP::NPROD - 1; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x002, NV, 0);
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x002, NV, 0);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-
-    // One ring stage: 16 groups = one 32-column chunk of W over K = 256 against the wave's 64 rows.  ride(g): the previous
-    // chunk's epilogue, cut into per-group pieces; its stores only in groups <= 8, this stage's weight pieces from group 9 on.
+    // One ring stage: 16 groups = one 32-column chunk of W over K = 256 against the wave's 64 rows; a group is the 16-deep step g of
+    // both row groups against the same weight fragment, GM matrix instructions (row group 0's products, then row group 1's).
+    // KIND 0: acc^T += W . x^T (lane = row, registers = features); KIND 1: acc += x . W^T (lane = feature, registers = rows).
+    // Every matrix instruction is placed BY HAND: sched_barrier(0) on both sides of it, so what stands between two of them in the
+    // source is what stands between them in the code.  ride(g, m) is the piece of the previous chunk's epilogue that goes behind
+    // matrix instruction m of group g: every ride cuts itself into GM pieces per group of a few vector instructions each, at most
+    // one of them a transcendental -- behind a 32-cycle matrix instruction about five vector instructions issue for free, one
+    // wave per SIMD has nothing else to issue while a dependent chain waits, and a gap left empty hides nothing.  The fragment
+    // reads of the next group go behind the group's first matrix instruction, the ride's stores in groups <= Q_WIN, this stage's
+    // weight pieces one per PIECE_STRIDE gaps from group Q_WIN + 1 on.
     auto stage = [&](auto kind, f32x16 (&a)[2], auto ride) __attribute__((always_inline)) {
+        constexpr int KIND = decltype(kind)::value;
         ring_barrier<INFLIGHT>();
         __builtin_amdgcn_sched_barrier(0);
         const char* wb = smem + (q % T_SLOTS) * STAGE + lane * 16;
         V wf[P_PF][NP];
+        f32x16 z;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) z[e] = 0.f;
 #pragma unroll
         for (int g0 = 0; g0 < P_PF - 1; ++g0)
 #pragma unroll
             for (int p = 0; p < NP; ++p) wf[g0][p] = ld_frag<V>(wb + (p * 16 + g0) * 1024);
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
-            if (g + P_PF - 1 < 16) {
 #pragma unroll
-                for (int p = 0; p < NP; ++p) wf[(g + P_PF - 1) % P_PF][p] = ld_frag<V>(wb + (p * 16 + g + P_PF - 1) * 1024);
-            }
-            if (g >= 9 && g < 13) {  // the PIECES weight pieces of the stage after next, two per group, behind every store of this stage's ride
+            for (int m = 0; m < GM; ++m) {
+                const int rg = m / SP::NPROD, i = m % SP::NPROD;
+                __builtin_amdgcn_sched_barrier(0);
+                if (KIND == 0) a[rg] = SP::product(i, wf[g % P_PF], xp[rg][g], g == 0 && i == 0 ? z : a[rg]);
+                else a[rg] = SP::product(i, xp[rg][g], wf[g % P_PF], g == 0 && i == 0 ? z : a[rg]);
+                __builtin_amdgcn_sched_barrier(0);
+                if (m == 0 && g + P_PF - 1 < 16) {
 #pragma unroll
-                for (int u = (g - 9) * 2; u < (g - 8) * 2; ++u)
-                    if (u < PIECES) dma_piece(q + 2, u);
+                    for (int p = 0; p < NP; ++p) wf[(g + P_PF - 1) % P_PF][p] = ld_frag<V>(wb + (p * 16 + g + P_PF - 1) * 1024);
+                }
+                const int ps = (g - Q_WIN - 1) * GM + m;  // the PIECES weight pieces of the stage after next, behind every store of this stage's ride
+                if (ps >= 0 && ps % PIECE_STRIDE == 0 && ps / PIECE_STRIDE < PIECES) dma_piece(q + 2, ps / PIECE_STRIDE);
+                ride(g, m);
             }
-            ride(g);
-            group(kind, a, wf[g % P_PF], g, g == 0);
         }
+        __builtin_amdgcn_sched_barrier(0);
         ++q;
     };
     static_assert(wave_pieces<SP>() <= 8, "the request schedule of a stage holds eight pieces");
@@ -224,16 +230,22 @@ __global__ __launch_bounds__(TT, 1) void proj_ring_kernel(ProjArgs pa) {
     constexpr std::integral_constant<int, 1> kindKV{};
 
     // ---- rides --------------------------------------------------------------------------------------------------------------
+    // items k0 .. k1 - 1 of n_items go into slot s of n_slots: in order, as evenly as the two numbers allow
+    auto first_item = [](int s, int n_items, int n_slots) __attribute__((always_inline)) { return (s * n_items + n_slots - 1) / n_slots; };
+    auto per_slot = [](int n_items, int n_slots) constexpr { return (n_items + n_slots - 1) / n_slots; };  // the most a slot holds
+    Elu1Pair ep;  // the elu + 1 chains under way: element i of both row groups in lock-step (common.h: elu1s_pair)
     // Q' chunk = elu(q) + 1 in place, fragment-major: piece a of an accumulator tile is one 1 KiB wave store (tail_split.hip: store_chunk)
-    auto ride_q = [&](f32x16 (&t)[2], int g) __attribute__((always_inline)) {
-        if (g < 8) {
+    // 16 pairs of four steps over the Q_WIN * GM gaps of groups 0 .. Q_WIN - 1
+    auto ride_q = [&](f32x16 (&t)[2], int g, int m) __attribute__((always_inline)) {
+        if (g < Q_WIN) {
+            const int s = g * GM + m;
 #pragma unroll
-            for (int rg = 0; rg < 2; ++rg)
-#pragma unroll
-                for (int e = 0; e < 2; ++e) t[rg][2 * g + e] = elu1s(t[rg][2 * g + e], pa.ec);
+            for (int j = 0; j < per_slot(64, Q_WIN * GM); ++j) {
+                const int k = first_item(s, 64, Q_WIN * GM) + j;
+                if (k < first_item(s + 1, 64, Q_WIN * GM)) elu1s_pair(k & 3, t[0], t[1], k >> 2, ep, pa.ec);
+            }
         }
-        if (g == 8) {
-            __builtin_amdgcn_sched_barrier(0);
+        if (g == Q_WIN && m == 0) {
             if (q_pend_ok) {
 #pragma unroll
                 for (int rg = 0; rg < 2; ++rg)
@@ -243,36 +255,45 @@ __global__ __launch_bounds__(TT, 1) void proj_ring_kernel(ProjArgs pa) {
                         __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(q_pend + rg * 8192 + a * 256));
                     }
             }
-            __builtin_amdgcn_sched_barrier(0);
         }
     };
-    // K' = elu(k) + 1 with the padding rows zeroed, its row sum and its two fp16 planes: one register of both row groups per group.
+    // K' = elu(k) + 1 with the padding rows zeroed, its row sum and its two fp16 planes: register g of both row groups in group g,
+    // six items (the four steps of the pair's elu + 1, mask and row sum, the split) over the group's GM gaps.
     // MASK (compile time; wave-uniform per tile): only a cloud's last tile has padding rows -- everywhere else the compare and
-    // select per element (two of a dozen vector instructions; at the socket power cap every one of them is paid in time) are left out
-    auto ride_k = [&](auto mask, const f32x16 (&t)[2], int valid, int g) __attribute__((always_inline)) {
-        if (g == 0) ks = 0.f;
+    // select per element are left out
+    auto ride_k = [&](auto mask, f32x16 (&t)[2], int valid, int g, int m) __attribute__((always_inline)) {
 #pragma unroll
-        for (int rg = 0; rg < 2; ++rg) {
-            float a = elu1s(t[rg][g], pa.ec);
-            if (decltype(mask)::value && (g & 3) + 8 * (g >> 2) + 32 * rg >= valid) a = 0.f;  // row mfma32_row(g, half) + 32 rg of the wave's 64 (valid carries the half)
-            ks += a;
-            SplitH2::split1s(a, pa.kv_sk, g & 7, kp[rg][g >> 3]);
+        for (int j = 0; j < per_slot(6, GM); ++j) {
+            const int k = first_item(m, 6, GM) + j;
+            if (k >= first_item(m + 1, 6, GM)) continue;
+            if (k < 4) elu1s_pair(k, t[0], t[1], g, ep, pa.ec);
+            if (k == 4) {
+                if (g == 0) ks = 0.f;
+#pragma unroll
+                for (int rg = 0; rg < 2; ++rg) {
+                    if (decltype(mask)::value && (g & 3) + 8 * (g >> 2) + 32 * rg >= valid) t[rg][g] = 0.f;  // row mfma32_row(g, half) + 32 rg of the wave's 64 (valid carries the half)
+                    ks += t[rg][g];
+                }
+                keep_here(ks);
+            }
+            if (k == 5) {
+                SplitH2::split1s_pair_here(t[0][g], t[1][g], pa.kv_sk, g & 7, kp[0][g >> 3], kp[1][g >> 3]);
+                if (g == 15) ks += __shfl_xor(ks, 32);
+            }
         }
-        if (g == 15) ks += __shfl_xor(ks, 32);
     };
     // V's planes, the 12 MFMAs of K'^T V over the wave's 64 rows, the wave's tile into its LDS slab
     f16x8 vp[2][2];  // [row group][plane] of the 16-row step being made
-    auto ride_v = [&](const f32x16 (&t)[2], int g) __attribute__((always_inline)) {
+    auto ride_v = [&](const f32x16 (&t)[2], int g, int m) __attribute__((always_inline)) {
         if (g < 8) {
             const int s2 = g >> 2;  // groups 0-3: rows' step 0, groups 4-7: step 1
-#pragma unroll
-            for (int rg = 0; rg < 2; ++rg)
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const int i = 8 * s2 + 2 * (g & 3) + e;
-                    SplitH2::split1s(t[rg][i], pa.kv_cv, i & 7, vp[rg]);
-                }
-            if ((g & 3) == 3) {
+            // the group's two elements of both row groups behind its first two matrix instructions; a step's products behind the last
+            // matrix instruction of its fourth group
+            if (m < 2) {
+                const int i = 8 * s2 + 2 * (g & 3) + m;
+                SplitH2::split1s_pair_here(t[0][i], t[1][i], pa.kv_cv, i & 7, vp[0], vp[1]);
+            }
+            if ((g & 3) == 3 && m == GM - 1) {
                 f32x16 z;
 #pragma unroll
                 for (int e = 0; e < 16; ++e) z[e] = 0.f;
@@ -280,27 +301,44 @@ __global__ __launch_bounds__(TT, 1) void proj_ring_kernel(ProjArgs pa) {
                 SplitH2::products(kv, kp[1][s2], vp[1], kv);
             }
         }
-        if (g == 9) kv *= pa.kv_inv;  // exact: a power of two (1 / v_length is applied once, in scream_kv_finalize_image)
+        if (g == 9) {  // exact: a power of two (1 / v_length is applied once, in scream_kv_finalize_image)
+#pragma unroll
+            for (int j = 0; j < per_slot(16, GM); ++j) {
+                const int e = first_item(m, 16, GM) + j;
+                if (e < first_item(m + 1, 16, GM)) kv[e] *= pa.kv_inv;
+            }
+        }
         if (g >= 10 && g < 14) {
             float* sw = slabs + wave * P_KV_ELEMS;
+            const int s = (g - 10) * GM + m;
 #pragma unroll
-            for (int e = 4 * (g - 10); e < 4 * (g - 9); ++e) sw[mfma32_row(e, half) * 32 + r] = kv[e];  // [d][v]
-            if (g == 13 && half == 0) sw[32 * 32 + r] = ks;
+            for (int j = 0; j < per_slot(16, 4 * GM); ++j) {
+                const int e = first_item(s, 16, 4 * GM) + j;
+                if (e < first_item(s + 1, 16, 4 * GM)) sw[mfma32_row(e, half) * 32 + r] = kv[e];  // [d][v]
+            }
+            if (g == 13 && m == GM - 1 && half == 0) sw[32 * 32 + r] = ks;
         }
     };
-    // the two waves of a 128-row tile add their K'^T V tiles (even wave's first) and write the partial: 1 056 floats, half each
-    auto ride_kvstore = [&](int g) __attribute__((always_inline)) {
-        if (g > 8) return;
+    // the two waves of a 128-row tile add their K'^T V tiles (even wave's first) and write the partial: 1 056 floats, half each;
+    // the two LDS reads behind one matrix instruction, the sum and its store behind a later one
+    float kvs[2];
+    auto ride_kvstore = [&](int g, int m) __attribute__((always_inline)) {
+        constexpr int M_RD = GM >= 4 ? 1 : 0, M_ST = GM >= 4 ? 3 : GM - 1;
+        if (g > 8 || (m != M_RD && m != M_ST)) return;
         const int i = (wave & 1) * 64 + lane + 128 * g;
         if (i < P_KV_ELEMS && part_pend_ok) {
             const float* s2 = slabs + (wave & ~1) * P_KV_ELEMS + i;
-            part_pend[i] = s2[0] + s2[P_KV_ELEMS];  // a plain store: non-temporal, kv_finalize_image reads the partials from memory (profiles/r04_nontemporal_and_stash.txt)
+            if (m == M_RD) {
+                kvs[0] = s2[0];
+                kvs[1] = s2[P_KV_ELEMS];
+            }
+            if (m == M_ST) part_pend[i] = kvs[0] + kvs[1];  // a plain store: non-temporal, kv_finalize_image reads the partials from memory (profiles/r04_nontemporal_and_stash.txt)
         }
     };
 
     // ---- the block's units ----------------------------------------------------------------------------------------------------
     int prev = 0;  // what the previous unit left pending in acc[1]: 0 nothing, 1 a query chunk, 2 a value chunk (+ its head's K' planes)
-    auto no_ride = [&](int) __attribute__((always_inline)) {};
+    auto no_ride = [&](int, int) __attribute__((always_inline)) {};
 #define LAMBDA(...) [&](__VA_ARGS__) __attribute__((always_inline))
     for (int64_t u = u_lo; u < u_hi; ++u) {
         const int64_t t = u / UPT;
@@ -310,31 +348,31 @@ __global__ __launch_bounds__(TT, 1) void proj_ring_kernel(ProjArgs pa) {
             // ---- two query chunks 2 uu, 2 uu + 1
             float* q_even = qg + (2 * uu) * 1024;
             if (prev == 0) stage(kindQ, acc[0], no_ride);
-            else if (prev == 1) stage(kindQ, acc[0], LAMBDA(int g) { ride_q(acc[1], g); });
-            else stage(kindQ, acc[0], LAMBDA(int g) { ride_v(acc[1], g); });
+            else if (prev == 1) stage(kindQ, acc[0], LAMBDA(int g, int m) { ride_q(acc[1], g, m); });
+            else stage(kindQ, acc[0], LAMBDA(int g, int m) { ride_v(acc[1], g, m); });
             const bool store_kv = prev == 2;
             q_pend = q_even;
             q_pend_ok = wave_ok;
-            if (store_kv) stage(kindQ, acc[1], LAMBDA(int g) { ride_kvstore(g); ride_q(acc[0], g); });
-            else stage(kindQ, acc[1], LAMBDA(int g) { ride_q(acc[0], g); });
+            if (store_kv) stage(kindQ, acc[1], LAMBDA(int g, int m) { ride_kvstore(g, m); ride_q(acc[0], g, m); });
+            else stage(kindQ, acc[1], LAMBDA(int g, int m) { ride_q(acc[0], g, m); });
             q_pend = q_even + 1024;
             prev = 1;
         } else {
             // ---- head h of layer l: K chunk, then V chunk
             const int p = uu - nq2, l = p >> 3, h = p & 7;
             if (prev == 0) stage(kindKV, acc[0], no_ride);
-            else if (prev == 1) stage(kindKV, acc[0], LAMBDA(int g) { ride_q(acc[1], g); });
-            else stage(kindKV, acc[0], LAMBDA(int g) { ride_v(acc[1], g); });
+            else if (prev == 1) stage(kindKV, acc[0], LAMBDA(int g, int m) { ride_q(acc[1], g, m); });
+            else stage(kindKV, acc[0], LAMBDA(int g, int m) { ride_v(acc[1], g, m); });
             const bool store_kv = prev == 2;
             const int valid = valid0 - 4 * half;  // per lane: the compare below is then against a literal
             constexpr std::integral_constant<bool, true> masked{};
             constexpr std::integral_constant<bool, false> whole{};
             if (valid0 < 64) {  // (idle waves: valid0 == 0)
-                if (store_kv) stage(kindKV, acc[1], LAMBDA(int g) { ride_kvstore(g); ride_k(masked, acc[0], valid, g); });
-                else stage(kindKV, acc[1], LAMBDA(int g) { ride_k(masked, acc[0], valid, g); });
+                if (store_kv) stage(kindKV, acc[1], LAMBDA(int g, int m) { ride_kvstore(g, m); ride_k(masked, acc[0], valid, g, m); });
+                else stage(kindKV, acc[1], LAMBDA(int g, int m) { ride_k(masked, acc[0], valid, g, m); });
             } else {
-                if (store_kv) stage(kindKV, acc[1], LAMBDA(int g) { ride_kvstore(g); ride_k(whole, acc[0], valid, g); });
-                else stage(kindKV, acc[1], LAMBDA(int g) { ride_k(whole, acc[0], valid, g); });
+                if (store_kv) stage(kindKV, acc[1], LAMBDA(int g, int m) { ride_kvstore(g, m); ride_k(whole, acc[0], valid, g, m); });
+                else stage(kindKV, acc[1], LAMBDA(int g, int m) { ride_k(whole, acc[0], valid, g, m); });
             }
             part_pend = part_tile + (int64_t)l * pa.kv_layer_stride + h * P_KV_ELEMS;
             part_pend_ok = wave_ok;
@@ -345,14 +383,20 @@ __global__ __launch_bounds__(TT, 1) void proj_ring_kernel(ProjArgs pa) {
     __builtin_amdgcn_sched_barrier(0);
     if (prev == 1) {
 #pragma unroll
-        for (int g = 0; g < 9; ++g) ride_q(acc[1], g);
+        for (int g = 0; g <= Q_WIN; ++g)
+#pragma unroll
+            for (int m = 0; m < GM; ++m) ride_q(acc[1], g, m);
     } else if (prev == 2) {
         lds_only_barrier();  // every wave has read the previous head's slabs (the ride of the stage just finished)
 #pragma unroll
-        for (int g = 0; g < 14; ++g) ride_v(acc[1], g);
+        for (int g = 0; g < 14; ++g)
+#pragma unroll
+            for (int m = 0; m < GM; ++m) ride_v(acc[1], g, m);
         lds_only_barrier();
 #pragma unroll
-        for (int g = 0; g < 9; ++g) ride_kvstore(g);
+        for (int g = 0; g < 9; ++g)
+#pragma unroll
+            for (int m = 0; m < GM; ++m) ride_kvstore(g, m);
     }
 #undef LAMBDA
     VM_WAIT(0);  // the ring's last two stages (requested past the end) must have landed before the LDS is released

@@ -100,6 +100,36 @@ struct SplitH2 {
         p[0] = __builtin_bit_cast(vec, a);
         p[1] = __builtin_bit_cast(vec, b);
     }
+    // split1s of element i of TWO plane sets (x into p, y into q) as the four v_fma_mix instructions it is, in lock-step (both leading
+    // planes, then both residuals: a residual reads its leading plane, and one wave per SIMD has nothing else to issue while it
+    // waits) and where the caller stands (volatile: proj_ring.hip places them behind a matrix instruction of its choice; left to
+    // itself hipcc makes seven instructions of some of these splits and gathers them where their reader is).  An even element
+    // must be written before its odd neighbour: it starts the register.
+    static __device__ __forceinline__ void split1s_pair_here(float x, float y, float s, int i, vec (&p)[2], vec (&q)[2]) {
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        u32x4 pa = __builtin_bit_cast(u32x4, p[0]), pb = __builtin_bit_cast(u32x4, p[1]);
+        u32x4 qa = __builtin_bit_cast(u32x4, q[0]), qb = __builtin_bit_cast(u32x4, q[1]);
+        unsigned ph = pa[i >> 1], pl = pb[i >> 1], qh = qa[i >> 1], ql = qb[i >> 1];
+        if ((i & 1) == 0) {
+            asm volatile("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(ph) : "v"(x), "s"(s));
+            asm volatile("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(qh) : "v"(y), "s"(s));
+            asm volatile("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(pl) : "v"(x), "s"(s), "v"(ph));
+            asm volatile("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(ql) : "v"(y), "s"(s), "v"(qh));
+        } else {
+            asm volatile("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(ph) : "v"(x), "s"(s));
+            asm volatile("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(qh) : "v"(y), "s"(s));
+            asm volatile("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(pl) : "v"(x), "s"(s), "v"(ph));
+            asm volatile("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(ql) : "v"(y), "s"(s), "v"(qh));
+        }
+        pa[i >> 1] = ph;
+        pb[i >> 1] = pl;
+        qa[i >> 1] = qh;
+        qb[i >> 1] = ql;
+        p[0] = __builtin_bit_cast(vec, pa);
+        p[1] = __builtin_bit_cast(vec, pb);
+        q[0] = __builtin_bit_cast(vec, qa);
+        q[1] = __builtin_bit_cast(vec, qb);
+    }
     static __device__ __forceinline__ f32x16 mfma(vec a, vec b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
     template <bool MIRROR = false>
     static __device__ __forceinline__ void products(f32x16& acc, const vec (&x)[2], const vec (&y)[2], const f32x16& c0) {
@@ -107,6 +137,10 @@ struct SplitH2 {
         acc = mfma(x[0], y[1], c0);
         acc = mfma(x[1], y[0], acc);
         acc = mfma(x[0], y[0], acc);
+    }
+    // product i of products() alone, for a kernel that places every matrix instruction itself (proj_ring.hip)
+    static __device__ __forceinline__ f32x16 product(int i, const vec (&x)[2], const vec (&y)[2], const f32x16& c) {
+        return i == 0 ? mfma(x[0], y[1], c) : i == 1 ? mfma(x[1], y[0], c) : mfma(x[0], y[0], c);
     }
 };
 
@@ -131,6 +165,7 @@ struct SplitH1 {
     static __device__ __forceinline__ void products(f32x16& acc, const vec (&x)[1], const vec (&y)[1], const f32x16& c0) {
         acc = mfma(x[0], y[0], c0);
     }
+    static __device__ __forceinline__ f32x16 product(int, const vec (&x)[1], const vec (&y)[1], const f32x16& c) { return mfma(x[0], y[0], c); }
 };
 
 // eight consecutive operand values (two f32x4) -> planes (SplitH2: the values already carry the operand's 2^e)
