@@ -767,6 +767,40 @@ int scream_l1_pairs_bwd(const float* dout, const float* pred, const float* xyz, 
                         const float* target, const int32_t* cloud_row0, const int32_t* cloud_len, int32_t n_pairs, int32_t max_len,
                         int64_t rows_src, float* dpred, void* stream);
 
+/* ---- The optimiser step: torch.optim.Adam (weight_decay = 0, amsgrad = False, maximize = False) over every parameter of a
+ * model in one launch (csrc/optim.hip; scream_amd/optim.py is its host layer, tests/adam_ref.py its numpy restatement).
+ * tensors: DEVICE work list of n_tensors rows of SCREAM_ADAM_TENSOR_BYTES bytes, { float* p; const float* grad; float* m;
+ * float* v; int64_t numel; }, every array contiguous fp32.  chunks: DEVICE int32 [n_chunks,2], (row of the work list, chunk
+ * inside that tensor); chunk k of a tensor is its elements k * SCREAM_ADAM_CHUNK .. min((k + 1) * SCREAM_ADAM_CHUNK, numel),
+ * one block each, so the caller lists ceil(numel / SCREAM_ADAM_CHUNK) chunks per tensor (none for an empty one).  A tensor
+ * whose four bases are all 16-byte aligned moves in 16-byte accesses with its numel % 4 tail element by element; any other
+ * tensor is handled element by element.  Nothing is read or written past numel.
+ * state: DEVICE, 8-byte aligned, { double q1; double q2; float step; float unused; }: the running powers beta1^step and
+ * beta2^step (both 1.0 before the first step) and the step count.  grad_scale / found_inf: optional fp32 DEVICE scalars
+ * (a GradScaler's); lr, beta1, beta2, eps by value.
+ *
+ * Every step below is ONE IEEE float64 operation on the stated operands, from the fp32 values widened first:
+ *   g   = double(grad) * inv,  inv = 1.0 / double(*grad_scale)  (1.0 without a grad_scale)
+ *   m'  = m + (g - m) * (1 - beta1)
+ *   v'  = (beta2 * v) + ((1 - beta2) * (g * g))
+ *   q1' = q1 * beta1,  q2' = q2 * beta2
+ *   step_size = lr / (1 - q1'),  denom = sqrt(v') / sqrt(1 - q2') + eps
+ *   p'  = p - step_size * (m' / denom)
+ * p', m' and v' are each rounded to fp32 once and stored; p' is computed from the unrounded m' and v'.
+ * If found_inf is given and *found_inf != 0 the call changes nothing, bit for bit: not p, m, v, nor q1, q2, step.
+ * Two launches on `stream`: the element kernel reads q1, q2 and computes q1', q2' for itself; a one-thread kernel BEHIND it
+ * stores q1', q2' and step + 1 (no block of the first launch can still be reading what the second writes; there is no
+ * double-buffering and the host keeps no step parity).  No atomics, no host synchronisation; bitwise repeatable.
+ * step is fp32 as in torch: exact up to 2^24 steps.
+ * SCREAM_EINVAL: negative counts, n_chunks > 2^31 - 1, a null or misaligned state, null tables with n_chunks > 0, tables not
+ * 8-byte aligned, lr or eps negative or not finite, a beta outside [0, 1).  A chunk row that names no tensor of the list or
+ * begins past its numel is skipped on the device. */
+#define SCREAM_ADAM_CHUNK 4096
+#define SCREAM_ADAM_TENSOR_BYTES 40
+int scream_adam_step(const void* tensors, int32_t n_tensors, const int32_t* chunks, int64_t n_chunks, double* state,
+                     const float* grad_scale, const float* found_inf, double lr, double beta1, double beta2, double eps,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,7 @@ computes needs libscream_hip.so and an MI355X and raises ``ScreamHipError`` othe
 """
 from ._lib import ScreamHipError  # noqa: F401
 from .dsm import extract_dsm, extract_dsm_batch, make_dsm_dem, make_dsm_dem_batch, tile_windows  # noqa: F401
+from .optim import FusedAdam  # noqa: F401
 from .overlap import (overlap_batch, prepare_3dmatch_batch, radius_count_batch, radius_pairs_batch,  # noqa: F401
                       select_outputs)
 from .prep import (PreparedPairs, packed_l1_loss, prepare_3dmatch_train, prepare_3dmatch_val, prepare_kitti_train,  # noqa: F401
@@ -15,5 +16,5 @@ from .voxel import voxel_down_sample, voxel_down_sample_batch  # noqa: F401
 __all__ = ["ScreamHipError", "voxel_down_sample", "voxel_down_sample_batch", "extract_dsm", "extract_dsm_batch", "make_dsm_dem",
            "make_dsm_dem_batch", "tile_windows", "radius_count_batch", "radius_pairs_batch", "overlap_batch", "prepare_3dmatch_batch",
            "select_outputs", "sample_perturbations", "prepare_pairs", "PreparedPairs", "prepare_3dmatch_train", "prepare_3dmatch_val",
-           "prepare_kitti_train", "prepare_kitti_val", "packed_l1_loss", "icp_raw_batch", "raw_nn_batch", "RawIcpRun"]
+           "prepare_kitti_train", "prepare_kitti_val", "packed_l1_loss", "icp_raw_batch", "raw_nn_batch", "RawIcpRun", "FusedAdam"]
 __version__ = "0.1.0"

@@ -129,6 +129,7 @@ SIGNATURES = {
     "scream_icp_raw_workspace_bytes": (C.c_int64, [I64, I64, I32]),
     "scream_icp_raw_range": (C.c_int, [V, V, V, V, V, V, I32, I32, I32, I64, I64, F64, I32, F64, F64, V, V, V, I32, I32, V, V, I64, V]),
     "scream_icp_raw_nn": (C.c_int, [V, V, V, V, V, V, I32, I32, I32, I64, I64, F64, V, V, V, V, V, I64, V]),
+    "scream_adam_step": (C.c_int, [V, I32, V, I64, V, V, V, F64, F64, F64, F64, V]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -37,6 +37,8 @@ SOURCES = {
     "prep.hip": ["-ffp-contract=off"],
     # every step of the raw-scan ICP is one IEEE float64 operation in a documented order (the file header)
     "icp_raw.hip": ["-ffp-contract=off"],
+    # the Adam update is one IEEE float64 operation per step of its contract, restated in numpy by tests/adam_ref.py
+    "optim.hip": ["-ffp-contract=off"],
 }
 ASM_LOADS = ("gemm_split.hip", "tail_split.hip", "proj_ring.hip")  # verified after code generation, see verify_one
 # kernels that must not touch scratch at all: a spill inside a ring stage costs a round trip per stage, and hipcc orders a scratch

@@ -97,6 +97,50 @@ class SyntheticPairs(Dataset):
         return (src_n, tgt_n, rot, trans, s, torch.LongTensor(idx), torch.Tensor(cov), c, scene)
 
 
+class RawPairFiles(Dataset):
+    """The directory format of PairFileDataset as TRAINING input: item i is the raw metric (src [N,3], tgt [M,3], T [4,4]),
+    float64, not normalised -- what prepare_3dmatch_* / prepare_kitti_* (scream_amd/prep.py) augment and normalise on the GPU.
+    The pair count is that of info/scene_names.txt when the directory has one, else the number of T%d.npy files.  Batches are
+    lists: DataLoader(..., collate_fn=list)."""
+
+    def __init__(self, root: str):
+        self.root = root
+        names = os.path.join(root, "info", "scene_names.txt")
+        if os.path.exists(names):
+            with open(names) as f:
+                self.count = len([l for l in f if l.strip()])
+        else:
+            self.count = 0
+            while os.path.exists(os.path.join(root, "T%d.npy" % self.count)):
+                self.count += 1
+
+    def __len__(self):
+        return self.count
+
+    def __getitem__(self, i):
+        return tuple(torch.from_numpy(np.asarray(np.load(os.path.join(self.root, "%s%d.npy" % (k, i))), dtype=np.float64))
+                     for k in ("src", "tgt", "T"))
+
+
+class SyntheticRawPairs(Dataset):
+    """Seeded raw training pairs, (src, tgt, T) float64 as RawPairFiles yields them: kind "3dmatch" | "lo" | "zero"
+    (synthetic.make_3dmatch_pair) or "kitti" (synthetic.make_kitti_pair); pair i comes from seed0 + i."""
+
+    def __init__(self, kind: str = "3dmatch", count: int = 16, seed0: int = 0):
+        if kind not in ("3dmatch", "lo", "zero", "kitti"):
+            raise ValueError("kind must be '3dmatch', 'lo', 'zero' or 'kitti', got %r" % (kind,))
+        self.kind, self.count, self.seed0 = kind, count, seed0
+
+    def __len__(self):
+        return self.count
+
+    def __getitem__(self, i):
+        if not 0 <= i < self.count:
+            raise IndexError(i)
+        raw = synthetic.make_kitti_pair(self.seed0 + i) if self.kind == "kitti" else synthetic.make_3dmatch_pair(self.seed0 + i, self.kind)
+        return tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)) for a in raw[:3])
+
+
 _PACKED = "scream-packed-batch-v1"
 
 
