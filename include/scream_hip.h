@@ -423,7 +423,12 @@ int scream_point_loss(const float* src_pred, const float* src, const int32_t* sr
  * starts there; every call of a run gets the same arguments and workspace) and then copies the per-pair stopped flags to
  * done_flags [n_pairs] (device int32, may be NULL) -- the caller copies them to pinned memory behind an event and decides on the
  * host, between pieces, without ever blocking the stream (scream_amd/ops.py: IcpRun).  T is complete for pair p once its flag
- * is set.  Results do not depend on how the schedule was cut. */
+ * is set.  Results do not depend on how the schedule was cut.
+ * scream_icp_p2p_brute_range is the YARDSTICK of the tests and of tools/icp_bench.py, not a product path: the arguments and the
+ * schedule of scream_icp_p2p_range, with every search done by scream_nn_search over all targets instead of the target grid
+ * (three or four launches per iteration instead of one).  Its results are bit for bit those of scream_icp_p2p_range.  A run
+ * uses ONE of the two entry points from it_begin == 0 to its end (they lay the workspace out differently);
+ * scream_icp_workspace_bytes covers both.  Nothing here reads the process environment. */
 int64_t scream_icp_workspace_bytes(int64_t src_rows_total, int64_t ref_rows_total, int32_t n_pairs);
 int scream_icp_p2p_range(const float* src, const float* ref, const int32_t* src_row0, const int32_t* src_len,
                          const int32_t* ref_row0, const int32_t* ref_len, const float* s, const float* c,
@@ -431,6 +436,12 @@ int scream_icp_p2p_range(const float* src, const float* ref, const int32_t* src_
                          int64_t ref_rows_total, float max_corr_dist, int32_t max_iter, float rel_fitness,
                          float rel_rmse, float* T, float* fitness_rmse, int32_t* iters, int32_t it_begin, int32_t it_end,
                          int32_t* done_flags, void* workspace, int64_t workspace_bytes, void* stream);
+int scream_icp_p2p_brute_range(const float* src, const float* ref, const int32_t* src_row0, const int32_t* src_len,
+                               const int32_t* ref_row0, const int32_t* ref_len, const float* s, const float* c,
+                               int32_t n_pairs, int32_t max_src_len, int32_t max_ref_len, int64_t src_rows_total,
+                               int64_t ref_rows_total, float max_corr_dist, int32_t max_iter, float rel_fitness,
+                               float rel_rmse, float* T, float* fitness_rmse, int32_t* iters, int32_t it_begin, int32_t it_end,
+                               int32_t* done_flags, void* workspace, int64_t workspace_bytes, void* stream);
 int scream_icp_p2p(const float* src, const float* ref, const int32_t* src_row0, const int32_t* src_len,
                    const int32_t* ref_row0, const int32_t* ref_len, const float* s, const float* c,
                    int32_t n_pairs, int32_t max_src_len, int32_t max_ref_len, int64_t src_rows_total,

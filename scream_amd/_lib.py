@@ -109,6 +109,7 @@ SIGNATURES = {
     "scream_grad3": (C.c_int, [V, V, V, V, I64, V, I32, V, V, I32, V, I64, V]),
     "scream_pe_embed": (C.c_int, [V, V, V, V, V, V, V, I64, V]),
     "scream_icp_p2p_range": (C.c_int, [V, V, V, V, V, V, V, V, I32, I32, I32, I64, I64, F32, I32, F32, F32, V, V, V, I32, I32, V, V, I64, V]),
+    "scream_icp_p2p_brute_range": (C.c_int, [V, V, V, V, V, V, V, V, I32, I32, I32, I64, I64, F32, I32, F32, F32, V, V, V, I32, I32, V, V, I64, V]),
     "scream_render_workspace_bytes": (C.c_int64, [I32, I32, I32, I64]),
     "scream_render_depth": (C.c_int, [V, V, V, V, V, V, I32, I32, I32, I64, V, I32, I32, F32, V, V, V, I64, V]),
     "scream_render_depth_bwd": (C.c_int, [V, V, V, I32, I32, I64, V, I32, I32, F32, V, V, V, I64, V, V]),

@@ -29,6 +29,7 @@ SOURCES = {
     "forward.hip": [],
     "nn_search.hip": ["-ffp-contract=off"],
     "kabsch.hip": ["-ffp-contract=off"],
+    "icp_p2p.hip": ["-ffp-contract=off"],
     "icp_grid.hip": ["-ffp-contract=off"],
     "render.hip": ["-ffp-contract=off"],
     "voxel.hip": ["-ffp-contract=off"],

@@ -29,27 +29,22 @@ struct Workspace {
 // intermediates go into Q' and the idle feature buffer.  The target side of all n_cross cross layers is projected at once.
 Workspace carve(void* base, int64_t rows_src, int64_t rows_total, int32_t n_pairs, int32_t max_chunks, int split, int32_t n_cross) {
     Workspace w;
-    float* p = reinterpret_cast<float*>(base);
-    auto take = [&](int64_t n) {
-        float* r = p;
-        p += (n + 63) / 64 * 64;  // keep every buffer 256-byte aligned
-        return r;
-    };
+    Carver cv{base};  // (an image is a whole number of floats, so the byte counts below are what the float counts were)
     const int64_t n_cross_batched = split ? n_cross : 0;
-    w.x0 = take(rows_total * D);
-    w.x1 = take(rows_total * D);
-    w.q = take(rows_total * D);
-    w.att = split ? nullptr : take(rows_total * D);
-    w.m1 = split ? nullptr : take(rows_total * D);
-    w.hid = split ? nullptr : take(rows_total * 4 * D);
-    w.kvp = take(rows_total / SCREAM_ROW_TILE * SCREAM_NHEAD * KV_ELEMS);  // one K^T V partial per 128-row tile and head
-    w.kv = take((int64_t)2 * n_pairs * SCREAM_NHEAD * KV_ELEMS);
-    w.kvimg = reinterpret_cast<char*>(take((int64_t)2 * n_pairs * scream_kv_image_bytes() / 4));
+    w.x0 = cv.take<float>(rows_total * D);
+    w.x1 = cv.take<float>(rows_total * D);
+    w.q = cv.take<float>(rows_total * D);
+    w.att = split ? nullptr : cv.take<float>(rows_total * D);
+    w.m1 = split ? nullptr : cv.take<float>(rows_total * D);
+    w.hid = split ? nullptr : cv.take<float>(rows_total * 4 * D);
+    w.kvp = cv.take<float>(rows_total / SCREAM_ROW_TILE * SCREAM_NHEAD * KV_ELEMS);  // one K^T V partial per 128-row tile and head
+    w.kv = cv.take<float>((int64_t)2 * n_pairs * SCREAM_NHEAD * KV_ELEMS);
+    w.kvimg = cv.take<char>((int64_t)2 * n_pairs * scream_kv_image_bytes());
     w.kvp_cross_stride = (rows_total - rows_src) / SCREAM_ROW_TILE * SCREAM_NHEAD * KV_ELEMS;
     w.kvimg_cross_stride = (int64_t)n_pairs * scream_kv_image_bytes();
-    w.kvp_cross = take(n_cross_batched * w.kvp_cross_stride);
-    w.kvimg_cross = reinterpret_cast<char*>(take(n_cross_batched * w.kvimg_cross_stride / 4));
-    w.bytes = (p - reinterpret_cast<float*>(base)) * (int64_t)sizeof(float);
+    w.kvp_cross = cv.take<float>(n_cross_batched * w.kvp_cross_stride);
+    w.kvimg_cross = cv.take<char>(n_cross_batched * w.kvimg_cross_stride);
+    w.bytes = cv.used;
     return w;
 }
 

@@ -1,7 +1,6 @@
-// Internal interface between kabsch.hip (the ICP loop) and icp_grid.hip / nn_search.hip; not part of the C ABI.
+// Internal interface between icp_p2p.hip (the ICP loop) and icp_grid.hip / nn_search.hip; not part of the C ABI.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "common.h"  // Carver
 
 constexpr int ICP_GRID_CELLS = 1 << 17;  // cells per pair (50^3 fits: a 5 m cloud at the 0.1 m radius of evaluate_3d_match.py)
 
@@ -23,7 +22,7 @@ __device__ __forceinline__ int cell_coord(float x, float o, float inv_h, int n) 
 // Nearest target of ONE query point within the radius (thresh = radius^2), over the nine x-runs of the 27 cells around it:
 // the same explicitly rounded distance as nn_search_kernel with s = 1, ties to the lowest ORIGINAL target index.
 // st / sp / si: the pair's cell starts, sorted records {b, |b|^2} and original indices; b_out: the coordinates of the winner
-// (the record's own, i.e. what ref[idx] holds).  Used by icp_iter_kernel (kabsch.hip), one launch per iteration.
+// (the record's own, i.e. what ref[idx] holds).  Used by icp_iter_kernel (icp_p2p.hip), one launch per iteration.
 __device__ __forceinline__ void grid_search_point(const GridParam& g, const int32_t* __restrict__ st, const float* __restrict__ sp,
                                                   const int32_t* __restrict__ si, float ax, float ay, float az, float thresh,
                                                   int32_t& idx_out, float& d_out, uint8_t& valid_out, float (&b_out)[3]) {
@@ -84,16 +83,19 @@ __device__ __forceinline__ void grid_search_point(const GridParam& g, const int3
 #endif
 
 struct IcpGrid {
-    const void* params;        // per pair: origin, 1 / cell edge, dimensions
-    const int32_t* start;      // [n_pairs][ICP_GRID_CELLS + 1] first sorted position of every cell
-    const float* sorted_prep;  // [ref_rows_total][4] {b, |b|^2} in cell order (per pair, from the pair's first target row)
-    const int32_t* sorted_idx; // [ref_rows_total] original target index of every sorted record
+    GridParam* params;    // per pair: origin, 1 / cell edge, dimensions
+    int32_t* start;       // [n_pairs][ICP_GRID_CELLS + 1] first sorted position of every cell (while building: the cell counts)
+    float* sorted_prep;   // [ref_rows_total][4] {b, |b|^2} in cell order (per pair, from the pair's first target row)
+    int32_t* sorted_idx;  // [ref_rows_total] original target index of every sorted record
+    int32_t* cursor;      // [n_pairs][ICP_GRID_CELLS] scatter cursors; only icp_grid_build uses these two
+    int32_t* cell_of;     // [ref_rows_total]
 };
 
-int64_t icp_grid_workspace_floats(int64_t ref_rows_total, int32_t n_pairs);
-void icp_grid_carve(int64_t ref_rows_total, int32_t n_pairs, float* work, IcpGrid* out);  // the pointers icp_grid_build fills
+// The grid's share of a workspace: a pure function of (sizes, where cv stands), so a later call of the same run finds the grid
+// an earlier one built (scream_icp_p2p_range).  On a Carver with a null base it only measures.
+void icp_grid_carve(Carver& cv, int64_t ref_rows_total, int32_t n_pairs, IcpGrid* out);
 int icp_grid_build(const float* ref_m, const float* ref_prep, const int32_t* r_row0, const int32_t* r_len, int32_t n_pairs,
-                   int32_t max_r_len, int64_t ref_rows_total, float radius, float* work, IcpGrid* out, hipStream_t st);
+                   int32_t max_r_len, float radius, const IcpGrid& grid, hipStream_t st);
 // nn_search.hip: ref_prep[row] = {b / s, |b / s|^2} (the brute-force search's own preparation) and the padding fill
 int nn_prepare_targets(const float* ref, const int32_t* r_row0, const int32_t* r_len, const float* s, int32_t n_pairs,
                        int32_t max_r_len, float* ref_prep, hipStream_t st);

@@ -1,4 +1,4 @@
-// Radius-limited nearest neighbour for the ICP loop (scream_icp_p2p, kabsch.hip) on a uniform grid over the TARGET cloud.
+// Radius-limited nearest neighbour for the ICP loop (scream_icp_p2p, icp_p2p.hip) on a uniform grid over the TARGET cloud.
 //
 // open3d's registration_icp, which the reference calls after every prediction (evaluate_3d_match.py:106-119,
 // evaluate_kitti.py:63-76), only ever uses correspondences closer than max_correspondence_distance, and the target cloud does
@@ -12,8 +12,8 @@
 // below the threshold lies in the 27 cells (the 1 % margin on h is four orders of magnitude above the rounding of the
 // cell arithmetic and of the distance).  Where no target is inside the radius the brute-force search still returns the
 // global nearest neighbour with valid = 0; this one returns idx = -1, dmin = inf, valid = 0 -- the ICP update reads
-// neither for such a point (icp_store_partial, kabsch.hip: valid correspondences only).
-// The search itself (grid_search_point, icp_grid.h) is called from icp_iter_kernel (kabsch.hip), which does a whole iteration.
+// neither for such a point (icp_store_partial, icp_p2p.hip: valid correspondences only).
+// The search itself (grid_search_point, icp_grid.h) is called from icp_iter_kernel (icp_p2p.hip), which does a whole iteration.
 //
 // Build, once per scream_icp_p2p call: bounding box per pair -> grid parameters (the cell edge grows by 2^(1/3) until the
 // grid fits ICP_GRID_CELLS cells: correct for any h >= the radius, only more candidates) -> count -> exclusive scan ->
@@ -140,57 +140,29 @@ __global__ __launch_bounds__(256) void grid_scatter_kernel(const float* __restri
 
 namespace scream_internal {
 
-int64_t icp_grid_workspace_floats(int64_t ref_rows_total, int32_t n_pairs) {
-    // params (8) + count/start (CELLS + 1) + cursor (CELLS) per pair; cell_of (1) + sorted record (4) + sorted index (1) per target
-    return (int64_t)n_pairs * (8 + 2 * (int64_t)ICP_GRID_CELLS + 1) + ref_rows_total * 6 + 5 * 64;
-}
-
-// where the grid of a workspace lives: a pure function of (sizes, work), so a later call of the same run finds the grid an
-// earlier one built (scream_icp_p2p_range)
-struct GridCarve {
-    GridParam* gp;
-    int32_t *count, *cursor, *cell_of, *sorted_idx;
-    float* sorted_prep;
-};
-static GridCarve carve_grid(int64_t ref_rows_total, int32_t n_pairs, float* work) {
-    float* w = work;
-    auto take = [&](int64_t n) { float* r = w; w += (n + 63) / 64 * 64; return r; };
-    GridCarve c;
-    c.gp = reinterpret_cast<GridParam*>(take((int64_t)n_pairs * 8));
-    c.count = reinterpret_cast<int32_t*>(take((int64_t)n_pairs * (ICP_GRID_CELLS + 1)));
-    c.cursor = reinterpret_cast<int32_t*>(take((int64_t)n_pairs * ICP_GRID_CELLS));
-    c.cell_of = reinterpret_cast<int32_t*>(take(ref_rows_total));
-    c.sorted_prep = take(ref_rows_total * 4);
-    c.sorted_idx = reinterpret_cast<int32_t*>(take(ref_rows_total));
-    return c;
-}
-
-void icp_grid_carve(int64_t ref_rows_total, int32_t n_pairs, float* work, IcpGrid* out) {
-    const GridCarve c = carve_grid(ref_rows_total, n_pairs, work);
-    out->params = c.gp;
-    out->start = c.count;
-    out->sorted_prep = c.sorted_prep;
-    out->sorted_idx = c.sorted_idx;
+void icp_grid_carve(Carver& cv, int64_t ref_rows_total, int32_t n_pairs, IcpGrid* out) {
+    out->params = cv.take<GridParam>(n_pairs);
+    out->start = cv.take<int32_t>((int64_t)n_pairs * (ICP_GRID_CELLS + 1));
+    out->cursor = cv.take<int32_t>((int64_t)n_pairs * ICP_GRID_CELLS);
+    out->cell_of = cv.take<int32_t>(ref_rows_total);
+    out->sorted_prep = cv.take<float>(ref_rows_total * 4);
+    out->sorted_idx = cv.take<int32_t>(ref_rows_total);
 }
 
 int icp_grid_build(const float* ref_m, const float* ref_prep, const int32_t* r_row0, const int32_t* r_len, int32_t n_pairs,
-                   int32_t max_r_len, int64_t ref_rows_total, float radius, float* work, IcpGrid* out, hipStream_t st) {
-    const GridCarve cv = carve_grid(ref_rows_total, n_pairs, work);
-    GridParam* gp = cv.gp;
-    int32_t *count = cv.count, *cursor = cv.cursor, *cell_of = cv.cell_of, *sorted_idx = cv.sorted_idx;
-    float* sorted_prep = cv.sorted_prep;
-    icp_grid_carve(ref_rows_total, n_pairs, work, out);
+                   int32_t max_r_len, float radius, const IcpGrid& g, hipStream_t st) {
+    int32_t* count = g.start;  // counts first; the scan turns them into cell starts in place
     hipError_t e = hipMemsetAsync(count, 0, sizeof(int32_t) * (size_t)n_pairs * (ICP_GRID_CELLS + 1), st);
     if (e != hipSuccess) return (int)e;
-    grid_params_kernel<<<dim3(n_pairs), dim3(256), 0, st>>>(ref_m, r_row0, r_len, radius * 1.01f, gp);
+    grid_params_kernel<<<dim3(n_pairs), dim3(256), 0, st>>>(ref_m, r_row0, r_len, radius * 1.01f, g.params);
     SCREAM_LAUNCH_CHECK();
     if (max_r_len > 0) {
         const dim3 grid((max_r_len + 255) / 256, n_pairs);
-        grid_count_kernel<<<grid, dim3(256), 0, st>>>(ref_m, r_row0, r_len, gp, count, cell_of);
+        grid_count_kernel<<<grid, dim3(256), 0, st>>>(ref_m, r_row0, r_len, g.params, count, g.cell_of);
         SCREAM_LAUNCH_CHECK();
-        grid_scan_kernel<<<dim3(n_pairs), dim3(1024), 0, st>>>(gp, count, cursor);
+        grid_scan_kernel<<<dim3(n_pairs), dim3(1024), 0, st>>>(g.params, count, g.cursor);
         SCREAM_LAUNCH_CHECK();
-        grid_scatter_kernel<<<grid, dim3(256), 0, st>>>(ref_prep, r_row0, r_len, cell_of, cursor, sorted_prep, sorted_idx);
+        grid_scatter_kernel<<<grid, dim3(256), 0, st>>>(ref_prep, r_row0, r_len, g.cell_of, g.cursor, g.sorted_prep, g.sorted_idx);
         SCREAM_LAUNCH_CHECK();
     }
     return 0;

@@ -1,6 +1,6 @@
 // Point-to-point ICP of RAW scans in float64 (scream_icp_raw_range / scream_icp_raw_nn): the pose refinement that
 // datasets/kitti.py:105-126 runs with open3d.registration_icp on the unvoxelised clouds (two scans of ~120 k points spanning
-// +-80 m, radius 0.2 m) before anything is voxelised.  scream_icp_p2p (kabsch.hip + icp_grid.hip) selects with the fp32 expanded
+// +-80 m, radius 0.2 m) before anything is voxelised.  scream_icp_p2p (icp_p2p.hip + icp_grid.hip) selects with the fp32 expanded
 // form and bins into a dense grid capped at 2^17 cells; neither holds at this extent.  Here every step is ONE IEEE float64
 // operation in a fixed order (this file is compiled with -ffp-contract=off), and the grid is sparse.
 //

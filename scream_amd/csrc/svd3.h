@@ -1,5 +1,5 @@
-// The float64 3x3 singular value decomposition shared by the pose solves (kabsch.hip: the A9 solve and the ICP update of
-// scream_icp_p2p; icp_raw.hip: the update of scream_icp_raw): a one-sided (Hestenes) Jacobi sweep held entirely in registers.
+// The float64 3x3 singular value decomposition shared by the pose solves (kabsch.hip: the A9 solve; icp_p2p.hip: the ICP update
+// of scream_icp_p2p; icp_raw.hip: the update of scream_icp_raw): a one-sided (Hestenes) Jacobi sweep held entirely in registers.
 // Every file that includes this is compiled with -ffp-contract=off.  tests/pose_ref.py (jacobi_svd3) restates it.
 #pragma once
 #include <math.h>

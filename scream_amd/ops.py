@@ -597,21 +597,33 @@ def point_loss(src_pred: torch.Tensor, src: torch.Tensor, src_row0, src_len, rot
 
 
 def icp_p2p(src, ref, src_row0, src_len, ref_row0, ref_len, s, c, T_init, max_src_len: int, max_ref_len: int,
-            max_corr_dist: float, max_iter: int = 30, rel_fitness: float = 1e-6, rel_rmse: float = 1e-6):
-    """Batched point-to-point ICP (scream_icp_p2p).  Returns (T [n,4,4], fitness_rmse [n,2], iters int32 [n])."""
+            max_corr_dist: float, max_iter: int = 30, rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, search: str = "grid"):
+    """Batched point-to-point ICP (scream_icp_p2p).  Returns (T [n,4,4], fitness_rmse [n,2], iters int32 [n]).
+    search="brute": the yardstick of the tests and of tools/icp_bench.py (scream_icp_p2p_brute_range), the same bits, slower."""
     lib = _lib.load()
+    range_fn, range_name = _icp_range_fn(lib, search)
     n_pairs = s.shape[0]
     dev = src.device
     T = T_init.detach().clone().contiguous().float()
     fr = torch.empty(n_pairs, 2, device=dev, dtype=torch.float32)
     iters = torch.empty(n_pairs, device=dev, dtype=torch.int32)
     ws = _icp_workspace(lib, src, ref, n_pairs)
-    check(lib.scream_icp_p2p(_p(src), _p(ref), _p(src_row0, torch.int32), _p(src_len, torch.int32),
-                             _p(ref_row0, torch.int32), _p(ref_len, torch.int32), _p(s), _p(c), n_pairs, max_src_len,
-                             max_ref_len, src.shape[0], ref.shape[0], float(max_corr_dist), int(max_iter),
-                             float(rel_fitness), float(rel_rmse), _p(T), _p(fr), _p(iters, torch.int32),
-                             ws.data_ptr(), ws.numel(), _stream()), "scream_icp_p2p")
+    args = (_p(src), _p(ref), _p(src_row0, torch.int32), _p(src_len, torch.int32), _p(ref_row0, torch.int32),
+            _p(ref_len, torch.int32), _p(s), _p(c), n_pairs, max_src_len, max_ref_len, src.shape[0], ref.shape[0],
+            float(max_corr_dist), int(max_iter), float(rel_fitness), float(rel_rmse), _p(T), _p(fr), _p(iters, torch.int32))
+    if search == "grid":
+        check(lib.scream_icp_p2p(*args, ws.data_ptr(), ws.numel(), _stream()), "scream_icp_p2p")
+    else:  # the whole schedule, as scream_icp_p2p enqueues it
+        check(range_fn(*args, 0, int(max_iter) + 2, None, ws.data_ptr(), ws.numel(), _stream()), range_name)
     return T, fr, iters
+
+
+def _icp_range_fn(lib, search: str):
+    """(C function, its name) that enqueues a piece of an ICP run with this search."""
+    if search not in ("grid", "brute"):
+        raise ValueError('search must be "grid" or "brute", not %r' % (search,))
+    name = "scream_icp_p2p_range" if search == "grid" else "scream_icp_p2p_brute_range"
+    return getattr(lib, name), name
 
 
 def _icp_workspace(lib, src, ref, n_pairs: int) -> torch.Tensor:
@@ -680,8 +692,9 @@ class IcpRun(PiecewiseRun):
     holds the refined transform of every pair whose flag is set.  Results are those of icp_p2p whatever the piece sizes."""
 
     def __init__(self, src, ref, src_row0, src_len, ref_row0, ref_len, s, c, T_init, max_src_len: int, max_ref_len: int,
-                 max_corr_dist: float, max_iter: int, rel_fitness: float = 1e-6, rel_rmse: float = 1e-6):
+                 max_corr_dist: float, max_iter: int, rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, search: str = "grid"):
         self.lib = _lib.load()
+        self._fn, self._fn_name = _icp_range_fn(self.lib, search)  # one search for the whole run
         n = s.shape[0]
         dev = src.device
         self.max_iter = int(max_iter)
@@ -699,5 +712,5 @@ class IcpRun(PiecewiseRun):
     launches_left = PiecewiseRun.steps_left
 
     def _enqueue(self, begin: int, end: int) -> None:
-        check(self.lib.scream_icp_p2p_range(*self._args, begin, end, _p(self.flags, torch.int32), self.ws.data_ptr(), self.ws.numel(),
-                                            _stream()), "scream_icp_p2p_range")
+        check(self._fn(*self._args, begin, end, _p(self.flags, torch.int32), self.ws.data_ptr(), self.ws.numel(), _stream()),
+              self._fn_name)

@@ -1,4 +1,4 @@
-"""Reference and yardstick of the ICP loop (scream_icp_p2p: icp_pose_step + icp_store_partial of csrc/kabsch.hip), in plain numpy.
+"""Reference and yardstick of the ICP loop (scream_icp_p2p: icp_pose_step + icp_store_partial of csrc/icp_p2p.hip), in plain numpy.
 Nothing here imports scream_amd or touches a GPU; tests/test_icp_step_ref_host.py holds this file on the CPU before
 tests/test_gpu_icp_step.py holds the kernels with it.
 

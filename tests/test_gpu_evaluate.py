@@ -128,11 +128,11 @@ def test_gpu_icp_vs_oracle_loop():
 
 
 @pytest.mark.parametrize("kind", ["3dmatch", "kitti"])
-def test_gpu_icp_grid_search_equals_brute_force_bitwise(kind, monkeypatch):
+def test_gpu_icp_grid_search_equals_brute_force_bitwise(kind):
     """The ICP loop looks for correspondences on a uniform grid over the (fixed) target cloud (csrc/icp_grid.hip).  Wherever
     the brute-force search of nn_search.hip reports a valid correspondence the grid reports the same index and the same
     distance bit for bit, so whole ICP runs -- poses, fitness, RMSE, iteration counts -- are IDENTICAL to runs with
-    SCREAM_ICP_BRUTE=1, on 3DMatch-size pairs (radius 0.1 m, 30 iterations, incl. a one-point target and a source far from
+    search="brute", on 3DMatch-size pairs (radius 0.1 m, 30 iterations, incl. a one-point target and a source far from
     its target) and on KITTI-size pairs (13-16 k points, whose extent makes the grid coarsen its cells)."""
     from scream_amd import ops
     from scream_amd.packing import PackedBatch
@@ -168,11 +168,8 @@ def test_gpu_icp_grid_search_equals_brute_force_bitwise(kind, monkeypatch):
     tgt_row0 = (batch.tgt_row0 - batch.rows_src).contiguous()
     args = (batch.xyz[: batch.rows_src], batch.xyz[batch.rows_src:], batch.src_row0, batch.src_len_dev, tgt_row0,
             batch.tgt_len_dev, s, c, T0, max(batch.src_len), max(batch.tgt_len), radius, iters)
-    monkeypatch.delenv("SCREAM_ICP_BRUTE", raising=False)
     got = ops.icp_p2p(*args)
-    monkeypatch.setenv("SCREAM_ICP_BRUTE", "1")
-    want = ops.icp_p2p(*args)
-    monkeypatch.delenv("SCREAM_ICP_BRUTE", raising=False)
+    want = ops.icp_p2p(*args, search="brute")
     for a, b in zip(got, want):
         assert torch.equal(a, b), (a, b)
     fit = got[1][:, 0].cpu().numpy()

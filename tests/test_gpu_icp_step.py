@@ -1,4 +1,4 @@
-"""The ICP loop on the MI355X (scream_icp_p2p: icp_pose_step + icp_store_partial of csrc/kabsch.hip) against the float64 loop of
+"""The ICP loop on the MI355X (scream_icp_p2p: icp_pose_step + icp_store_partial of csrc/icp_p2p.hip) against the float64 loop of
 tests/icp_step_ref.py: the chunk-partial sums at their group boundaries, the expanded covariance, the centroid denominators, the
 composition dT . T, both parities of the buffers, the freeze of stopped pairs, the stop rules, empty and partnerless sources, and
 frames 30 m and 300 m from the origin.
@@ -55,20 +55,25 @@ def pack(clouds):
     return out, row0
 
 
-def gpu_icp(problems, max_iter, rel=1e-6, pieces=None):
-    """The problems as ONE call of ops.icp_p2p (pieces: through ops.IcpRun, that many launches at a time).  Returns numpy
-    (T [n,4,4] fp32, fitness [n] fp32, rmse [n] fp32, iters [n])."""
+def icp_args(problems, max_iter, rel):
+    """The positional arguments of ops.icp_p2p / ops.IcpRun for the problems as one packed call."""
     radius = problems[0][3]
     assert all(p[3] == radius for p in problems), "one call has one radius"
     src, s0 = pack([p[0] for p in problems])
     tgt, t0 = pack([p[1] for p in problems])
     ns, ms, k = [len(p[0]) for p in problems], [len(p[1]) for p in problems], len(problems)
-    args = (dev(src), dev(tgt), i32(s0), i32(ns), i32(t0), i32(ms), dev(np.ones(k, np.float32)), dev(np.zeros((k, 3), np.float32)),
+    return (dev(src), dev(tgt), i32(s0), i32(ns), i32(t0), i32(ms), dev(np.ones(k, np.float32)), dev(np.zeros((k, 3), np.float32)),
             dev(np.stack([p[2] for p in problems]).astype(np.float32)), max(ns), max(ms), radius, max_iter, rel, rel)
+
+
+def gpu_icp(problems, max_iter, rel=1e-6, pieces=None, search="grid"):
+    """The problems as ONE call of ops.icp_p2p (pieces: through ops.IcpRun, that many launches at a time).  Returns numpy
+    (T [n,4,4] fp32, fitness [n] fp32, rmse [n] fp32, iters [n])."""
+    args, k = icp_args(problems, max_iter, rel), len(problems)
     if pieces is None:
-        T, fr, iters = ops.icp_p2p(*args)
+        T, fr, iters = ops.icp_p2p(*args, search=search)
     else:
-        run = ops.IcpRun(*args)
+        run = ops.IcpRun(*args, search=search)
         while run.launches_left > 0:
             run.advance(pieces)
         T, fr, iters = run.T, run.fr, run.iters
@@ -243,7 +248,7 @@ def test_icp_degenerate_pair_between_two_ordinary_pairs(name):
 
 
 # ------------------------------------------------------------------------------------- batch independence and freeze
-def test_icp_pairs_of_one_batch_equal_their_own_calls(monkeypatch):
+def test_icp_pairs_of_one_batch_equal_their_own_calls():
     """Five pairs of different lengths and frames that stop after 2, 3, 1, 1 and 2 updates in one call: every output is bitwise that
     of the pair's own call (a stopped pair freezes while the others go on), on the grid path and on the brute-force path, which
     agree bit for bit."""
@@ -252,14 +257,67 @@ def test_icp_pairs_of_one_batch_equal_their_own_calls(monkeypatch):
         f64, yard = IR.icp_f64(*pb, 30), IR.icp_f32_storage(*pb, 30)
         assert_valid(f64, yard)
         assert f64["iters"] == yard["iters"] == want and IR.stop_rule_is_decided(f64)
-    monkeypatch.delenv("SCREAM_ICP_BRUTE", raising=False)
     together = gpu_icp(probs, 30)
     assert tuple(together[3]) == IR.BATCH_ITERS
     for p, pb in enumerate(probs):
         for a, b in zip(together, gpu_icp([pb], 30)):
             np.testing.assert_array_equal(a[p], b[0])
-    monkeypatch.setenv("SCREAM_ICP_BRUTE", "1")
-    brute = gpu_icp(probs, 30)
-    monkeypatch.delenv("SCREAM_ICP_BRUTE", raising=False)
+    brute = gpu_icp(probs, 30, search="brute")
     for a, b in zip(together, brute):
         np.testing.assert_array_equal(a, b)
+
+
+# ------------------------------------------------------------------------------------------- the workspace and its size
+WS_MARGIN = 264  # bytes of the big tensor on either side of the workspace; not a multiple of 256, so the slice starts unaligned
+
+
+def _range_call(search, args, ws, ws_bytes, outputs=None):
+    """One whole run through the C function itself with the caller's workspace pointer and size.  Returns (T, fr, iters)."""
+    from scream_amd import _lib
+    lib = _lib.load()
+    fn = {"grid": lib.scream_icp_p2p_range, "brute": lib.scream_icp_p2p_brute_range}[search]
+    src, tgt, s0, ns, t0, ms, s, c, T0, max_n, max_m, radius, max_iter, rel_f, rel_r = args
+    k = s.shape[0]
+    if outputs is None:
+        outputs = (T0.clone(), torch.empty(k, 2, device=DEV), torch.empty(k, dtype=torch.int32, device=DEV))
+    T, fr, iters = outputs
+    ptr = lambda t: t.data_ptr()
+    _lib.check(fn(ptr(src), ptr(tgt), ptr(s0), ptr(ns), ptr(t0), ptr(ms), ptr(s), ptr(c), k, max_n, max_m, src.shape[0], tgt.shape[0],
+                  float(radius), int(max_iter), float(rel_f), float(rel_r), ptr(T), ptr(fr), ptr(iters), 0, int(max_iter) + 2, None,
+                  ws, ws_bytes, torch.cuda.current_stream().cuda_stream), "scream_icp_p2p_%srange" % ("brute_" if search == "brute" else ""))
+    return T, fr, iters
+
+
+@pytest.mark.parametrize("search", ["grid", "brute"])
+def test_icp_run_stays_inside_exactly_the_workspace_it_asks_for(search):
+    """A run given exactly scream_icp_workspace_bytes bytes, unaligned, in the middle of a larger tensor: the bytes around it keep
+    their pattern, what the workspace held before (zeros, 0xFF) changes no output bit, the outputs are those of ops.icp_p2p, and
+    one byte less is refused before anything is enqueued.  Three pairs with source lengths on both sides of a 256-row chunk
+    (257, 40, 300) in one call, and a call whose only source is empty; max_iter = 5."""
+    from scream_amd import _lib
+    first, last = IR.degenerate_neighbours()
+    degenerate = {nm: pb for nm, pb, _ in IR.degenerate_problems()}
+    for problems in ([first, degenerate["one_corr"], last], [degenerate["empty"]]):
+        args = icp_args(problems, 5, 1e-6)
+        need = _lib.load().scream_icp_workspace_bytes(args[0].shape[0], args[1].shape[0], len(problems))
+        assert need > 0
+        want = ops.icp_p2p(*args, search=search)
+        runs = []
+        for fill in (0x00, 0xFF):
+            big = torch.full((WS_MARGIN + need + WS_MARGIN,), fill, dtype=torch.uint8, device=DEV)
+            runs.append(_range_call(search, args, big.data_ptr() + WS_MARGIN, need))
+            torch.cuda.synchronize()
+            assert bool((big[:WS_MARGIN] == fill).all()) and bool((big[WS_MARGIN + need:] == fill).all()), (search, fill)
+        for got in runs:
+            for a, b in zip(got, want):
+                assert torch.equal(a, b), (search, a, b)
+        # one byte short: SCREAM_EINVAL, and nothing was enqueued -- the outputs keep what they held
+        outputs = (args[8].clone(), torch.full((len(problems), 2), -7.0, device=DEV), torch.full((len(problems),), -7, dtype=torch.int32, device=DEV))
+        before = [o.clone() for o in outputs]
+        big = torch.zeros(WS_MARGIN + need + WS_MARGIN, dtype=torch.uint8, device=DEV)
+        with pytest.raises(_lib.ScreamHipError, match="SCREAM_EINVAL"):
+            _range_call(search, args, big.data_ptr() + WS_MARGIN, need - 1, outputs)
+        torch.cuda.synchronize()
+        for a, b in zip(outputs, before):
+            assert torch.equal(a, b)
+        assert not bool(big.any())

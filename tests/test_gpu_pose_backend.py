@@ -411,13 +411,13 @@ def test_transformation_error_clamps_give_exactly_0_and_180_degrees():
 
 
 # ------------------------------------------------------------------------------------------- the search inside ICP
-def _icp(src, tgt, radius, max_iter):
+def _icp(src, tgt, radius, max_iter, search="grid"):
     n, m = len(src), len(tgt)
     return ops.icp_p2p(dev(src), dev(tgt), i32([0]), i32([n]), i32([0]), i32([m]), dev(np.ones(1, np.float32)), dev(np.zeros((1, 3), np.float32)),
-                       dev(np.eye(4, dtype=np.float32)[None]), n, m, radius, max_iter)
+                       dev(np.eye(4, dtype=np.float32)[None]), n, m, radius, max_iter, search=search)
 
 
-def test_icp_grid_search_on_a_lattice_ties_and_points_at_the_radius(monkeypatch):
+def test_icp_grid_search_on_a_lattice_ties_and_points_at_the_radius():
     """A metric-frame lattice problem (s = 1, c = 0, T0 = I, radius 0.5): sources with 8 equidistant targets, sources at exactly the
     radius from their only neighbour (d^2 == thresh: not a correspondence).  Without an update the fitness is the exact count and
     the RMSE the exact value; with updates the whole run is bit for bit that of the brute-force search (a tie resolved differently
@@ -425,22 +425,15 @@ def test_icp_grid_search_on_a_lattice_ties_and_points_at_the_radius(monkeypatch)
     src, tgt, radius = PR.icp_lattice_problem()
     cnt, rmse = PR.icp_lattice_ref(src, tgt, radius)
     for brute in (False, True):
-        if brute:
-            monkeypatch.setenv("SCREAM_ICP_BRUTE", "1")
-        else:
-            monkeypatch.delenv("SCREAM_ICP_BRUTE", raising=False)
-        T, fr, iters = _icp(src, tgt, radius, 0)
+        T, fr, iters = _icp(src, tgt, radius, 0, search="brute" if brute else "grid")
         fr = fr.cpu().numpy()[0]
         assert fr[0] == np.float32(cnt / len(src)), (brute, fr, cnt)
         assert abs(float(fr[1]) - rmse) <= np.spacing(np.float32(rmse)), (brute, fr, rmse)
         np.testing.assert_array_equal(T.cpu().numpy()[0], np.eye(4, dtype=np.float32))
         assert int(iters[0]) == 0
     for max_iter in (1, 5):
-        monkeypatch.delenv("SCREAM_ICP_BRUTE", raising=False)
         got = _icp(src, tgt, radius, max_iter)
-        monkeypatch.setenv("SCREAM_ICP_BRUTE", "1")
-        want = _icp(src, tgt, radius, max_iter)
-        monkeypatch.delenv("SCREAM_ICP_BRUTE", raising=False)
+        want = _icp(src, tgt, radius, max_iter, search="brute")
         for a, b in zip(got, want):
             assert torch.equal(a, b), (max_iter, a, b)
         assert 1 <= int(got[2][0]) <= max_iter

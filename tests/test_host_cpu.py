@@ -54,6 +54,41 @@ def test_host_side_argument_checks_need_no_gpu():
     assert lib.scream_nn_search(*([None] * 7), 1, 1, 1, 128, 128, 0.1, *([None] * 6)) == -1
 
 
+def test_library_sources_never_read_the_environment_and_the_icp_yardstick_has_a_name():
+    """The library's behaviour is a function of its arguments: no source or header calls getenv, and the brute-force yardstick of
+    the ICP is an entry point of its own with the arguments of scream_icp_p2p_range."""
+    for d in (os.path.join(REPO, "scream_amd", "csrc"), os.path.join(REPO, "include")):
+        files = sorted(os.listdir(d))
+        assert files
+        for f in files:
+            assert "getenv" not in open(os.path.join(d, f)).read(), f
+    assert "icp_p2p.hip" in os.listdir(os.path.join(REPO, "scream_amd", "csrc"))
+    assert "scream_icp_p2p_brute_range" in _header_functions()
+    assert _lib.SIGNATURES["scream_icp_p2p_brute_range"] == _lib.SIGNATURES["scream_icp_p2p_range"]
+    text = open(os.path.join(REPO, "include", "scream_hip.h")).read()
+    params = [re.search(r"\bint %s\((.*?)\);" % n, text, flags=re.S).group(1).split() for n in ("scream_icp_p2p_range", "scream_icp_p2p_brute_range")]
+    assert params[0] == params[1] and len(params[0]) > 50  # the same declaration, token for token
+
+
+# scream_icp_workspace_bytes of the commit before the carve became the size (a hand-written formula + 16 KiB), same shapes
+ICP_WS_SHAPES = [(0, 0, 0), (0, 0, 1), (128, 128, 1), (384, 512, 3), (16384 * 8, 16384 * 8, 8)]
+ICP_WS_BEFORE = [18192, 1067236, 1079524, 3209116, 21132720]
+
+
+def test_icp_workspace_bytes_is_monotone_and_no_larger_than_the_formula_it_replaced():
+    f = _lib.load().scream_icp_workspace_bytes
+    for (s, r, n), before in zip(ICP_WS_SHAPES, ICP_WS_BEFORE):
+        b = f(s, r, n)
+        assert 0 <= b <= before, ((s, r, n), b, before)
+        assert b % 256 == 0
+        for ds, dr, dn in ((1, 0, 0), (256, 0, 0), (0, 1, 0), (0, 256, 0), (0, 0, 1)):
+            assert f(s + ds, r + dr, n + dn) >= b, ((s, r, n), (ds, dr, dn))
+    for a, b in zip(ICP_WS_SHAPES, ICP_WS_SHAPES[1:]):  # the shapes themselves ascend in every argument
+        assert f(*a) <= f(*b)
+    for bad in ((-1, 0, 0), (0, -1, 0), (0, 0, -1), (-128, 128, 1)):
+        assert f(*bad) == -1  # SCREAM_EINVAL
+
+
 def test_product_code_never_imports_the_oracle():
     for root, _, files in os.walk(os.path.join(REPO, "scream_amd")):
         for f in files:

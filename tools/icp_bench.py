@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time of the batched GPU ICP (scream_icp_p2p) with the target grid of csrc/icp_grid.hip against the brute-force search
-(SCREAM_ICP_BRUTE=1): 32 3DMatch-like pairs (radius 0.1 m, 30 iterations) and 8 KITTI-like pairs (radius 0.6 m, 200 iterations)."""
+(search="brute"): 32 3DMatch-like pairs (radius 0.1 m, 30 iterations) and 8 KITTI-like pairs (radius 0.6 m, 200 iterations)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -40,14 +40,11 @@ def case(kind):
             batch.tgt_len_dev, s, c, T0, max(batch.src_len), max(batch.tgt_len), radius, iters)
     out = {}
     for mode in ("grid", "brute"):
-        if mode == "brute": os.environ["SCREAM_ICP_BRUTE"] = "1"
-        else: os.environ.pop("SCREAM_ICP_BRUTE", None)
-        res = ops.icp_p2p(*args); torch.cuda.synchronize()
+        res = ops.icp_p2p(*args, search=mode); torch.cuda.synchronize()
         t0 = time.perf_counter(); n = 0
         while time.perf_counter() - t0 < 1.0:
-            res = ops.icp_p2p(*args); torch.cuda.synchronize(); n += 1
+            res = ops.icp_p2p(*args, search=mode); torch.cuda.synchronize(); n += 1
         out[mode] = ((time.perf_counter() - t0) / n * 1e3, res)
-    os.environ.pop("SCREAM_ICP_BRUTE", None)
     same = all(torch.equal(a, b) for a, b in zip(out["grid"][1], out["brute"][1]))
     it_ = out["grid"][1][2].float().mean().item()
     print("%-8s %2d pairs, mean %5.0f / %5.0f points, radius %.1f m, %.1f iterations on average: grid %.2f ms, brute force %.2f ms "
