@@ -637,28 +637,33 @@ __global__ __launch_bounds__(256) void skinny_reduce_kernel(const float* __restr
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 unsigned grid_for(int64_t n, int64_t per_block, int64_t cap) {
     int64_t g = (n + per_block - 1) / per_block;
     if (g > cap) g = cap;
     return (unsigned)(g < 1 ? 1 : g);
 }
 
-}  // namespace
-
-// ------------------------------------------------------------------------------------------------ C ABI
-extern "C" int64_t scream_wgrad_workspace_bytes(int64_t rows, int32_t N, int32_t K) {
-    if (rows < 0 || N <= 0 || K <= 0 || N % WG_T || K % WG_T) return -1;
-    if (rows == 0) return 0;
-    const int64_t per = wgrad_slice_rows(rows, N, K);
-    const int64_t slices = (rows + per - 1) / per;
-    return slices * ((int64_t)N * K + N) * (int64_t)sizeof(float);
+// THE row slices of a weight gradient and where their partial sums go: part [slices][N][K], then colpart [slices][N].  From a
+// null base it only measures.
+struct WgradWs {
+    int64_t per, slices, bytes;
+    float *part, *colpart;
+};
+WgradWs wgrad_carve(void* base, int64_t rows, int32_t N, int32_t K) {
+    WgradWs w;
+    w.per = wgrad_slice_rows(rows, N, K);
+    w.slices = rows > 0 ? (rows + w.per - 1) / w.per : 0;
+    Carver cv{base};
+    w.part = cv.take<float>(w.slices * N * K);
+    w.colpart = cv.take<float>(w.slices * N);
+    w.bytes = cv.used;
+    return w;
 }
 
-extern "C" int scream_gemm_wgrad_f32(const float* dY, int64_t ldy, const float* X, int64_t ldx, int64_t rows, int32_t N,
-                                     int32_t K, float* dW, int32_t accumulate, float* colsum, void* workspace,
-                                     int64_t workspace_bytes, void* stream) {
+// dW (+)= dY^T X with the row slices' partial products from Partial (the fp32-input or the split-operand kernel)
+template <auto Partial>
+int wgrad_run(const float* dY, int64_t ldy, const float* X, int64_t ldx, int64_t rows, int32_t N, int32_t K, float* dW,
+              int32_t accumulate, float* colsum, void* workspace, int64_t workspace_bytes, void* stream) {
     SCREAM_REQUIRE(dY && X && dW, SCREAM_EINVAL);
     SCREAM_REQUIRE(rows >= 0 && N > 0 && K > 0 && N % WG_T == 0 && K % WG_T == 0, SCREAM_EUNSUPPORTED);
     SCREAM_REQUIRE(ldy >= N && ldx >= K && ldy % 4 == 0 && ldx % 4 == 0 && aligned16(dY) && aligned16(X), SCREAM_EINVAL);
@@ -670,21 +675,41 @@ extern "C" int scream_gemm_wgrad_f32(const float* dY, int64_t ldy, const float* 
         }
         return 0;
     }
-    const int64_t need = scream_wgrad_workspace_bytes(rows, N, K);
-    SCREAM_REQUIRE(workspace && workspace_bytes >= need && aligned16(workspace), SCREAM_EINVAL);
-    const int64_t per = wgrad_slice_rows(rows, N, K);
-    const int64_t slices = (rows + per - 1) / per;
-    SCREAM_REQUIRE(slices <= 65535, SCREAM_EUNSUPPORTED);
-    float* part = static_cast<float*>(workspace);
-    float* colpart = colsum ? part + slices * (int64_t)N * K : nullptr;
+    const WgradWs w = wgrad_carve(workspace, rows, N, K);
+    SCREAM_REQUIRE(workspace && workspace_bytes >= w.bytes && aligned16(workspace), SCREAM_EINVAL);
+    SCREAM_REQUIRE(w.slices <= 65535, SCREAM_EUNSUPPORTED);
+    float* colpart = colsum ? w.colpart : nullptr;
     const int tiles = (N / WG_T) * (K / WG_T);
-    wgrad_partial_kernel<<<dim3(tiles, (unsigned)slices), dim3(256), 0, st>>>(dY, ldy, X, ldx, rows, N, K, per, part, colpart);
+    Partial<<<dim3(tiles, (unsigned)w.slices), dim3(256), 0, st>>>(dY, ldy, X, ldx, rows, N, K, w.per, w.part, colpart);
     SCREAM_LAUNCH_CHECK();
     const int64_t nk = (int64_t)N * K;
-    wgrad_reduce_kernel<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st>>>(part, (int)slices, nk, dW, accumulate, colpart, N,
-                                                                                 colsum);
+    wgrad_reduce_kernel<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st>>>(w.part, (int)w.slices, nk, dW, accumulate, colpart,
+                                                                                 N, colsum);
     SCREAM_LAUNCH_CHECK();
     return 0;
+}
+
+// THE workspace of the attention backward, a head block per entry: part [n_q_clouds][max_chunks][NH][KV_ELEMS], the chunk
+// partials, then dkv [n_q_clouds][NH][KV_ELEMS], their sums.  Returns the bytes; from a null base it only measures.
+int64_t attn_bwd_carve(void* base, int32_t n_q_clouds, int32_t max_chunks, float** part, float** dkv) {
+    Carver cv{base};
+    *part = cv.take<float>((int64_t)n_q_clouds * max_chunks * NH * KV_ELEMS);
+    *dkv = cv.take<float>((int64_t)n_q_clouds * NH * KV_ELEMS);
+    return cv.used;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------ C ABI
+extern "C" int64_t scream_wgrad_workspace_bytes(int64_t rows, int32_t N, int32_t K) {
+    if (rows < 0 || N <= 0 || K <= 0 || N % WG_T || K % WG_T) return -1;
+    return wgrad_carve(nullptr, rows, N, K).bytes;
+}
+
+extern "C" int scream_gemm_wgrad_f32(const float* dY, int64_t ldy, const float* X, int64_t ldx, int64_t rows, int32_t N,
+                                     int32_t K, float* dW, int32_t accumulate, float* colsum, void* workspace,
+                                     int64_t workspace_bytes, void* stream) {
+    return wgrad_run<wgrad_partial_kernel>(dY, ldy, X, ldx, rows, N, K, dW, accumulate, colsum, workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t scream_wgrad_split_workspace_bytes(int64_t rows, int32_t N, int32_t K) {
@@ -694,34 +719,9 @@ extern "C" int64_t scream_wgrad_split_workspace_bytes(int64_t rows, int32_t N, i
 extern "C" int scream_gemm_wgrad_split_f32(const float* dY, int64_t ldy, const float* X, int64_t ldx, int64_t rows, int32_t N,
                                            int32_t K, float* dW, int32_t accumulate, float* colsum, int32_t split,
                                            void* workspace, int64_t workspace_bytes, void* stream) {
-    SCREAM_REQUIRE(dY && X && dW, SCREAM_EINVAL);
     SCREAM_REQUIRE(split == SCREAM_SPLIT_BF3, SCREAM_EINVAL);
-    SCREAM_REQUIRE(rows >= 0 && N > 0 && K > 0 && N % WG_T == 0 && K % WG_T == 0, SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE(ldy >= N && ldx >= K && ldy % 4 == 0 && ldx % 4 == 0 && aligned16(dY) && aligned16(X), SCREAM_EINVAL);
-    hipStream_t st = as_stream(stream);
-    if (rows == 0) {  // an empty sum: dW (+)= 0
-        if (!accumulate) {
-            if (hipMemsetAsync(dW, 0, (size_t)N * K * sizeof(float), st) != hipSuccess) return SCREAM_EINVAL;
-            if (colsum && hipMemsetAsync(colsum, 0, (size_t)N * sizeof(float), st) != hipSuccess) return SCREAM_EINVAL;
-        }
-        return 0;
-    }
-    const int64_t need = scream_wgrad_split_workspace_bytes(rows, N, K);
-    SCREAM_REQUIRE(workspace && workspace_bytes >= need && aligned16(workspace), SCREAM_EINVAL);
-    const int64_t per = wgrad_slice_rows(rows, N, K);
-    const int64_t slices = (rows + per - 1) / per;
-    SCREAM_REQUIRE(slices <= 65535, SCREAM_EUNSUPPORTED);
-    float* part = static_cast<float*>(workspace);
-    float* colpart = colsum ? part + slices * (int64_t)N * K : nullptr;
-    const int tiles = (N / WG_T) * (K / WG_T);
-    wgrad_split_partial_kernel<SplitBf3><<<dim3(tiles, (unsigned)slices), dim3(256), 0, st>>>(dY, ldy, X, ldx, rows, N, K, per, part,
-                                                                                             colpart);
-    SCREAM_LAUNCH_CHECK();
-    const int64_t nk = (int64_t)N * K;
-    wgrad_reduce_kernel<<<dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st>>>(part, (int)slices, nk, dW, accumulate, colpart, N,
-                                                                                 colsum);
-    SCREAM_LAUNCH_CHECK();
-    return 0;
+    return wgrad_run<wgrad_split_partial_kernel<SplitBf3>>(dY, ldy, X, ldx, rows, N, K, dW, accumulate, colsum, workspace,
+                                                           workspace_bytes, stream);
 }
 
 extern "C" int scream_ln_fwd(const float* a, const float* b, const float* gamma, const float* beta, float* y, float* mean,
@@ -769,7 +769,8 @@ extern "C" int scream_ln_bwd(const float* dy, const float* a, const float* b, co
 
 extern "C" int64_t scream_attn_bwd_workspace_bytes(int32_t n_q_clouds, int32_t max_chunks) {
     if (n_q_clouds < 0 || max_chunks < 1) return -1;
-    return (int64_t)n_q_clouds * (max_chunks + 1) * NH * KV_ELEMS * (int64_t)sizeof(float);
+    float *part, *dkv;
+    return attn_bwd_carve(nullptr, n_q_clouds, max_chunks, &part, &dkv);
 }
 
 extern "C" int scream_attn_bwd(const float* Qf, int64_t ldq, int64_t q_rows, int64_t q_row_base, const float* O,
@@ -785,11 +786,10 @@ extern "C" int scream_attn_bwd(const float* Qf, int64_t ldq, int64_t q_rows, int
                    SCREAM_EINVAL);
     SCREAM_REQUIRE(n_q_clouds <= 65535, SCREAM_EUNSUPPORTED);
     if (n_q_clouds == 0) return 0;
-    SCREAM_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= scream_attn_bwd_workspace_bytes(n_q_clouds, max_chunks),
-                   SCREAM_EINVAL);
+    float *part, *dkv;
+    const int64_t need = attn_bwd_carve(workspace, n_q_clouds, max_chunks, &part, &dkv);
+    SCREAM_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= need, SCREAM_EINVAL);
     hipStream_t st = as_stream(stream);
-    float* part = static_cast<float*>(workspace);
-    float* dkv = part + (int64_t)n_q_clouds * max_chunks * NH * KV_ELEMS;
     attn_bwd_partial_kernel<<<dim3(max_chunks, n_q_clouds), dim3(512), 0, st>>>(Qf, ldq, q_row_base, O, dO, kv, cloud_row0, cloud_len,
                                                                                 q_cloud_begin, kv_cloud_offset, max_chunks, part);
     SCREAM_LAUNCH_CHECK();

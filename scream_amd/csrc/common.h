@@ -21,6 +21,12 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// what the entry points ask of a caller's pointer: 16 bytes for the dwordx4 accesses, 8 for arrays of doubles and of pointers,
+// 256 for the raw-scan ICP's workspace
+static inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static inline bool aligned256(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 255) == 0; }
+
 // ---- host helpers of the ops on packed clouds (the rows of many clouds back to back, row0 / len per cloud)
 static inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
 // blocks of 256 threads that cover the longest cloud of a call

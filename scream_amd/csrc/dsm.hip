@@ -158,7 +158,7 @@ extern "C" int scream_dsm_extract(const float* patch, const int32_t* p_row0, con
     const int side = grid_side(max_p_len);
     const GridWs<2> ws = grid_carve<2>(workspace, patch_rows_total, n_clouds, side);
     SCREAM_REQUIRE(workspace_bytes_given >= ws.bytes, SCREAM_EINVAL);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(workspace), SCREAM_EINVAL);
     const double R = (double)radius;
     hipStream_t st = as_stream(stream);
     const int rc = cell_grid_enqueue<2>(patch, p_row0, p_len, max_p_len, patch_rows_total, d_row0, d_len, max_d_len, dem_rows_total, n_clouds,

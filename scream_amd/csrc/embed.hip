@@ -159,7 +159,7 @@ int pe_embed_ln_launch(const float* xyz, const int32_t* tile_cloud, const float*
                        void* stream) {
     SCREAM_REQUIRE(xyz && tile_cloud && center && dim_t && emb_w && emb_b && gamma && beta && feats, SCREAM_EINVAL);
     SCREAM_REQUIRE(rows >= 0 && rows % SCREAM_ROW_TILE == 0, SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(feats) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(feats), SCREAM_EINVAL);
     if (rows == 0) return 0;
     const int64_t blocks = rows / 32;
     SCREAM_REQUIRE(blocks < (1ll << 31), SCREAM_EUNSUPPORTED);
@@ -190,7 +190,7 @@ extern "C" int scream_pe_embed(const float* xyz, const int32_t* tile_cloud, cons
                                const float* emb_w, const float* emb_b, float* z, int64_t rows, void* stream) {
     SCREAM_REQUIRE(xyz && tile_cloud && center && dim_t && emb_w && emb_b && z, SCREAM_EINVAL);
     SCREAM_REQUIRE(rows >= 0 && rows % SCREAM_ROW_TILE == 0, SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(z) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(z), SCREAM_EINVAL);
     if (rows == 0) return 0;
     const int64_t blocks = rows / 32;
     SCREAM_REQUIRE(blocks < (1ll << 31), SCREAM_EUNSUPPORTED);

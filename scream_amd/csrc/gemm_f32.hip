@@ -218,8 +218,7 @@ extern "C" int scream_gemm_f32(const float* A, int64_t lda, const float* W, floa
     SCREAM_REQUIRE(A && W && C, SCREAM_EINVAL);
     SCREAM_REQUIRE(M >= 0 && M % BM == 0 && N > 0 && N % BN == 0 && K > 0 && K % 64 == 0, SCREAM_EUNSUPPORTED);
     SCREAM_REQUIRE(lda >= K && ldc >= N && lda % 4 == 0 && ldc % 4 == 0, SCREAM_EINVAL);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0 &&
-                       (reinterpret_cast<uintptr_t>(C) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(A) && aligned16(W) && aligned16(C), SCREAM_EINVAL);
     EpiArgs ep{n_act, bias, residual, ldr, gamma, beta, nullptr, nullptr, nullptr, nullptr, 0};
     hipStream_t st = as_stream(stream);
     switch (epilogue) {
@@ -236,7 +235,7 @@ extern "C" int scream_gemm_f32(const float* A, int64_t lda, const float* W, floa
         case SCREAM_EPI_RES_LN:
             SCREAM_REQUIRE(N == BN, SCREAM_EUNSUPPORTED);
             SCREAM_REQUIRE(residual && gamma && beta && ldr >= N && ldr % 4 == 0, SCREAM_EINVAL);
-            SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(residual) & 15) == 0, SCREAM_EINVAL);
+            SCREAM_REQUIRE(aligned16(residual), SCREAM_EINVAL);
             return launch<SCREAM_EPI_RES_LN>(A, lda, W, C, ldc, M, N, K, ep, st);
         default:
             return SCREAM_EINVAL;
@@ -250,9 +249,9 @@ extern "C" int scream_gemm_qkv_f32(const float* A, int64_t lda, const float* W, 
     SCREAM_REQUIRE(A && W && kv_partial && tile_cloud && cloud_row0 && cloud_len, SCREAM_EINVAL);
     SCREAM_REQUIRE(M >= 0 && M % BM == 0 && N > 0 && N % BN == 0 && K > 0 && K % 64 == 0, SCREAM_EUNSUPPORTED);
     SCREAM_REQUIRE((n_q == 0 || n_q == BN) && N == n_q + 2 * BN && row_base >= 0 && row_base % BM == 0, SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE(n_q == 0 || (Q && ldq >= n_q && ldq % 4 == 0 && (reinterpret_cast<uintptr_t>(Q) & 15) == 0), SCREAM_EINVAL);
+    SCREAM_REQUIRE(n_q == 0 || (Q && ldq >= n_q && ldq % 4 == 0 && aligned16(Q)), SCREAM_EINVAL);
     SCREAM_REQUIRE(lda >= K && lda % 4 == 0, SCREAM_EINVAL);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(W) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(A) && aligned16(W), SCREAM_EINVAL);
     EpiArgs ep{n_q, nullptr, nullptr, 0, nullptr, nullptr, kv_partial, tile_cloud, cloud_row0, cloud_len, row_base};
     return launch<SCREAM_EPI_QKV>(A, lda, W, Q, ldq, M, N, K, ep, as_stream(stream));
 }

@@ -377,7 +377,7 @@ extern "C" int scream_pack_w_split(const float* W, int32_t N, int32_t K, int32_t
     SCREAM_REQUIRE(W && packed, SCREAM_EINVAL);
     SCREAM_REQUIRE(split_args_ok(SplitArgs{split, 0, w_exp}), SCREAM_EINVAL);
     SCREAM_REQUIRE(N > 0 && N % 4 == 0 && K > 0 && K % XBK == 0, SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(W) & 15) == 0 && (reinterpret_cast<uintptr_t>(packed) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(W) && aligned16(packed), SCREAM_EINVAL);
     const int64_t threads = (int64_t)N * (K / XBK) * 4;
     const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
     if (split == SCREAM_SPLIT_H2)
@@ -409,8 +409,7 @@ extern "C" int scream_gemm_split_f32(const float* A, int64_t lda, const void* W_
     SCREAM_REQUIRE(split_args_ok(sa), SCREAM_EINVAL);
     SCREAM_REQUIRE(M >= 0 && M % SCREAM_ROW_TILE == 0 && N > 0 && N % XBN == 0 && K >= 64 && K % 64 == 0 && (K / 32 - 2) % 3 == 0, SCREAM_EUNSUPPORTED);  // K = 64 + 192 j: an EVEN number of k-tiles (stage = kt & 1), in groups of three after the first two
     SCREAM_REQUIRE(lda >= K && ldc >= N && lda % 4 == 0 && ldc % 4 == 0, SCREAM_EINVAL);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(W_packed) & 15) == 0 &&
-                       (reinterpret_cast<uintptr_t>(C) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(A) && aligned16(W_packed) && aligned16(C), SCREAM_EINVAL);
     if (int rc = check_layout(layout, lda, ldc, K, epilogue, n_act)) return rc;
     const bool af = layout & SCREAM_LAYOUT_A_FRAG;
     EpiArgs ep{n_act, bias, residual, ldr, gamma, beta, nullptr, nullptr, nullptr, nullptr, 0, (layout & SCREAM_LAYOUT_C_FRAG) ? 1 : 0};
@@ -429,7 +428,7 @@ extern "C" int scream_gemm_split_f32(const float* A, int64_t lda, const void* W_
         case SCREAM_EPI_RES_LN:
             SCREAM_REQUIRE(N == XBN, SCREAM_EUNSUPPORTED);
             SCREAM_REQUIRE(residual && gamma && beta && ldr >= N && ldr % 4 == 0, SCREAM_EINVAL);
-            SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(residual) & 15) == 0, SCREAM_EINVAL);
+            SCREAM_REQUIRE(aligned16(residual), SCREAM_EINVAL);
             return launch_split<SCREAM_EPI_RES_LN>(A, lda, W_packed, C, ldc, M, N, K, ep, st, af, sa);
         default:
             return SCREAM_EINVAL;
@@ -449,9 +448,9 @@ extern "C" int scream_gemm_qkv_split_f32(const float* A, int64_t lda, const void
     // N = n_q + 512 L: L key/value tile pairs; L > 1 (several layers' key/value projections of the same rows) only without queries
     SCREAM_REQUIRE((n_q == 0 || n_q == XBN) && N > n_q && (N - n_q) % (2 * XBN) == 0 && (n_q == 0 || N == n_q + 2 * XBN) && row_base >= 0 &&
                        row_base % SCREAM_ROW_TILE == 0, SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE(n_q == 0 || (Q && ldq >= n_q && ldq % 4 == 0 && (reinterpret_cast<uintptr_t>(Q) & 15) == 0), SCREAM_EINVAL);
+    SCREAM_REQUIRE(n_q == 0 || (Q && ldq >= n_q && ldq % 4 == 0 && aligned16(Q)), SCREAM_EINVAL);
     SCREAM_REQUIRE(lda >= K && lda % 4 == 0, SCREAM_EINVAL);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(W_packed) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(A) && aligned16(W_packed), SCREAM_EINVAL);
     SCREAM_REQUIRE(!(layout & SCREAM_LAYOUT_C_FRAG) || n_q == XBN, SCREAM_EUNSUPPORTED);
     if (int rc = check_layout(layout, lda, n_q ? ldq : SCREAM_D_MODEL, K, SCREAM_EPI_QKV, n_q ? n_q : SCREAM_D_MODEL)) return rc;
     EpiArgs ep{n_q, nullptr, nullptr, 0, nullptr, nullptr, kv_partial, tile_cloud, cloud_row0, cloud_len, row_base,

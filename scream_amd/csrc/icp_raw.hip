@@ -56,17 +56,21 @@ struct RawCarve {
     double* state;     // [n_pairs][2] fitness, rmse of the last evaluation
     double* part;      // [chunks_cap][RI_NP]
     f32x4* rec;        // [tgt_rows] sorted records
-    void* sort_ws;
+    void* sort_ws;     // where the voxel sort's buffers begin (no kernel reads it; the kernels take this struct by value)
+};
+struct RawSetup {
+    RawCarve cv;
+    Carve sort;
+    int64_t bytes;
 };
 
 inline int64_t chunks_cap(int64_t src_rows, int32_t n_pairs) { return src_rows / 256 + n_pairs + 1; }
-inline int64_t raw_workspace_bytes(int64_t src_rows, int64_t tgt_rows, int32_t n_pairs) {
-    return align256((int64_t)n_pairs * 8) + 5 * align256((int64_t)n_pairs * 4) + align256((int64_t)n_pairs * 16) +
-           align256(chunks_cap(src_rows, n_pairs) * RI_NP * 8) + align256(tgt_rows * 16) + workspace_bytes(tgt_rows, n_pairs);
-}
-inline RawCarve raw_carve(void* workspace, int64_t src_rows, int64_t tgt_rows, int32_t n_pairs) {
+// THE layout of a run: its own buffers, then the voxel sort's.  From a null base it only measures: `bytes` is what
+// scream_icp_raw_workspace_bytes reports and what both entry points ask for.
+inline RawSetup raw_carve(void* workspace, int64_t src_rows, int64_t tgt_rows, int32_t n_pairs) {
     Carver w{workspace};
-    RawCarve c;
+    RawSetup su;
+    RawCarve& c = su.cv;
     c.voxel = w.take<double>(n_pairs);
     c.status = w.take<int32_t>(n_pairs);
     c.done = w.take<int32_t>(n_pairs);
@@ -76,8 +80,10 @@ inline RawCarve raw_carve(void* workspace, int64_t src_rows, int64_t tgt_rows, i
     c.state = w.take<double>(2 * (int64_t)n_pairs);
     c.part = w.take<double>(chunks_cap(src_rows, n_pairs) * RI_NP);
     c.rec = w.take<f32x4>(tgt_rows);
-    c.sort_ws = w.take<char>(0);
-    return c;
+    su.sort = voxel_carve(w, tgt_rows, n_pairs);
+    c.sort_ws = su.sort.plan;
+    su.bytes = w.used;
+    return su;
 }
 
 __device__ __forceinline__ int raw_chunks(int n) { return n > 0 ? (n + 255) / 256 : 1; }  // an empty source keeps its block 0
@@ -371,32 +377,23 @@ __global__ __launch_bounds__(64) void raw_pose_kernel(RawCarve cv, int e, int32_
     }
 }
 
-struct RawSetup {
-    RawCarve cv;
-    Carve sort;
-};
-
-// carve the workspace; with `build`, enqueue the set-up: target grid, records, pair status
+// enqueue the set-up of a carved run: target grid, records, pair status
 int raw_setup(const float* src, const float* tgt, const int32_t* src_row0, const int32_t* src_len, const int32_t* tgt_row0,
               const int32_t* tgt_len, int32_t n_pairs, int32_t max_src_len, int32_t max_tgt_len, int64_t src_rows_total,
-              int64_t tgt_rows_total, double radius, void* workspace, bool build, int32_t* iters, int32_t* status_out, hipStream_t st,
-              RawSetup* out) {
-    out->cv = raw_carve(workspace, src_rows_total, tgt_rows_total, n_pairs);
-    out->sort = carve(out->cv.sort_ws, tgt_rows_total, n_pairs);
-    if (!build) return 0;
-    const RawCarve& cv = out->cv;
+              int64_t tgt_rows_total, double radius, const RawSetup& su, int32_t* iters, int32_t* status_out, hipStream_t st) {
+    const RawCarve& cv = su.cv;
     raw_fill_kernel<<<dim3((n_pairs + 255) / 256), dim3(256), 0, st>>>(cv.voxel, radius, n_pairs);
     SCREAM_LAUNCH_CHECK();
-    const int rc = voxel_sort_enqueue(tgt, tgt_row0, tgt_len, n_pairs, max_tgt_len, cv.voxel, tgt_rows_total, out->sort, st);
+    const int rc = voxel_sort_enqueue(tgt, tgt_row0, tgt_len, n_pairs, max_tgt_len, cv.voxel, tgt_rows_total, su.sort, st);
     if (rc != 0) return rc;
     raw_src_check_kernel<<<dim3(n_pairs), dim3(256), 0, st>>>(src, src_row0, src_len, max_src_len, src_rows_total, cv.src_ok);
     SCREAM_LAUNCH_CHECK();
-    raw_status_kernel<<<dim3(1), dim3(64), 0, st>>>(out->sort.plan, src_len, cv, radius, n_pairs, chunks_cap(src_rows_total, n_pairs),
+    raw_status_kernel<<<dim3(1), dim3(64), 0, st>>>(su.sort.plan, src_len, cv, radius, n_pairs, chunks_cap(src_rows_total, n_pairs),
                                                    iters, status_out);
     SCREAM_LAUNCH_CHECK();
     if (max_tgt_len > 0) {
-        raw_records_kernel<<<dim3((max_tgt_len + 255) / 256, n_pairs), dim3(256), 0, st>>>(tgt, out->sort.plan, out->sort.rows[0],
-                                                                                          out->sort.rows[1], cv.rec);
+        raw_records_kernel<<<dim3((max_tgt_len + 255) / 256, n_pairs), dim3(256), 0, st>>>(tgt, su.sort.plan, su.sort.rows[0],
+                                                                                          su.sort.rows[1], cv.rec);
         SCREAM_LAUNCH_CHECK();
     }
     return 0;
@@ -411,7 +408,7 @@ bool raw_args_ok(int32_t n_pairs, int32_t max_src_len, int32_t max_tgt_len, int6
 
 extern "C" int64_t scream_icp_raw_workspace_bytes(int64_t src_rows_total, int64_t tgt_rows_total, int32_t n_pairs) {
     if (!raw_args_ok(n_pairs, 0, 0, src_rows_total, tgt_rows_total)) return SCREAM_EINVAL;
-    return raw_workspace_bytes(src_rows_total, tgt_rows_total, n_pairs);
+    return raw_carve(nullptr, src_rows_total, tgt_rows_total, n_pairs).bytes;
 }
 
 extern "C" int scream_icp_raw_range(const float* src, const float* tgt, const int32_t* src_row0, const int32_t* src_len,
@@ -423,15 +420,16 @@ extern "C" int scream_icp_raw_range(const float* src, const float* tgt, const in
     SCREAM_REQUIRE(src && tgt && src_row0 && src_len && tgt_row0 && tgt_len && T && workspace, SCREAM_EINVAL);
     SCREAM_REQUIRE(raw_args_ok(n_pairs, max_src_len, max_tgt_len, src_rows_total, tgt_rows_total), SCREAM_EINVAL);
     SCREAM_REQUIRE(max_iter >= 0 && max_iter < (1 << 30) && it_begin >= 0 && it_end >= it_begin, SCREAM_EINVAL);
-    SCREAM_REQUIRE(workspace_bytes_given >= raw_workspace_bytes(src_rows_total, tgt_rows_total, n_pairs), SCREAM_EINVAL);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, SCREAM_EINVAL);
+    const RawSetup su = raw_carve(workspace, src_rows_total, tgt_rows_total, n_pairs);
+    SCREAM_REQUIRE(workspace_bytes_given >= su.bytes && aligned256(workspace), SCREAM_EINVAL);
     if (n_pairs == 0) return 0;
     SCREAM_REQUIRE(n_pairs <= 65535, SCREAM_EUNSUPPORTED);
     hipStream_t st = as_stream(stream);
-    RawSetup su;
-    const int rc = raw_setup(src, tgt, src_row0, src_len, tgt_row0, tgt_len, n_pairs, max_src_len, max_tgt_len, src_rows_total,
-                             tgt_rows_total, max_corr_dist, workspace, it_begin == 0, iters, nullptr, st, &su);
-    if (rc != 0) return rc;
+    if (it_begin == 0) {
+        const int rc = raw_setup(src, tgt, src_row0, src_len, tgt_row0, tgt_len, n_pairs, max_src_len, max_tgt_len, src_rows_total,
+                                 tgt_rows_total, max_corr_dist, su, iters, nullptr, st);
+        if (rc != 0) return rc;
+    }
     const dim3 chunks((max_src_len > 0 ? max_src_len + 255 : 256) / 256, n_pairs);
     const double r2 = max_corr_dist * max_corr_dist;
     // launch pair `it` = search under T_it, then evaluation it: stop, or T_{it+1} = dT . T_it.  Nothing here waits for the device.
@@ -457,14 +455,13 @@ extern "C" int scream_icp_raw_nn(const float* src, const float* tgt, const int32
                                  void* stream) {
     SCREAM_REQUIRE(src && tgt && src_row0 && src_len && tgt_row0 && tgt_len && T && idx && d2 && workspace, SCREAM_EINVAL);
     SCREAM_REQUIRE(raw_args_ok(n_pairs, max_src_len, max_tgt_len, src_rows_total, tgt_rows_total), SCREAM_EINVAL);
-    SCREAM_REQUIRE(workspace_bytes_given >= raw_workspace_bytes(src_rows_total, tgt_rows_total, n_pairs), SCREAM_EINVAL);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, SCREAM_EINVAL);
+    const RawSetup su = raw_carve(workspace, src_rows_total, tgt_rows_total, n_pairs);
+    SCREAM_REQUIRE(workspace_bytes_given >= su.bytes && aligned256(workspace), SCREAM_EINVAL);
     if (n_pairs == 0) return 0;
     SCREAM_REQUIRE(n_pairs <= 65535, SCREAM_EUNSUPPORTED);
     hipStream_t st = as_stream(stream);
-    RawSetup su;
     const int rc = raw_setup(src, tgt, src_row0, src_len, tgt_row0, tgt_len, n_pairs, max_src_len, max_tgt_len, src_rows_total,
-                             tgt_rows_total, radius, workspace, true, nullptr, status, st, &su);
+                             tgt_rows_total, radius, su, nullptr, status, st);
     if (rc != 0) return rc;
     if (max_src_len > 0) {
         raw_nn_kernel<<<dim3((max_src_len + 255) / 256, n_pairs), dim3(256), 0, st>>>(src, src_row0, su.sort.plan, su.sort.keys[0],

@@ -286,7 +286,7 @@ extern "C" int scream_nn_search(const float* query, const float* ref, const int3
     SCREAM_REQUIRE(n_pairs >= 0 && max_q_len >= 0 && max_r_len >= 0 && q_rows_total >= 0 && r_rows_total >= 0,
                    SCREAM_EINVAL);
     SCREAM_REQUIRE(n_pairs <= 65535, SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(ref_prep) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(ref_prep), SCREAM_EINVAL);
     if (n_pairs == 0 || q_rows_total == 0) return 0;
     hipStream_t st = as_stream(stream);
     const unsigned qblk = (unsigned)((q_rows_total + 255) / 256);

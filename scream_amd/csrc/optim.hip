@@ -97,9 +97,9 @@ extern "C" int scream_adam_step(const void* tensors, int32_t n_tensors, const in
                                 const float* grad_scale, const float* found_inf, double lr, double beta1, double beta2, double eps,
                                 void* stream) {
     SCREAM_REQUIRE(n_tensors >= 0 && n_chunks >= 0 && n_chunks <= INT32_MAX, SCREAM_EINVAL);
-    SCREAM_REQUIRE(state && (reinterpret_cast<uintptr_t>(state) & 7) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(state && aligned8(state), SCREAM_EINVAL);
     SCREAM_REQUIRE(n_chunks == 0 || (tensors && chunks && n_tensors > 0), SCREAM_EINVAL);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(tensors) & 7) == 0 && (reinterpret_cast<uintptr_t>(chunks) & 7) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned8(tensors) && aligned8(chunks), SCREAM_EINVAL);
     SCREAM_REQUIRE(lr >= 0.0 && lr < INFINITY && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && eps < INFINITY,
                    SCREAM_EINVAL);
     hipStream_t st = as_stream(stream);

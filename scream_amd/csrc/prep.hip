@@ -48,21 +48,20 @@ struct PrepWs {
     double* part_cen;   // [B][nchunk][3]   chunk sums of the normalised source (centre rule 0)
     double* aug;        // [raw_rows][3]    the augmented points
 };
-inline int64_t prep_workspace_bytes(int64_t raw_rows, int32_t n_pairs, int32_t max_len) {
-    const int64_t P = 2 * (int64_t)n_pairs * n_chunks(max_len);
-    return align256(P * 16 * 8) + align256(raw_rows * 24);
-}
-inline PrepWs prep_carve(void* workspace, int32_t n_pairs, int32_t max_len) {
-    const int64_t P = 2 * (int64_t)n_pairs * n_chunks(max_len);
-    double* w = reinterpret_cast<double*>(workspace);
+// THE layout of a call, each piece with the element count stated above.  From a null base it only measures: *bytes is what
+// scream_prep_pairs_workspace_bytes reports and what scream_prep_pairs asks for.
+inline PrepWs prep_carve(void* workspace, int64_t raw_rows, int32_t n_pairs, int32_t max_len, int64_t* bytes) {
+    const int64_t per_pair = (int64_t)n_pairs * n_chunks(max_len), per_cloud = 2 * per_pair;
+    Carver w{workspace};
     PrepWs ws;
-    ws.part_mean = w;
-    ws.part_reg = w + 3 * P;
-    ws.part_lo = w + 6 * P;
-    ws.part_hi = w + 9 * P;
-    ws.part_max = w + 12 * P;
-    ws.part_cen = w + 13 * P;
-    ws.aug = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + align256(P * 16 * 8));
+    ws.part_mean = w.take<double>(per_pair * 3);
+    ws.part_reg = w.take<double>(per_cloud * 3);
+    ws.part_lo = w.take<double>(per_cloud * 3);
+    ws.part_hi = w.take<double>(per_cloud * 3);
+    ws.part_max = w.take<double>(per_cloud);
+    ws.part_cen = w.take<double>(per_pair * 3);
+    ws.aug = w.take<double>(raw_rows * 3);
+    *bytes = w.used;
     return ws;
 }
 
@@ -532,7 +531,9 @@ inline bool loss_call_ok(const float* pred, const float* xyz, const float* rot, 
 
 extern "C" int64_t scream_prep_pairs_workspace_bytes(int64_t raw_rows, int32_t n_pairs, int32_t max_len) {
     if (raw_rows < 0 || raw_rows > INT32_MAX || n_pairs < 0 || max_len < 0 || max_len > raw_rows) return SCREAM_EINVAL;
-    return prep_workspace_bytes(raw_rows, n_pairs, max_len);
+    int64_t bytes;
+    prep_carve(nullptr, raw_rows, n_pairs, max_len, &bytes);
+    return bytes;
 }
 
 extern "C" int scream_prep_pairs(const void* raw, int32_t raw_is_f64, int64_t raw_rows, const int32_t* raw_row0, const int32_t* raw_len,
@@ -549,14 +550,14 @@ extern "C" int scream_prep_pairs(const void* raw, int32_t raw_is_f64, int64_t ra
     SCREAM_REQUIRE(max_len > 0 && raw && raw_row0 && raw_len && T && perturb && side && sample_id && cloud_row0 && xyz && center && rot &&
                        trans && s && c && T_aug && workspace,
                    SCREAM_EINVAL);
-    SCREAM_REQUIRE(workspace_bytes >= prep_workspace_bytes(raw_rows, n_pairs, max_len), SCREAM_EINVAL);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, SCREAM_EINVAL);
     PrepArgs A;
+    int64_t need;
+    A.ws = prep_carve(workspace, raw_rows, n_pairs, max_len, &need);
+    SCREAM_REQUIRE(workspace_bytes >= need && aligned16(workspace), SCREAM_EINVAL);
     A.raw = raw, A.raw_is_f64 = raw_is_f64 != 0, A.raw_rows = raw_rows, A.raw_row0 = raw_row0, A.raw_len = raw_len, A.max_len = max_len;
     A.T = T, A.perturb = perturb, A.side = side, A.noise_std = noise_std, A.seed = seed, A.sample_id = sample_id;
     A.mode = mode, A.center_rule = center_rule, A.cloud_row0 = cloud_row0, A.n_pairs = n_pairs, A.rows_total = rows_total;
     A.nchunk = n_chunks(max_len);
-    A.ws = prep_carve(workspace, n_pairs, max_len);
     hipStream_t st = as_stream(stream);
     const dim3 blk(PREP_CHUNK), per_pair(A.nchunk, n_pairs), per_cloud(A.nchunk, 2 * n_pairs);
     prep_mean_kernel<<<per_pair, blk, 0, st>>>(A);
@@ -576,7 +577,9 @@ extern "C" int scream_prep_pairs(const void* raw, int32_t raw_is_f64, int64_t ra
 
 extern "C" int64_t scream_l1_pairs_workspace_bytes(int32_t n_pairs, int32_t max_len) {
     if (n_pairs < 0 || max_len < 0) return SCREAM_EINVAL;
-    return align256((int64_t)n_pairs * n_chunks(max_len) * 8);
+    Carver w{nullptr};
+    w.take<double>((int64_t)n_pairs * n_chunks(max_len));  // one piece: the chunk sums
+    return w.used;
 }
 
 extern "C" int scream_l1_pairs_fwd(const float* pred, const float* xyz, const float* rot, const float* trans, const float* target,
@@ -586,7 +589,7 @@ extern "C" int scream_l1_pairs_fwd(const float* pred, const float* xyz, const fl
     SCREAM_REQUIRE(loss_call_ok(pred, xyz, rot, trans, target, cloud_row0, cloud_len, n_pairs, max_len, rows_src), SCREAM_EINVAL);
     SCREAM_REQUIRE(n_pairs <= 65535, SCREAM_EUNSUPPORTED);
     SCREAM_REQUIRE(loss_pair && loss && workspace && workspace_bytes >= scream_l1_pairs_workspace_bytes(n_pairs, max_len), SCREAM_EINVAL);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned8(workspace), SCREAM_EINVAL);
     LossArgs A = {pred, xyz, rot, trans, target, cloud_row0, cloud_len, n_pairs, max_len, n_chunks(max_len), rows_src};
     double* part = reinterpret_cast<double*>(workspace);
     hipStream_t st = as_stream(stream);

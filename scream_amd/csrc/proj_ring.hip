@@ -441,7 +441,7 @@ extern "C" int64_t scream_proj_image_bytes(int32_t N, int32_t split) {
 extern "C" int scream_pack_proj(const float* W, int32_t N, int32_t n_q, int32_t split, int32_t w_exp, void* image, void* stream) {
     SCREAM_REQUIRE(W && image && proj_split_ok(split), SCREAM_EINVAL);
     SCREAM_REQUIRE((n_q == 0 || n_q == SCREAM_D_MODEL) && N > n_q && (N - n_q) % 512 == 0, SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE(w_exp >= -60 && w_exp <= 60 && (reinterpret_cast<uintptr_t>(image) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(w_exp >= -60 && w_exp <= 60 && aligned16(image), SCREAM_EINVAL);
     const int S = N / 32;
     const dim3 grid(S * 16 * 64 / 256), block(256);
     if (split == SCREAM_SPLIT_H2)
@@ -466,8 +466,7 @@ extern "C" int scream_proj_qkv_f32(const float* x, const void* proj_image, float
     // are checked as well so that widening a range above cannot let them through silently
     const auto in126 = [](int e) { return e >= -126 && e <= 126; };
     SCREAM_REQUIRE(in126(a_exp + w_exp) && in126(v_exp - a_exp - w_exp) && in126(k_exp + v_exp), SCREAM_EINVAL);
-    SCREAM_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(proj_image) | reinterpret_cast<uintptr_t>(Q) |
-                     reinterpret_cast<uintptr_t>(kv_partial)) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(x) && aligned16(proj_image) && aligned16(Q) && aligned16(kv_partial), SCREAM_EINVAL);
     if (M == 0) return 0;
     ProjArgs pa;
     pa.x = x;

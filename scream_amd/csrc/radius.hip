@@ -179,7 +179,7 @@ inline int check_call(const void* src, const int32_t* s_row0, const int32_t* s_l
     SCREAM_REQUIRE(n_pairs <= 65535, SCREAM_EUNSUPPORTED);
     SCREAM_REQUIRE(src && s_row0 && s_len && tgt && t_row0 && t_len && T && out && workspace, SCREAM_EINVAL);
     SCREAM_REQUIRE(workspace_bytes_given >= grid_carve<3>(nullptr, t_rows, n_pairs, grid_side(max_t_len)).bytes, SCREAM_EINVAL);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(workspace), SCREAM_EINVAL);
     return 0;
 }
 

@@ -314,9 +314,23 @@ __global__ __launch_bounds__(256) void render_bwd_reduce_kernel(const float* __r
     dsrc[row * 3 + 2] = c;
 }
 
-int64_t range_bytes(int32_t n_pairs, int32_t V) { return align256((int64_t)n_pairs * V * 2 * 4); }
-int64_t key_bytes(int32_t n_pairs, int32_t V, int32_t w) { return (int64_t)n_pairs * V * 2 * w * w * 8; }
-int64_t partial_bytes(int32_t V, int64_t src_rows_total) { return (int64_t)V * src_rows_total * 3 * 4; }
+// THE layout of the workspace: range [n_pairs][V][2], which the backward reads where the forward left it, then the forward's keys
+// [n_pairs][V][2][w][w] or the backward's partial [V][src_rows_total][3].  From a null base it only measures.
+struct RenderWs {
+    uint32_t* range;
+    uint64_t* keys;
+    float* partial;
+    int64_t bytes;
+};
+RenderWs render_carve(void* base, int32_t n_pairs, int32_t V, int32_t w, int64_t src_rows_total, bool backward) {
+    Carver cv{base};
+    RenderWs r = {};
+    r.range = cv.take<uint32_t>((int64_t)n_pairs * V * 2);
+    if (backward) r.partial = cv.take<float>((int64_t)V * src_rows_total * 3);
+    else r.keys = cv.take<uint64_t>((int64_t)n_pairs * V * 2 * w * w);
+    r.bytes = cv.used;
+    return r;
+}
 
 float exp2_scale(float rho) { return (float)(-0.5 * (double)rho * (double)rho * 1.4426950408889634); }
 
@@ -328,8 +342,9 @@ bool bad_geometry(int32_t n_pairs, int32_t V, int32_t w, int64_t src_rows_total)
 
 extern "C" int64_t scream_render_workspace_bytes(int32_t n_pairs, int32_t n_views, int32_t w, int64_t src_rows_total) {
     if (bad_geometry(n_pairs, n_views, w, src_rows_total)) return SCREAM_EINVAL;
-    const int64_t kb = key_bytes(n_pairs, n_views, w), pb = partial_bytes(n_views, src_rows_total);
-    return range_bytes(n_pairs, n_views) + (kb > pb ? kb : pb);
+    const int64_t fwd = render_carve(nullptr, n_pairs, n_views, w, src_rows_total, false).bytes;
+    const int64_t bwd = render_carve(nullptr, n_pairs, n_views, w, src_rows_total, true).bytes;
+    return fwd > bwd ? fwd : bwd;
 }
 
 extern "C" int scream_render_depth(const float* src, const int32_t* s_row0, const int32_t* s_len, const float* tgt,
@@ -341,12 +356,13 @@ extern "C" int scream_render_depth(const float* src, const int32_t* s_row0, cons
     SCREAM_REQUIRE(!bad_geometry(n_pairs, n_views, w, src_rows_total) && max_s_len >= 0 && max_t_len >= 0, SCREAM_EINVAL);
     SCREAM_REQUIRE(isfinite(rho), SCREAM_EINVAL);
     SCREAM_REQUIRE(workspace_bytes >= scream_render_workspace_bytes(n_pairs, n_views, w, src_rows_total), SCREAM_EINVAL);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(workspace), SCREAM_EINVAL);
     if (n_pairs == 0) return 0;
     SCREAM_REQUIRE((int64_t)n_pairs * n_views * 2 <= 65535, SCREAM_EUNSUPPORTED);
     hipStream_t st = as_stream(stream);
-    uint32_t* range = reinterpret_cast<uint32_t*>(workspace);
-    uint64_t* keys = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) + range_bytes(n_pairs, n_views));
+    const RenderWs ws = render_carve(workspace, n_pairs, n_views, w, src_rows_total, false);
+    uint32_t* range = ws.range;
+    uint64_t* keys = ws.keys;
     const int64_t n_range = (int64_t)n_pairs * n_views * 2, n_pix = n_range * w * w;
     SCREAM_REQUIRE((n_pix + 255) / 256 < (1ll << 31), SCREAM_EUNSUPPORTED);
     render_setup_kernel<<<dim3((unsigned)((n_pix + 255) / 256)), dim3(256), 0, st>>>(range, n_range, keys, n_pix);
@@ -384,12 +400,13 @@ extern "C" int scream_render_depth_bwd(const float* src, const int32_t* s_row0, 
     SCREAM_REQUIRE(!bad_geometry(n_pairs, n_views, w, src_rows_total) && max_s_len >= 0, SCREAM_EINVAL);
     SCREAM_REQUIRE(isfinite(rho), SCREAM_EINVAL);
     SCREAM_REQUIRE(workspace_bytes >= scream_render_workspace_bytes(n_pairs, n_views, w, src_rows_total), SCREAM_EINVAL);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(workspace), SCREAM_EINVAL);
     if (n_pairs == 0 || max_s_len == 0) return 0;
     SCREAM_REQUIRE(n_views <= 65535 && n_pairs <= 65535, SCREAM_EUNSUPPORTED);
     hipStream_t st = as_stream(stream);
-    const uint32_t* range = reinterpret_cast<const uint32_t*>(workspace);
-    float* partial = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + range_bytes(n_pairs, n_views));
+    const RenderWs ws = render_carve(workspace, n_pairs, n_views, w, src_rows_total, true);
+    const uint32_t* range = ws.range;
+    float* partial = ws.partial;
     const float cexp = exp2_scale(rho);
     // g > 0 needs d^2 cexp >= -150 or so; the window reaches sqrt(160 / |cexp|) (all of the image when rho == 0)
     const float reach = cexp < 0.0f ? (float)sqrt(160.0 / -(double)cexp) : 4.0f;

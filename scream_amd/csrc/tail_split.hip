@@ -940,7 +940,7 @@ extern "C" int scream_pack_tail(const float* Wm, const float* W1, const float* W
                                 const scream_tail_exps_t* exps, void* image, void* stream) {
     SCREAM_REQUIRE(Wm && W1 && W2 && image && split_ok(split), SCREAM_EINVAL);
     SCREAM_REQUIRE(!Wq_next || split != SCREAM_SPLIT_BF3, SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(image) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(image), SCREAM_EINVAL);
     const dim3 grid((TAIL_STAGES + (Wq_next ? NEXT_Q_STAGES : 0)) * 16 * 64 / 256), block(256);
     if (split != SCREAM_SPLIT_BF3) {
         TailScales sc;
@@ -964,8 +964,7 @@ extern "C" int scream_kv_finalize_image(const float* kv_partial, const int32_t* 
     SCREAM_REQUIRE(kv_partial && cloud_row0 && cloud_len && kv_image && split_ok(split), SCREAM_EINVAL);
     SCREAM_REQUIRE(n_kv >= 0 && cloud_begin >= 0 && row_base >= 0 && n_layers >= 1 && n_layers <= 65535, SCREAM_EINVAL);
     SCREAM_REQUIRE(n_layers == 1 || (partial_layer_stride > 0 && image_layer_stride > 0 && image_layer_stride % 16 == 0), SCREAM_EINVAL);
-    SCREAM_REQUIRE(((reinterpret_cast<uintptr_t>(kv_image) | reinterpret_cast<uintptr_t>(kv_partial)) & 15) == 0 && partial_layer_stride % 4 == 0,
-                   SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(kv_image) && aligned16(kv_partial) && partial_layer_stride % 4 == 0, SCREAM_EINVAL);
     if (n_kv == 0) return 0;
     const dim3 grid(n_kv * SCREAM_NHEAD, n_layers), block(KVF_THREADS);
     if (split != SCREAM_SPLIT_BF3)
@@ -995,10 +994,8 @@ extern "C" int scream_layer_tail_f32(const float* Q, const void* kv_image, const
                                      const scream_tail_exps_t* exps, void* stream) {
     SCREAM_REQUIRE(Q && kv_image && tile_cloud && cloud_len && x && tail_image && g1 && b1 && g2 && b2 && y && split_ok(split), SCREAM_EINVAL);
     SCREAM_REQUIRE(M >= 0 && M % SCREAM_ROW_TILE == 0, SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE(((reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(kv_image) | reinterpret_cast<uintptr_t>(x) |
-                     reinterpret_cast<uintptr_t>(tail_image) | reinterpret_cast<uintptr_t>(g1) | reinterpret_cast<uintptr_t>(b1) |
-                     reinterpret_cast<uintptr_t>(g2) | reinterpret_cast<uintptr_t>(b2) | reinterpret_cast<uintptr_t>(y) |
-                     reinterpret_cast<uintptr_t>(q_next)) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(Q) && aligned16(kv_image) && aligned16(x) && aligned16(tail_image) && aligned16(g1) && aligned16(b1) &&
+                       aligned16(g2) && aligned16(b2) && aligned16(y) && aligned16(q_next), SCREAM_EINVAL);
     SCREAM_REQUIRE(x != y, SCREAM_EINVAL);  // the residual of a row is read twice, long after its neighbours were written
     // q_next (the image then has its eight query stages): fp16 splits only; it may be Q itself, never x or y
     SCREAM_REQUIRE(!q_next || (split != SCREAM_SPLIT_BF3 && q_next != x && q_next != y), SCREAM_EINVAL);
@@ -1027,7 +1024,7 @@ extern "C" int scream_layer_tail_f32(const float* Q, const void* kv_image, const
 extern "C" int scream_act_layout(const float* src, float* dst, int64_t M, int32_t to_fragment, void* stream) {
     SCREAM_REQUIRE(src && dst && src != dst, SCREAM_EINVAL);
     SCREAM_REQUIRE(M >= 0 && M % 32 == 0 && M / 32 < (1ll << 31), SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE(((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(src) && aligned16(dst), SCREAM_EINVAL);
     if (M == 0) return 0;
     act_layout_kernel<<<dim3((unsigned)(M / 32)), dim3(256), 0, as_stream(stream)>>>(src, dst, to_fragment ? 1 : 0);
     SCREAM_LAUNCH_CHECK();

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void voxel_centroid_kernel(const float* __rest
 
 extern "C" int64_t scream_voxel_workspace_bytes(int64_t rows_total, int32_t n_clouds) {
     if (rows_total < 0 || rows_total > INT32_MAX || n_clouds < 0) return SCREAM_EINVAL;
-    return workspace_bytes(rows_total, n_clouds);
+    return voxel_carve_bytes(rows_total, n_clouds);
 }
 
 extern "C" int scream_voxel_down_sample(const float* xyz, const int32_t* row0, const int32_t* len, int32_t n_clouds, int32_t max_len,
@@ -70,18 +70,19 @@ extern "C" int scream_voxel_down_sample(const float* xyz, const int32_t* row0, c
                                         int64_t workspace_bytes_given, void* stream) {
     SCREAM_REQUIRE(n_clouds >= 0 && max_len >= 0 && workspace_bytes_given >= 0, SCREAM_EINVAL);
     SCREAM_REQUIRE(xyz && row0 && len && voxel && out_xyz && out_len && workspace, SCREAM_EINVAL);
-    SCREAM_REQUIRE(workspace_bytes_given >= workspace_bytes(max_len, n_clouds), SCREAM_EINVAL);
-    SCREAM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, SCREAM_EINVAL);
+    SCREAM_REQUIRE(workspace_bytes_given >= voxel_carve_bytes(max_len, n_clouds), SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(workspace), SCREAM_EINVAL);
     if (n_clouds == 0) return 0;
     SCREAM_REQUIRE(n_clouds <= 65535, SCREAM_EUNSUPPORTED);
     // the rows this workspace was sized for: the largest rows_total whose workspace fits (the size is monotone in rows)
     int64_t rows_cap = max_len, hi = INT32_MAX;
     while (rows_cap < hi) {
         const int64_t mid = rows_cap + (hi - rows_cap + 1) / 2;
-        if (workspace_bytes(mid, n_clouds) <= workspace_bytes_given) rows_cap = mid;
+        if (voxel_carve_bytes(mid, n_clouds) <= workspace_bytes_given) rows_cap = mid;
         else hi = mid - 1;
     }
-    const Carve cv = carve(workspace, rows_cap, n_clouds);
+    Carver w{workspace};
+    const Carve cv = voxel_carve(w, rows_cap, n_clouds);
     hipStream_t st = as_stream(stream);
     const int rc = voxel_sort_enqueue(xyz, row0, len, n_clouds, max_len, voxel, rows_cap, cv, st);
     if (rc != 0) return rc;

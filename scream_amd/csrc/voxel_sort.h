@@ -39,12 +39,9 @@ struct Carve {
 };
 
 inline int64_t blocks_cap(int64_t rows, int32_t n_clouds) { return rows / VX_TILE + n_clouds + 1; }
-inline int64_t workspace_bytes(int64_t rows, int32_t n_clouds) {
-    return align256((int64_t)n_clouds * (int64_t)sizeof(CloudPlan)) + 2 * align256(rows * 8) + 3 * align256(rows * 4) +
-           align256(blocks_cap(rows, n_clouds) * 256 * 4) + align256(blocks_cap(rows, n_clouds) * 4);
-}
-inline Carve carve(void* workspace, int64_t rows, int32_t n_clouds) {
-    Carver w{workspace};
+// THE layout of the sort's buffers, for `rows` rows in `n_clouds` clouds, from wherever `w` stands (voxel.hip: the caller's
+// workspace; icp_raw.hip: behind the run's own buffers).  On a Carver with a null base it only measures.
+inline Carve voxel_carve(Carver& w, int64_t rows, int32_t n_clouds) {
     Carve c;
     c.plan = w.take<CloudPlan>(n_clouds);
     c.keys[0] = w.take<uint64_t>(rows);
@@ -55,6 +52,11 @@ inline Carve carve(void* workspace, int64_t rows, int32_t n_clouds) {
     c.counts = w.take<uint32_t>(blocks_cap(rows, n_clouds) * 256);
     c.heads = w.take<int32_t>(blocks_cap(rows, n_clouds));
     return c;
+}
+inline int64_t voxel_carve_bytes(int64_t rows, int32_t n_clouds) {
+    Carver w{nullptr};
+    voxel_carve(w, rows, n_clouds);
+    return w.used;
 }
 
 // grid 1, block 256: every cloud's row range checked against what the host declared (the kernels below trust the plan, not

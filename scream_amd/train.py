@@ -36,7 +36,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import SPLIT_BF3, check
-from .ops import EPI_BIAS_RELU, EPI_ELU1, EPI_NONE, EPI_RELU, D_MODEL, _p, _stream, gemm_f32
+from .ops import EPI_BIAS_RELU, EPI_ELU1, EPI_NONE, EPI_RELU, D_MODEL, _p, _stream, _workspace, gemm_f32
 from .packing import PackedBatch
 
 F4 = 4  # bytes per float
@@ -54,29 +54,23 @@ def transpose(W: torch.Tensor) -> torch.Tensor:
 
 
 def wgrad(dY: torch.Tensor, X: torch.Tensor, dW: torch.Tensor, colsum: torch.Tensor = None, accumulate: bool = False,
-          ldy: int = None, ldx: int = None, rows: int = None) -> torch.Tensor:
-    """dW[N,K] (+)= dY^T X over rows (scream_gemm_wgrad_f32); dW any contiguous tensor of N * K floats."""
+          ldy: int = None, ldx: int = None, rows: int = None, split: int = None) -> torch.Tensor:
+    """dW[N,K] (+)= dY^T X over rows; dW any contiguous tensor of N * K floats.  split None: the fp32-input MFMA
+    (scream_gemm_wgrad_f32); SPLIT_BF3: the 16-bit matrix cores, fp32-accurate by operand splitting (scream_gemm_wgrad_split_f32)."""
     lib = _lib.load()
+    name = "scream_gemm_wgrad_f32" if split is None else "scream_gemm_wgrad_split_f32"
+    sizer = "scream_wgrad_workspace_bytes" if split is None else "scream_wgrad_split_workspace_bytes"
     rows = dY.shape[0] if rows is None else rows
     N, K = dY.shape[1], X.shape[1]
-    ws = torch.empty(max(lib.scream_wgrad_workspace_bytes(rows, N, K), 16), device=dY.device, dtype=torch.uint8)
-    check(lib.scream_gemm_wgrad_f32(dY.data_ptr(), dY.stride(0) if ldy is None else ldy, X.data_ptr(),
-                                    X.stride(0) if ldx is None else ldx, rows, N, K, _p(dW), int(accumulate), _p(colsum),
-                                    ws.data_ptr(), ws.numel(), _stream()), "scream_gemm_wgrad_f32")
+    ws = _workspace(getattr(lib, sizer), sizer, rows, N, K, device=dY.device)
+    check(getattr(lib, name)(dY.data_ptr(), dY.stride(0) if ldy is None else ldy, X.data_ptr(), X.stride(0) if ldx is None else ldx,
+                             rows, N, K, _p(dW), int(accumulate), _p(colsum), *(() if split is None else (split,)),
+                             ws.data_ptr(), ws.numel(), _stream()), name)
     return dW
 
 
-def wgrad_split(dY: torch.Tensor, X: torch.Tensor, dW: torch.Tensor, colsum: torch.Tensor = None, accumulate: bool = False,
-                ldy: int = None, ldx: int = None, rows: int = None, split: int = SPLIT_BF3) -> torch.Tensor:
-    """wgrad on the 16-bit matrix cores (scream_gemm_wgrad_split_f32): same contract, fp32-accurate by operand splitting."""
-    lib = _lib.load()
-    rows = dY.shape[0] if rows is None else rows
-    N, K = dY.shape[1], X.shape[1]
-    ws = torch.empty(max(lib.scream_wgrad_split_workspace_bytes(rows, N, K), 16), device=dY.device, dtype=torch.uint8)
-    check(lib.scream_gemm_wgrad_split_f32(dY.data_ptr(), dY.stride(0) if ldy is None else ldy, X.data_ptr(),
-                                          X.stride(0) if ldx is None else ldx, rows, N, K, _p(dW), int(accumulate), _p(colsum),
-                                          split, ws.data_ptr(), ws.numel(), _stream()), "scream_gemm_wgrad_split_f32")
-    return dW
+def wgrad_split(dY, X, dW, colsum=None, accumulate=False, ldy=None, ldx=None, rows=None, split: int = SPLIT_BF3) -> torch.Tensor:
+    return wgrad(dY, X, dW, colsum, accumulate, ldy, ldx, rows, split)
 
 
 SPLIT_K = 256  # a data gradient whose K scream_gemm_split_f32 does not take (K != 64 + 192 j) runs as products of this depth
@@ -120,7 +114,7 @@ class _Gemms:
         return out
 
     def wgrad(self, dY, X, dW, colsum=None):
-        return (wgrad_split if self.split else wgrad)(dY, X, dW, colsum)
+        return wgrad(dY, X, dW, colsum, split=SPLIT_BF3 if self.split else None)
 
 
 def ln_fwd(a: torch.Tensor, b, gamma, beta, out: torch.Tensor = None):
@@ -135,7 +129,7 @@ def ln_fwd(a: torch.Tensor, b, gamma, beta, out: torch.Tensor = None):
 def ln_bwd(dy, a, b, mean, rstd, gamma, dz, dsum, dgamma, dbeta, accumulate: bool = False):
     lib = _lib.load()
     rows = dy.shape[0]
-    ws = torch.empty(max(lib.scream_ln_bwd_workspace_bytes(rows), 16), device=dy.device, dtype=torch.uint8)
+    ws = _workspace(lib.scream_ln_bwd_workspace_bytes, "scream_ln_bwd_workspace_bytes", rows, device=dy.device)
     check(lib.scream_ln_bwd(_p(dy), _p(a), _p(b), _p(mean), _p(rstd), _p(gamma), _p(dz), _p(dsum), _p(dgamma), _p(dbeta),
                             int(accumulate), rows, ws.data_ptr(), ws.numel(), _stream()), "scream_ln_bwd")
     return dz
@@ -145,7 +139,7 @@ def attn_bwd(Qf, ldq, q_rows, q_row_base, O, dO, Kf, Vf, ldkv, kv_rows, kv_row_b
              q_cloud_begin, n_q, kv_cloud_offset, dq, lddq, dk, dv, lddkv):
     """Pointer-level wrapper of scream_attn_bwd: Qf / Kf / Vf / dq / dk / dv are device addresses (column offsets applied)."""
     lib = _lib.load()
-    ws = torch.empty(max(lib.scream_attn_bwd_workspace_bytes(n_q, batch.max_chunks), 16), device=O.device, dtype=torch.uint8)
+    ws = _workspace(lib.scream_attn_bwd_workspace_bytes, "scream_attn_bwd_workspace_bytes", n_q, batch.max_chunks, device=O.device)
     check(lib.scream_attn_bwd(Qf, ldq, q_rows, q_row_base, _p(O), _p(dO), Kf, Vf, ldkv, kv_rows, kv_row_base, _p(kv),
                               _p(batch.tile_cloud, torch.int32), _p(batch.cloud_row0, torch.int32), _p(batch.cloud_len, torch.int32),
                               q_cloud_begin, n_q, kv_cloud_offset, batch.max_chunks, dq, lddq, dk, dv, lddkv,
@@ -163,7 +157,7 @@ def add_(y, x):
 def grad3(w, s, dW, transpose_w: bool, col_w=None, col_s=None, center=None, tile_cloud=None):
     lib = _lib.load()
     rows = w.shape[0]
-    ws = torch.empty(max(lib.scream_grad3_workspace_bytes(rows), 16), device=w.device, dtype=torch.uint8)
+    ws = _workspace(lib.scream_grad3_workspace_bytes, "scream_grad3_workspace_bytes", rows, device=w.device)
     check(lib.scream_grad3(_p(w), _p(s), _p(center), _p(tile_cloud, torch.int32), rows, _p(dW), int(transpose_w), _p(col_w),
                            _p(col_s), 0, ws.data_ptr(), ws.numel(), _stream()), "scream_grad3")
 

@@ -89,6 +89,114 @@ def test_icp_workspace_bytes_is_monotone_and_no_larger_than_the_formula_it_repla
         assert f(*bad) == -1  # SCREAM_EINVAL
 
 
+# The *_workspace_bytes functions of the commit before every op's carve became its size (hand-written formulas), by shape: an empty
+# call, one row, three clouds of 257 / 0 / 300 rows, a KITTI-size call (8 pairs of 131 072 rows), a 3DMatch-size call (32 pairs of
+# 5 120 rows); wgrad and render at their own shapes.  RULE: how far the new size may lie above the old one ("==": byte for byte).
+WS_SHAPES = {
+    "scream_voxel_workspace_bytes": [(0, 0), (1, 1), (557, 3), (8 * 131072, 8), (64 * 5120, 64)],
+    "scream_icp_raw_workspace_bytes": [(0, 0, 0), (1, 1, 1), (557, 557, 3), (8 * 131072, 8 * 131072, 8), (32 * 5120, 32 * 5120, 32)],
+    "scream_wgrad_workspace_bytes": [(0, 256, 256), (1, 128, 128), (128, 256, 256), (330000, 256, 256), (300, 128, 128)],
+    "scream_wgrad_split_workspace_bytes": [(0, 256, 256), (1, 128, 128), (128, 256, 256), (330000, 256, 256), (300, 128, 128)],
+    "scream_attn_bwd_workspace_bytes": [(0, 1), (1, 1), (3, 2), (8, 512), (32, 20)],
+    "scream_ln_bwd_workspace_bytes": [(0,), (1,), (557,), (8 * 131072,), (32 * 5120,)],
+    "scream_grad3_workspace_bytes": [(0,), (1,), (557,), (8 * 131072,), (32 * 5120,)],
+    "scream_l1_pairs_workspace_bytes": [(0, 0), (1, 1), (3, 300), (8, 131072), (32, 5120)],
+    "scream_render_workspace_bytes": [(0, 1, 64, 0), (1, 1, 64, 1), (3, 2, 64, 557), (1, 6, 64, 5000), (2, 2, 64, 370), (1, 6, 64, 500001),
+                                      (8, 6, 64, 8 * 131072), (32, 6, 64, 32 * 5120)],
+    "scream_prep_pairs_workspace_bytes": [(0, 0, 0), (2, 1, 1), (1114, 3, 300), (16 * 131072, 8, 131072), (64 * 5120, 32, 5120)],
+}
+WS_BEFORE = {
+    "scream_voxel_workspace_bytes": [1280, 3840, 20736, 29896704, 9411584],
+    "scream_icp_raw_workspace_bytes": [1536, 6400, 32512, 47234048, 7421440],
+    "scream_wgrad_workspace_bytes": [0, 66048, 263168, 66318336, 198144],
+    "scream_wgrad_split_workspace_bytes": [0, 66048, 263168, 66318336, 198144],
+    "scream_attn_bwd_workspace_bytes": [0, 67584, 304128, 138682368, 22708224],
+    "scream_ln_bwd_workspace_bytes": [0, 2048, 4096, 4194304, 655360],
+    "scream_grad3_workspace_bytes": [0, 4112, 8224, 8421376, 1315840],
+    "scream_l1_pairs_workspace_bytes": [0, 256, 256, 32768, 5120],
+    "scream_render_workspace_bytes": [0, 65792, 393472, 393472, 262400, 36000328, 75497984, 12584448],  # (the sixth: the backward's partials)
+    "scream_prep_pairs_workspace_bytes": [0, 512, 28416, 51380224, 8028160],
+}
+WS_RULE = {"scream_render_workspace_bytes": 255, "scream_prep_pairs_workspace_bytes": 5 * 256}  # every other one: "=="
+
+
+@pytest.mark.parametrize("name", sorted(WS_SHAPES))
+def test_workspace_sizes_against_the_formulas_they_replaced(name):
+    """Every size is now its op's carve on a null base.  Against the formula it replaced: equal byte for byte where the formula
+    aligned every piece the way the Carver does (or the pieces are multiples of 256 already), and for render / prep at most one
+    rounding of the backward's partials / five more aligned pieces above it (prep may be smaller: part_mean and part_cen are
+    [B], not [2B]).  Monotone in every argument; what was refused is refused."""
+    f = getattr(_lib.load(), name)
+    for shape, before in zip(WS_SHAPES[name], WS_BEFORE[name]):
+        b = f(*shape)
+        print(name, shape, "before", before, "now", b)
+        if name in WS_RULE:
+            assert 0 <= b <= before + WS_RULE[name], (shape, b, before)
+            assert name != "scream_render_workspace_bytes" or b >= before, (shape, b, before)
+        else:
+            assert b == before, (shape, b, before)
+        for k in range(len(shape)):
+            if name.startswith("scream_wgrad") and k > 0:
+                steps = (128,)  # N and K come in tiles of 128
+            elif name == "scream_render_workspace_bytes" and k == 2:
+                steps = (64,)  # w in tiles of 64
+            else:
+                steps = (1, 256)
+            for d in steps:
+                up = tuple(v + d if i == k else v for i, v in enumerate(shape))
+                if name == "scream_prep_pairs_workspace_bytes" and k == 2:
+                    up = (up[0] + d,) + up[1:]  # max_len <= raw_rows
+                assert f(*up) >= b, (shape, up)
+
+
+def test_workspace_size_refusals_are_what_they_were():
+    lib = _lib.load()
+    refused = {
+        "scream_voxel_workspace_bytes": [(-1, 3), (1000, -1), (1 << 31, 1)],
+        "scream_icp_raw_workspace_bytes": [(-1, 0, 0), (0, -1, 0), (0, 0, -1), (1 << 31, 0, 1), (0, 1 << 31, 1)],
+        "scream_wgrad_workspace_bytes": [(-1, 256, 256), (128, 200, 256), (128, 256, 200), (128, 0, 256), (128, 256, 0)],
+        "scream_wgrad_split_workspace_bytes": [(-1, 256, 256), (330000, 200, 256), (128, 256, 200)],
+        "scream_attn_bwd_workspace_bytes": [(-1, 1), (1, 0)],
+        "scream_ln_bwd_workspace_bytes": [(-1,)],
+        "scream_grad3_workspace_bytes": [(-1,)],
+        "scream_l1_pairs_workspace_bytes": [(-1, 1), (1, -1)],
+        "scream_render_workspace_bytes": [(-1, 6, 64, 10), (1, 0, 64, 10), (1, 6, 96, 10), (1, 6, 0, 10), (1, 6, 4160, 10), (1, 6, 64, -1)],
+        "scream_prep_pairs_workspace_bytes": [(-1, 1, 0), (1 << 31, 1, 1), (10, -1, 1), (10, 1, -1), (10, 1, 11)],
+    }
+    assert sorted(refused) == sorted(WS_SHAPES)
+    for name, shapes in refused.items():
+        for shape in shapes:
+            assert getattr(lib, name)(*shape) == -1, (name, shape)
+
+
+def test_no_size_is_a_formula_and_no_alignment_check_is_spelled_out():
+    """In csrc, align256( occurs in common.h alone (the Carver): every workspace size is a carve on a null base.  So does a pointer
+    cast to uintptr_t and masked with 15: every entry point asks aligned16()."""
+    d = os.path.join(REPO, "scream_amd", "csrc")
+    for f in sorted(os.listdir(d)):
+        text = open(os.path.join(d, f)).read()
+        if f == "common.h":
+            assert "align256(" in text and re.search(r"reinterpret_cast<uintptr_t>[^;]*&\s*15\b", text)
+            continue
+        assert "align256(" not in text, f
+        assert not re.search(r"reinterpret_cast<uintptr_t>[^;]*&\s*15\b", text), f
+
+
+def test_train_wrappers_size_their_scratch_through_ops_workspace():
+    """train.wgrad_split stays importable (wgrad with split=SPLIT_BF3), and a weight gradient whose N the library refuses raises
+    from the size function, with the arguments in the message, before any tensor is touched."""
+    from scream_amd import ops, train
+    assert callable(train.wgrad_split) and train.wgrad_split is not train.wgrad
+    lib = _lib.load()
+    for sizer in ("scream_wgrad_workspace_bytes", "scream_wgrad_split_workspace_bytes"):
+        with pytest.raises(_lib.ScreamHipError, match=r"%s\(300, 200, 256\)" % sizer):
+            ops._workspace(getattr(lib, sizer), sizer, 300, 200, 256, device="cpu")
+    dY, X = torch.zeros(300, 200), torch.zeros(300, 256)
+    for fn in (train.wgrad, train.wgrad_split):
+        with pytest.raises(_lib.ScreamHipError, match=r"\(300, 200, 256\)"):
+            fn(dY, X, None)
+
+
 def test_product_code_never_imports_the_oracle():
     for root, _, files in os.walk(os.path.join(REPO, "scream_amd")):
         for f in files:
