@@ -18,7 +18,6 @@ constexpr int NH = SCREAM_NHEAD;          // 8
 constexpr int KV_ELEMS = (HD + 1) * HD;   // 1056 floats per head: 32 x 32 and a row of 32
 constexpr int CHUNK = SCREAM_KV_CHUNK;    // 256 query tokens per partial of the attention reduction
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 // ------------------------------------------------------------------------------------------------ weight gradient
@@ -719,7 +718,7 @@ extern "C" int64_t scream_wgrad_split_workspace_bytes(int64_t rows, int32_t N, i
 extern "C" int scream_gemm_wgrad_split_f32(const float* dY, int64_t ldy, const float* X, int64_t ldx, int64_t rows, int32_t N,
                                            int32_t K, float* dW, int32_t accumulate, float* colsum, int32_t split,
                                            void* workspace, int64_t workspace_bytes, void* stream) {
-    SCREAM_REQUIRE(split == SCREAM_SPLIT_BF3, SCREAM_EINVAL);
+    SCREAM_REQUIRE(split_valid(split) && !split_fp16(split), SCREAM_EINVAL);  // built for bf16 x 3 only
     return wgrad_run<wgrad_split_partial_kernel<SplitBf3>>(dY, ldy, X, ldx, rows, N, K, dW, accumulate, colsum, workspace,
                                                            workspace_bytes, stream);
 }

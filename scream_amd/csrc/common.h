@@ -45,6 +45,27 @@ struct Carver {
     }
 };
 
+// ---- device helpers of the matrix kernels (gemm_f32.hip, gemm_split.hip / gemm_epilogue.h, ring.h, backward.hip)
+typedef const __attribute__((address_space(1))) void* gptr_t;  // source and destination of an LDS-DMA piece
+typedef __attribute__((address_space(3))) void* lptr_t;
+
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+
+// s_waitcnt vmcnt(N) lgkmcnt(0) + workgroup barrier: the N youngest vector-memory operations of this wave (gemm_split.hip: the A
+// loads of the k-tile after next; the ring kernels: the DMA pieces of the stage after the one about to be read) stay in flight
+template <int N>
+__device__ __forceinline__ void ring_barrier() {
+    __builtin_amdgcn_s_waitcnt(0x0070 | (N & 15) | ((N >> 4) << 14));
+    __builtin_amdgcn_s_barrier();
+}
+
+// workgroup barrier that waits for this wave's LDS traffic only: a __syncthreads() would also drain the LDS-DMA prefetch that is
+// deliberately left in flight (the vector-memory queue stays untouched)
+__device__ __forceinline__ void lds_barrier() {
+    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+    __builtin_amdgcn_s_barrier();
+}
+
 // Row index inside a 32x32 MFMA accumulator tile held by lane (lane>>5 = half) in register reg.
 // (cdna_hip_programming.md section 3: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * half.)
 __device__ __forceinline__ int mfma32_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.h"
+#include "split.h"
 
 namespace {
 
@@ -90,10 +91,10 @@ struct Ctx {
     // scream_model_t.gemm_split, which alone selects the schedule.  0: fp32 weights, row-major features, one launch per step.
     // Else: packed operand planes, features FRAGMENT-major between the kernels (SCREAM_ACT_FRAG), one-launch layer tails.
     int split;
-    bool fp16() const { return split == SCREAM_SPLIT_H2 || split == SCREAM_SPLIT_H1; }
+    bool fp16() const { return split_fp16(split); }
 };
 
-bool valid_split(int s) { return s == 0 || s == SCREAM_SPLIT_H1 || s == SCREAM_SPLIT_H2 || s == SCREAM_SPLIT_BF3; }
+bool valid_split(int s) { return s == 0 || split_valid(s); }  // 0: the fp32 schedule
 
 // One layer against the table of include/scream_hip.h (scream_layer_t): what the schedule of `c.split` reads is there, and what
 // would select another schedule -- a tail image on fp32, a next-layer query projection where none is run -- is not.

@@ -1,5 +1,5 @@
 // Epilogues shared by the fp32-MFMA GEMM (gemm_f32.hip, 4 waves, 128-row tiles) and the 3xbf16-split GEMM
-// (gemm_x3.hip, 8 waves, 256-row tiles).  Both leave a 32 x 256 fp32 accumulator tile per wave in the
+// (gemm_split.hip, 8 waves, 256-row tiles).  Both leave a 32 x 256 fp32 accumulator tile per wave in the
 // 32x32 MFMA layout: acc[tn][e] = C[row = mfma32_row(e, half)][col = tn*32 + r].
 #pragma once
 #include "common.h"
@@ -21,7 +21,7 @@ struct EpiArgs {
     const int32_t* cloud_len;
     int64_t row_base;           // packed row of A's row 0
     // SCREAM_EPI_ELU1 / SCREAM_EPI_QKV, x3 kernel only: the activated tile (the 256 query columns) is written in the
-    // FRAGMENT-major activation layout (SCREAM_ACT_FRAG, include/scream_hip.h) that tail_x3.hip reads; ldc must be 256
+    // FRAGMENT-major activation layout (SCREAM_ACT_FRAG, include/scream_hip.h) that tail_split.hip reads; ldc must be 256
     int c_frag;
     // SCREAM_EPI_QKV with more than one key/value tile PAIR (the cross stage's six target-side projections as one GEMM,
     // N = n_act + 512 L): floats between the partial arrays of consecutive layers
@@ -32,15 +32,6 @@ struct EpiArgs {
 };
 
 constexpr int KV_ELEMS = (SCREAM_HEAD_DIM + 1) * SCREAM_HEAD_DIM;
-
-__device__ __forceinline__ void lds_barrier() {
-    // workgroup barrier that waits for this wave's LDS traffic only: a __syncthreads() would also drain the
-    // LDS-DMA prefetch of the next tile that is deliberately left in flight (vmcnt).
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
-    __builtin_amdgcn_s_barrier();
-}
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
 // NWAVES waves stacked in M (wave w owns rows w*32 .. w*32+31 of the block tile at packed-GEMM row m0);
 // slabs: LDS scratch of max(NWAVES * 8 * 256, 8 * KV_ELEMS) floats that no other wave-group touches meanwhile.
@@ -127,7 +118,7 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[8], float* slabs, in
     } else if ((EPI == SCREAM_EPI_ELU1 || EPI == SCREAM_EPI_QKV) && NWAVES == 8 && ep.c_frag && n0_cur < ep.n_act) {
     // ---- Q' = elu(q) + 1 in the fragment-major layout -------------------------------------------------------------
     // Element (row 32 t + rho, feature 32 blk + 8 a + 4 hf + b) lives at ((((t * 8 + blk) * 4 + a) * 64 + rho + 32 hf) * 4 + b:
-    // per 32-row group, segment and a, one 1 KiB run in lane order -- what a wave of tail_x3.hip loads with one instruction.
+    // per 32-row group, segment and a, one 1 KiB run in lane order -- what a wave of tail_split.hip loads with one instruction.
     // Eight rows at a time go through the wave's slab (row-major, the 16-byte chunks of row i XOR-swizzled by i so that the
     // transposing read below is 2-way conflicted at worst); a store instruction then writes eight full 128-byte lines.
     if (rows_exist) {

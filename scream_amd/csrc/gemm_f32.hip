@@ -31,6 +31,7 @@
 //   Tiles are numbered so that the N-tiles of one M-tile run back to back on ONE XCD (shared A
 //   rows in that XCD's L2) -- placement only changes speed, never results.
 #include "gemm_epilogue.h"
+#include "matrix_front.h"
 
 namespace {
 
@@ -38,9 +39,6 @@ constexpr int BM = 128;
 constexpr int BN = 256;
 constexpr int THREADS = 256;
 constexpr int MAX_GRID = 512;   // 256 CUs x 2 resident blocks
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 // BK is a template parameter only so that the staging geometry below is written once; BK = 32 is what ships
 // (BK = 64 needs 128 KiB of LDS -> one block per CU: measured 117 vs 130 TFLOP/s, profiles/r01_gemm_ablation.txt).
@@ -201,9 +199,8 @@ int launch(const float* A, int64_t lda, const float* W, float* C, int64_t ldc, i
            const EpiArgs& ep, hipStream_t st) {
     const int n_tiles = N / BN;
     const int64_t total = (M / BM) * n_tiles;
-    if (total == 0) return 0;
-    SCREAM_REQUIRE(total < (1ll << 31), SCREAM_EUNSUPPORTED);
-    const unsigned grid = total < MAX_GRID ? (unsigned)total : (unsigned)MAX_GRID;
+    const int grid = persistent_grid(total, MAX_GRID);
+    if (grid <= 0) return grid;
     gemm_f32_kernel<EPI, 32><<<dim3(grid), dim3(THREADS), 0, st>>>(A, lda, W, C, ldc, n_tiles, (unsigned)total, K, ep);
     SCREAM_LAUNCH_CHECK();
     return 0;
@@ -215,43 +212,19 @@ extern "C" int scream_gemm_f32(const float* A, int64_t lda, const float* W, floa
                                int32_t N, int32_t K, int32_t epilogue, int32_t n_act, const float* bias,
                                const float* residual, int64_t ldr, const float* gamma, const float* beta,
                                void* stream) {
-    SCREAM_REQUIRE(A && W && C, SCREAM_EINVAL);
-    SCREAM_REQUIRE(M >= 0 && M % BM == 0 && N > 0 && N % BN == 0 && K > 0 && K % 64 == 0, SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE(lda >= K && ldc >= N && lda % 4 == 0 && ldc % 4 == 0, SCREAM_EINVAL);
-    SCREAM_REQUIRE(aligned16(A) && aligned16(W) && aligned16(C), SCREAM_EINVAL);
-    EpiArgs ep{n_act, bias, residual, ldr, gamma, beta, nullptr, nullptr, nullptr, nullptr, 0};
-    hipStream_t st = as_stream(stream);
-    switch (epilogue) {
-        case SCREAM_EPI_NONE:
-            return launch<SCREAM_EPI_NONE>(A, lda, W, C, ldc, M, N, K, ep, st);
-        case SCREAM_EPI_ELU1:
-            SCREAM_REQUIRE(n_act >= 0 && n_act % BN == 0, SCREAM_EUNSUPPORTED);
-            return launch<SCREAM_EPI_ELU1>(A, lda, W, C, ldc, M, N, K, ep, st);
-        case SCREAM_EPI_RELU:
-            return launch<SCREAM_EPI_RELU>(A, lda, W, C, ldc, M, N, K, ep, st);
-        case SCREAM_EPI_BIAS_RELU:
-            SCREAM_REQUIRE(bias, SCREAM_EINVAL);
-            return launch<SCREAM_EPI_BIAS_RELU>(A, lda, W, C, ldc, M, N, K, ep, st);
-        case SCREAM_EPI_RES_LN:
-            SCREAM_REQUIRE(N == BN, SCREAM_EUNSUPPORTED);
-            SCREAM_REQUIRE(residual && gamma && beta && ldr >= N && ldr % 4 == 0, SCREAM_EINVAL);
-            SCREAM_REQUIRE(aligned16(residual), SCREAM_EINVAL);
-            return launch<SCREAM_EPI_RES_LN>(A, lda, W, C, ldc, M, N, K, ep, st);
-        default:
-            return SCREAM_EINVAL;
-    }
+    if (int rc = check_gemm(A, lda, W, C, ldc, M, N, K, K_MULT_64)) return rc;
+    const EpiArgs ep{n_act, bias, residual, ldr, gamma, beta, nullptr, nullptr, nullptr, nullptr, 0};
+    return dispatch_epilogue(epilogue, N, ep, [&](auto epi) {
+        return launch<decltype(epi)::value>(A, lda, W, C, ldc, M, N, K, ep, as_stream(stream));
+    });
 }
 
 extern "C" int scream_gemm_qkv_f32(const float* A, int64_t lda, const float* W, float* Q, int64_t ldq, int64_t M,
                                    int32_t N, int32_t K, int32_t n_q, const int32_t* tile_cloud,
                                    const int32_t* cloud_row0, const int32_t* cloud_len, int64_t row_base,
                                    float* kv_partial, void* stream) {
-    SCREAM_REQUIRE(A && W && kv_partial && tile_cloud && cloud_row0 && cloud_len, SCREAM_EINVAL);
-    SCREAM_REQUIRE(M >= 0 && M % BM == 0 && N > 0 && N % BN == 0 && K > 0 && K % 64 == 0, SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE((n_q == 0 || n_q == BN) && N == n_q + 2 * BN && row_base >= 0 && row_base % BM == 0, SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE(n_q == 0 || (Q && ldq >= n_q && ldq % 4 == 0 && aligned16(Q)), SCREAM_EINVAL);
-    SCREAM_REQUIRE(lda >= K && lda % 4 == 0, SCREAM_EINVAL);
-    SCREAM_REQUIRE(aligned16(A) && aligned16(W), SCREAM_EINVAL);
+    if (int rc = check_qkv(A, lda, W, Q, ldq, M, N, K, n_q, tile_cloud, cloud_row0, cloud_len, row_base, kv_partial, K_MULT_64, false))
+        return rc;
     EpiArgs ep{n_q, nullptr, nullptr, 0, nullptr, nullptr, kv_partial, tile_cloud, cloud_row0, cloud_len, row_base};
     return launch<SCREAM_EPI_QKV>(A, lda, W, Q, ldq, M, N, K, ep, as_stream(stream));
 }

@@ -24,7 +24,7 @@
 //   * A stays fp32 in HBM: lane (r, half) streams its 16 floats of row r per k-tile straight into registers (three
 //     register sets, requested TWO k-tiles ahead) and splits them there (v_cvt_pk_bf16_f32 + subtract, twice).
 //     Lane-half h owns k = 8 (2 s + (j >> 2)) + 4 h + (j & 3) of step s for both operands (the contraction index is a
-//     dummy; this is the ownership of a transposed accumulator tile in tail_x3.hip, so the two kernels share one
+//     dummy; this is the ownership of a transposed accumulator tile in tail_split.hip, so the two kernels share one
 //     activation layout).  Two layouts of A: row-major (the four 16-byte pieces 2a + h of the lane's 128-byte segment),
 //     or FRAGMENT-major (SCREAM_ACT_FRAG, include/scream_hip.h): the same pieces stored [32-row group][segment][a][lane],
 //     so that every wave instruction reads 1 KiB of contiguous memory instead of 32 half-used lines.
@@ -49,25 +49,14 @@
 #include <type_traits>
 
 #include "gemm_epilogue.h"
+#include "matrix_front.h"
 #include "split.h"
 
 namespace {
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 constexpr int XBM = 256, XBN = 256, XBK = 32, XTHREADS = 512, XWAVES = 8;
 constexpr int PLANE_BYTES = XBN * XBK * 2;     // 16 KiB; a k-tile stage is SP::NP of them
 constexpr int SLAB_BYTES = XWAVES * 8 * 256 * 4;  // 64 KiB
-constexpr int X_MAX_GRID = SCREAM_MAX_GRID;
-
-// s_waitcnt vmcnt(N) lgkmcnt(0) + workgroup barrier: the N youngest vector-memory operations of this wave (the A
-// loads of the k-tile after next) stay in flight across the barrier.
-template <int N>
-__device__ __forceinline__ void ring_barrier() {
-    __builtin_amdgcn_s_waitcnt(0x0070 | (N & 15) | ((N >> 4) << 14));
-    __builtin_amdgcn_s_barrier();
-}
 
 template <class SP, int EPI, bool AFRAG>
 __global__ __launch_bounds__(XTHREADS, 2) void gemm_split_kernel(const float* __restrict__ A, int64_t lda,
@@ -335,57 +324,38 @@ __global__ void pack_w_kernel(const float* __restrict__ W, int N, int K, float w
     for (int pl = 0; pl < SP::NP; ++pl) out[((int64_t)kt * N + n) * (XBK / 8) + cs + pl * plane] = p[pl];
 }
 
-struct SplitArgs {
-    int32_t split, a_exp, w_exp;
-};
-
-bool split_args_ok(const SplitArgs& sa) {
-    if (sa.split == SCREAM_SPLIT_BF3) return true;
-    return (sa.split == SCREAM_SPLIT_H2 || sa.split == SCREAM_SPLIT_H1) && sa.a_exp >= -60 && sa.a_exp <= 60 && sa.w_exp >= -60 && sa.w_exp <= 60;
-}
-
-template <class SP, int EPI>
-int launch_sp(const float* A, int64_t lda, const void* Wp, float* C, int64_t ldc, int64_t M, int N, int K, const EpiArgs& ep,
-              hipStream_t st, bool a_frag, const SplitArgs& sa) {
-    const int n_tiles = N / XBN;
-    const int64_t total = ((M + XBM - 1) / XBM) * n_tiles;
-    if (total == 0) return 0;
-    SCREAM_REQUIRE(total < (1ll << 31), SCREAM_EUNSUPPORTED);
-    const unsigned grid = total < X_MAX_GRID ? (unsigned)total : (unsigned)X_MAX_GRID;
-    const float a_scale = SP::SCALED ? exp2i(sa.a_exp) : 1.f, c_scale = SP::SCALED ? exp2i(-sa.a_exp - sa.w_exp) : 1.f;
-    if (a_frag)
-        gemm_split_kernel<SP, EPI, true><<<dim3(grid), dim3(XTHREADS), 0, st>>>(A, lda, reinterpret_cast<const char*>(Wp), C, ldc, M, n_tiles,
-                                                                                (unsigned)total, N, K, a_scale, c_scale, ep);
-    else
-        gemm_split_kernel<SP, EPI, false><<<dim3(grid), dim3(XTHREADS), 0, st>>>(A, lda, reinterpret_cast<const char*>(Wp), C, ldc, M, n_tiles,
-                                                                                 (unsigned)total, N, K, a_scale, c_scale, ep);
-    SCREAM_LAUNCH_CHECK();
-    return 0;
-}
-
 template <int EPI>
 int launch_split(const float* A, int64_t lda, const void* Wp, float* C, int64_t ldc, int64_t M, int N, int K, const EpiArgs& ep,
-                 hipStream_t st, bool a_frag, const SplitArgs& sa) {
-    if (sa.split == SCREAM_SPLIT_H2) return launch_sp<SplitH2, EPI>(A, lda, Wp, C, ldc, M, N, K, ep, st, a_frag, sa);
-    if (sa.split == SCREAM_SPLIT_H1) return launch_sp<SplitH1, EPI>(A, lda, Wp, C, ldc, M, N, K, ep, st, a_frag, sa);
-    return launch_sp<SplitBf3, EPI>(A, lda, Wp, C, ldc, M, N, K, ep, st, a_frag, sa);
+                 hipStream_t st, bool a_frag, int split, int a_exp, int w_exp) {
+    const int n_tiles = N / XBN;
+    const int64_t total = ((M + XBM - 1) / XBM) * n_tiles;
+    const int grid = persistent_grid(total, SCREAM_MAX_GRID);
+    if (grid <= 0) return grid;
+    with_split(split, [&](auto tag) {
+        typedef typename decltype(tag)::type SP;
+        const float a_scale = SP::SCALED ? exp2i(a_exp) : 1.f, c_scale = SP::SCALED ? exp2i(-a_exp - w_exp) : 1.f;
+        const auto kernel = a_frag ? gemm_split_kernel<SP, EPI, true> : gemm_split_kernel<SP, EPI, false>;
+        kernel<<<dim3(grid), dim3(XTHREADS), 0, st>>>(A, lda, reinterpret_cast<const char*>(Wp), C, ldc, M, n_tiles, (unsigned)total, N, K,
+                                                      a_scale, c_scale, ep);
+    });
+    SCREAM_LAUNCH_CHECK();
+    return 0;
 }
 
 }  // namespace
 
 extern "C" int scream_pack_w_split(const float* W, int32_t N, int32_t K, int32_t split, int32_t w_exp, void* packed, void* stream) {
     SCREAM_REQUIRE(W && packed, SCREAM_EINVAL);
-    SCREAM_REQUIRE(split_args_ok(SplitArgs{split, 0, w_exp}), SCREAM_EINVAL);
+    SCREAM_REQUIRE(split_exps_ok(split, 0, w_exp), SCREAM_EINVAL);
     SCREAM_REQUIRE(N > 0 && N % 4 == 0 && K > 0 && K % XBK == 0, SCREAM_EUNSUPPORTED);
     SCREAM_REQUIRE(aligned16(W) && aligned16(packed), SCREAM_EINVAL);
     const int64_t threads = (int64_t)N * (K / XBK) * 4;
     const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
-    if (split == SCREAM_SPLIT_H2)
-        pack_w_kernel<SplitH2><<<grid, block, 0, as_stream(stream)>>>(W, N, K, exp2i(w_exp), reinterpret_cast<f16x8*>(packed));
-    else if (split == SCREAM_SPLIT_H1)
-        pack_w_kernel<SplitH1><<<grid, block, 0, as_stream(stream)>>>(W, N, K, exp2i(w_exp), reinterpret_cast<f16x8*>(packed));
-    else
-        pack_w_kernel<SplitBf3><<<grid, block, 0, as_stream(stream)>>>(W, N, K, 1.f, reinterpret_cast<bf16x8*>(packed));
+    with_split(split, [&](auto tag) {
+        typedef typename decltype(tag)::type SP;
+        pack_w_kernel<SP><<<grid, block, 0, as_stream(stream)>>>(W, N, K, SP::SCALED ? exp2i(w_exp) : 1.f,
+                                                                 reinterpret_cast<typename SP::vec*>(packed));
+    });
     SCREAM_LAUNCH_CHECK();
     return 0;
 }
@@ -404,35 +374,14 @@ extern "C" int scream_gemm_split_f32(const float* A, int64_t lda, const void* W_
                                      int32_t N, int32_t K, int32_t epilogue, int32_t n_act, const float* bias,
                                      const float* residual, int64_t ldr, const float* gamma, const float* beta,
                                      int32_t layout, int32_t split, int32_t a_exp, int32_t w_exp, void* stream) {
-    SCREAM_REQUIRE(A && W_packed && C, SCREAM_EINVAL);
-    const SplitArgs sa{split, a_exp, w_exp};
-    SCREAM_REQUIRE(split_args_ok(sa), SCREAM_EINVAL);
-    SCREAM_REQUIRE(M >= 0 && M % SCREAM_ROW_TILE == 0 && N > 0 && N % XBN == 0 && K >= 64 && K % 64 == 0 && (K / 32 - 2) % 3 == 0, SCREAM_EUNSUPPORTED);  // K = 64 + 192 j: an EVEN number of k-tiles (stage = kt & 1), in groups of three after the first two
-    SCREAM_REQUIRE(lda >= K && ldc >= N && lda % 4 == 0 && ldc % 4 == 0, SCREAM_EINVAL);
-    SCREAM_REQUIRE(aligned16(A) && aligned16(W_packed) && aligned16(C), SCREAM_EINVAL);
+    SCREAM_REQUIRE(split_exps_ok(split, a_exp, w_exp), SCREAM_EINVAL);
+    if (int rc = check_gemm(A, lda, W_packed, C, ldc, M, N, K, K_64_PLUS_192)) return rc;
     if (int rc = check_layout(layout, lda, ldc, K, epilogue, n_act)) return rc;
-    const bool af = layout & SCREAM_LAYOUT_A_FRAG;
-    EpiArgs ep{n_act, bias, residual, ldr, gamma, beta, nullptr, nullptr, nullptr, nullptr, 0, (layout & SCREAM_LAYOUT_C_FRAG) ? 1 : 0};
-    hipStream_t st = as_stream(stream);
-    switch (epilogue) {
-        case SCREAM_EPI_NONE:
-            return launch_split<SCREAM_EPI_NONE>(A, lda, W_packed, C, ldc, M, N, K, ep, st, af, sa);
-        case SCREAM_EPI_ELU1:
-            SCREAM_REQUIRE(n_act >= 0 && n_act % XBN == 0, SCREAM_EUNSUPPORTED);
-            return launch_split<SCREAM_EPI_ELU1>(A, lda, W_packed, C, ldc, M, N, K, ep, st, af, sa);
-        case SCREAM_EPI_RELU:
-            return launch_split<SCREAM_EPI_RELU>(A, lda, W_packed, C, ldc, M, N, K, ep, st, af, sa);
-        case SCREAM_EPI_BIAS_RELU:
-            SCREAM_REQUIRE(bias, SCREAM_EINVAL);
-            return launch_split<SCREAM_EPI_BIAS_RELU>(A, lda, W_packed, C, ldc, M, N, K, ep, st, af, sa);
-        case SCREAM_EPI_RES_LN:
-            SCREAM_REQUIRE(N == XBN, SCREAM_EUNSUPPORTED);
-            SCREAM_REQUIRE(residual && gamma && beta && ldr >= N && ldr % 4 == 0, SCREAM_EINVAL);
-            SCREAM_REQUIRE(aligned16(residual), SCREAM_EINVAL);
-            return launch_split<SCREAM_EPI_RES_LN>(A, lda, W_packed, C, ldc, M, N, K, ep, st, af, sa);
-        default:
-            return SCREAM_EINVAL;
-    }
+    const EpiArgs ep{n_act, bias, residual, ldr, gamma, beta, nullptr, nullptr, nullptr, nullptr, 0, (layout & SCREAM_LAYOUT_C_FRAG) ? 1 : 0};
+    return dispatch_epilogue(epilogue, N, ep, [&](auto epi) {
+        return launch_split<decltype(epi)::value>(A, lda, W_packed, C, ldc, M, N, K, ep, as_stream(stream), layout & SCREAM_LAYOUT_A_FRAG,
+                                                  split, a_exp, w_exp);
+    });
 }
 
 extern "C" int scream_gemm_qkv_split_f32(const float* A, int64_t lda, const void* W_packed, float* Q, int64_t ldq, int64_t M,
@@ -440,21 +389,15 @@ extern "C" int scream_gemm_qkv_split_f32(const float* A, int64_t lda, const void
                                          const int32_t* cloud_row0, const int32_t* cloud_len, int64_t row_base,
                                          float* kv_partial, int32_t layout, int32_t split, int32_t a_exp, int32_t w_exp,
                                          int32_t k_exp, int32_t v_exp, void* stream) {
-    SCREAM_REQUIRE(A && W_packed && kv_partial && tile_cloud && cloud_row0 && cloud_len, SCREAM_EINVAL);
-    const SplitArgs sa{split, a_exp, w_exp};
-    SCREAM_REQUIRE(split_args_ok(sa), SCREAM_EINVAL);
-    SCREAM_REQUIRE(split == SCREAM_SPLIT_BF3 || (k_exp >= -40 && k_exp <= 40 && v_exp >= -40 && v_exp <= 40), SCREAM_EINVAL);
-    SCREAM_REQUIRE(M >= 0 && M % SCREAM_ROW_TILE == 0 && N > 0 && N % XBN == 0 && K >= 64 && K % 64 == 0 && (K / 32 - 2) % 3 == 0, SCREAM_EUNSUPPORTED);  // K = 64 + 192 j
-    // N = n_q + 512 L: L key/value tile pairs; L > 1 (several layers' key/value projections of the same rows) only without queries
-    SCREAM_REQUIRE((n_q == 0 || n_q == XBN) && N > n_q && (N - n_q) % (2 * XBN) == 0 && (n_q == 0 || N == n_q + 2 * XBN) && row_base >= 0 &&
-                       row_base % SCREAM_ROW_TILE == 0, SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE(n_q == 0 || (Q && ldq >= n_q && ldq % 4 == 0 && aligned16(Q)), SCREAM_EINVAL);
-    SCREAM_REQUIRE(lda >= K && lda % 4 == 0, SCREAM_EINVAL);
-    SCREAM_REQUIRE(aligned16(A) && aligned16(W_packed), SCREAM_EINVAL);
+    SCREAM_REQUIRE(split_exps_ok(split, a_exp, w_exp), SCREAM_EINVAL);
+    SCREAM_REQUIRE(!split_fp16(split) || (kv_exp_ok(k_exp) && kv_exp_ok(v_exp)), SCREAM_EINVAL);
+    if (int rc = check_qkv(A, lda, W_packed, Q, ldq, M, N, K, n_q, tile_cloud, cloud_row0, cloud_len, row_base, kv_partial, K_64_PLUS_192, true))
+        return rc;
     SCREAM_REQUIRE(!(layout & SCREAM_LAYOUT_C_FRAG) || n_q == XBN, SCREAM_EUNSUPPORTED);
     if (int rc = check_layout(layout, lda, n_q ? ldq : SCREAM_D_MODEL, K, SCREAM_EPI_QKV, n_q ? n_q : SCREAM_D_MODEL)) return rc;
     EpiArgs ep{n_q, nullptr, nullptr, 0, nullptr, nullptr, kv_partial, tile_cloud, cloud_row0, cloud_len, row_base,
                (layout & SCREAM_LAYOUT_C_FRAG) ? 1 : 0, (M / SCREAM_ROW_TILE) * SCREAM_NHEAD * (int64_t)KV_ELEMS,
                exp2i(k_exp), exp2i(v_exp), exp2i(-k_exp - v_exp)};
-    return launch_split<SCREAM_EPI_QKV>(A, lda, W_packed, Q, ldq, M, N, K, ep, as_stream(stream), layout & SCREAM_LAYOUT_A_FRAG, sa);
+    return launch_split<SCREAM_EPI_QKV>(A, lda, W_packed, Q, ldq, M, N, K, ep, as_stream(stream), layout & SCREAM_LAYOUT_A_FRAG, split,
+                                        a_exp, w_exp);
 }

@@ -44,6 +44,7 @@
 // x rows at a tile boundary, plain loads that hipcc waits for with vmcnt(0).
 #include <type_traits>
 
+#include "matrix_front.h"
 #include "ring.h"
 
 namespace {
@@ -53,7 +54,6 @@ constexpr int P_LB = 2;  // x segments per load batch at a tile boundary (two ba
 
 constexpr int P_KV_ELEMS = (SCREAM_HEAD_DIM + 1) * SCREAM_HEAD_DIM;  // 1056
 constexpr int P_SLAB_BYTES = 4 * P_KV_ELEMS * 4;                      // one K^T V tile + Ksum per wave
-constexpr int P_MAX_GRID = SCREAM_MAX_GRID;
 
 struct ProjArgs {
     const float* x;        // fragment-major [M, 256]
@@ -387,12 +387,12 @@ __global__ __launch_bounds__(TT, 1) void proj_ring_kernel(ProjArgs pa) {
 #pragma unroll
             for (int m = 0; m < GM; ++m) ride_q(acc[1], g, m);
     } else if (prev == 2) {
-        lds_only_barrier();  // every wave has read the previous head's slabs (the ride of the stage just finished)
+        lds_barrier();  // every wave has read the previous head's slabs (the ride of the stage just finished)
 #pragma unroll
         for (int g = 0; g < 14; ++g)
 #pragma unroll
             for (int m = 0; m < GM; ++m) ride_v(acc[1], g, m);
-        lds_only_barrier();
+        lds_barrier();
 #pragma unroll
         for (int g = 0; g < 9; ++g)
 #pragma unroll
@@ -429,25 +429,25 @@ __global__ void pack_proj_kernel(const float* __restrict__ W, int n_q, int S, fl
     for (int pl = 0; pl < SP::NP; ++pl) out[(((int64_t)stage * SP::NP + pl) * 16 + frag) * 64 + lane] = p[pl];
 }
 
-bool proj_split_ok(int32_t split) { return split == SCREAM_SPLIT_H2 || split == SCREAM_SPLIT_H1; }
-
 }  // namespace
 
+// (the ring kernel is built for the fp16 splits only)
 extern "C" int64_t scream_proj_image_bytes(int32_t N, int32_t split) {
-    if (!proj_split_ok(split) || N <= 0 || N % 64 != 0) return SCREAM_EINVAL;
+    if (!split_fp16(split) || N <= 0 || N % 64 != 0) return SCREAM_EINVAL;
     return (int64_t)(N / 32) * split * 16 * 1024;
 }
 
 extern "C" int scream_pack_proj(const float* W, int32_t N, int32_t n_q, int32_t split, int32_t w_exp, void* image, void* stream) {
-    SCREAM_REQUIRE(W && image && proj_split_ok(split), SCREAM_EINVAL);
+    SCREAM_REQUIRE(W && image && split_fp16(split), SCREAM_EINVAL);
     SCREAM_REQUIRE((n_q == 0 || n_q == SCREAM_D_MODEL) && N > n_q && (N - n_q) % 512 == 0, SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE(w_exp >= -60 && w_exp <= 60 && aligned16(image), SCREAM_EINVAL);
+    SCREAM_REQUIRE(operand_exp_ok(w_exp) && aligned16(image), SCREAM_EINVAL);
     const int S = N / 32;
     const dim3 grid(S * 16 * 64 / 256), block(256);
-    if (split == SCREAM_SPLIT_H2)
-        pack_proj_kernel<SplitH2><<<grid, block, 0, as_stream(stream)>>>(W, n_q, S, exp2i(w_exp), reinterpret_cast<f16x8*>(image));
-    else
-        pack_proj_kernel<SplitH1><<<grid, block, 0, as_stream(stream)>>>(W, n_q, S, exp2i(w_exp), reinterpret_cast<f16x8*>(image));
+    with_split(split, [&](auto tag) {
+        typedef typename decltype(tag)::type SP;
+        if constexpr (SP::SCALED)
+            pack_proj_kernel<SP><<<grid, block, 0, as_stream(stream)>>>(W, n_q, S, exp2i(w_exp), reinterpret_cast<f16x8*>(image));
+    });
     SCREAM_LAUNCH_CHECK();
     return 0;
 }
@@ -456,17 +456,13 @@ extern "C" int scream_proj_qkv_f32(const float* x, const void* proj_image, float
                                    const int32_t* tile_cloud, const int32_t* cloud_row0, const int32_t* cloud_len,
                                    int64_t row_base, float* kv_partial, int32_t split, int32_t a_exp, int32_t w_exp, int32_t k_exp,
                                    int32_t v_exp, void* stream) {
-    SCREAM_REQUIRE(x && proj_image && kv_partial && tile_cloud && cloud_row0 && cloud_len && proj_split_ok(split), SCREAM_EINVAL);
-    SCREAM_REQUIRE((n_q == 0 || n_q == SCREAM_D_MODEL) && N > n_q && (N - n_q) % 512 == 0 && (n_q == 0 || N == n_q + 512), SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE(M >= 0 && M % SCREAM_ROW_TILE == 0 && row_base >= 0 && row_base % SCREAM_ROW_TILE == 0, SCREAM_EUNSUPPORTED);
-    SCREAM_REQUIRE(n_q == 0 || Q, SCREAM_EINVAL);
-    SCREAM_REQUIRE(a_exp >= -60 && a_exp <= 60 && w_exp >= -60 && w_exp <= 60 && k_exp >= -40 && k_exp <= 40 && v_exp >= -40 && v_exp <= 40, SCREAM_EINVAL);
-    // the factors below combine them, and each must stay a normal fp32 power of two (exp2i), elu1s's c log2(e) included: with the
-    // ranges above only v_exp - a_exp - w_exp can leave [-126, 126] (it reaches +-160); the other two sums (at most 120 and 80 today)
-    // are checked as well so that widening a range above cannot let them through silently
-    const auto in126 = [](int e) { return e >= -126 && e <= 126; };
-    SCREAM_REQUIRE(in126(a_exp + w_exp) && in126(v_exp - a_exp - w_exp) && in126(k_exp + v_exp), SCREAM_EINVAL);
-    SCREAM_REQUIRE(aligned16(x) && aligned16(proj_image) && aligned16(Q) && aligned16(kv_partial), SCREAM_EINVAL);
+    SCREAM_REQUIRE(split_fp16(split), SCREAM_EINVAL);
+    // x and Q' are fragment-major [M,256] matrices: K, lda and ldq are the model width
+    if (int rc = check_qkv(x, SCREAM_D_MODEL, proj_image, Q, SCREAM_D_MODEL, M, N, SCREAM_D_MODEL, n_q, tile_cloud, cloud_row0, cloud_len,
+                           row_base, kv_partial, K_64_PLUS_192, true))
+        return rc;
+    SCREAM_REQUIRE(proj_exps_ok(a_exp, w_exp, k_exp, v_exp), SCREAM_EINVAL);
+    SCREAM_REQUIRE(aligned16(Q) && aligned16(kv_partial), SCREAM_EINVAL);
     if (M == 0) return 0;
     ProjArgs pa;
     pa.x = x;
@@ -486,10 +482,11 @@ extern "C" int scream_proj_qkv_f32(const float* x, const void* proj_image, float
     pa.kv_sk = exp2i(k_exp);
     pa.kv_cv = exp2i(-a_exp - w_exp + v_exp);
     pa.kv_inv = exp2i(-k_exp - v_exp);
-    const int64_t units = ((M + 255) / 256) * (pa.S / 2);
-    const unsigned grid = units < P_MAX_GRID ? (unsigned)units : (unsigned)P_MAX_GRID;
-    if (split == SCREAM_SPLIT_H2) proj_ring_kernel<SplitH2><<<dim3(grid), dim3(TT), 0, as_stream(stream)>>>(pa);
-    else proj_ring_kernel<SplitH1><<<dim3(grid), dim3(TT), 0, as_stream(stream)>>>(pa);
+    const int grid = persistent_grid(((M + 255) / 256) * (pa.S / 2), SCREAM_MAX_GRID, false);  // (the kernel numbers its units in 64 bits)
+    with_split(split, [&](auto tag) {
+        typedef typename decltype(tag)::type SP;
+        if constexpr (SP::SCALED) proj_ring_kernel<SP><<<dim3(grid), dim3(TT), 0, as_stream(stream)>>>(pa);
+    });
     SCREAM_LAUNCH_CHECK();
     return 0;
 }

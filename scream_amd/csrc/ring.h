@@ -1,7 +1,8 @@
 // Shared device helpers of the one-wave-per-SIMD kernel that streams its weights through a ring of LDS stages
-// (tail_split.hip: the row-local tail of a block), templated over the operand split (split.h): the ring's counted barrier,
-// LDS-DMA pieces with shared address registers, fragment reads, the MFMA group of one 16-deep step with its scheduling
-// pattern, and the inline-asm register loads (scalar base + 32-bit lane offset) with their hand-counted waits.
+// (tail_split.hip: the row-local tail of a block), templated over the operand split (split.h): LDS-DMA pieces with
+// shared address registers, fragment reads, the MFMA group of one 16-deep step with its scheduling pattern, and the inline-asm
+// register loads (scalar base + 32-bit lane offset) with their hand-counted waits.  (The ring's counted barrier is common.h's
+// ring_barrier, which the 8-wave GEMM shares.)
 #pragma once
 #include "split.h"
 
@@ -9,38 +10,19 @@ namespace {
 
 constexpr int T_PF = 3;  // register sets of weight fragments: fragments are read T_PF - 1 MFMA groups ahead
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 constexpr int TT = 256;               // threads
 constexpr int T_SLOTS = 3;
-constexpr int T_MAX_GRID = SCREAM_MAX_GRID;
 
 // one ring stage: 16 fragments of 1 KiB per operand plane (SplitBf3: 48 KiB, SplitH2: 32 KiB, SplitH1: 16 KiB); a wave issues a quarter of
 // its LDS-DMA pieces
 template <class SP> constexpr int stage_bytes() { return SP::NP * 16 * 1024; }
 template <class SP> constexpr int wave_pieces() { return SP::NP * 4; }
 
-// s_waitcnt vmcnt(N) lgkmcnt(0) + workgroup barrier (see gemm_split.hip): the N youngest vector-memory operations of
-// this wave -- the DMA pieces of the stage after the one about to be read -- stay in flight across the barrier.
-template <int N>
-__device__ __forceinline__ void ring_barrier() {
-    __builtin_amdgcn_s_waitcnt(0x0070 | (N & 15) | ((N >> 4) << 14));
-    __builtin_amdgcn_s_barrier();
-}
-
-__device__ __forceinline__ void lds_only_barrier() {  // lgkmcnt(0) + workgroup barrier, vector-memory queue untouched
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_s_barrier();
-}
-
 // Layout convention of every transposed tile in this file: accumulator tile blk, register i of lane (r, half) holds
 // feature 32 blk + mfma32_row(i, half) = 32 blk + 8 (i >> 2) + 4 half + (i & 3) of activation row r.  When such a tile
 // is the B operand of the next GEMM, registers 8 s2 .. 8 s2 + 7 are 16-deep step s2, so lane-half `half` supplies, as
 // element j of step s2, contraction index chunk_k(s2, half, j) of its 32-wide chunk.
 __host__ __device__ __forceinline__ int chunk_k(int s2, int half, int j) { return 8 * (2 * s2 + (j >> 2)) + 4 * half + (j & 3); }
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
 // One 1 KiB LDS-DMA piece, number k (0 .. 3) of a group of four that share their address registers: the instruction's
 // immediate offset moves the global source AND the LDS destination, so four pieces cost one address computation and

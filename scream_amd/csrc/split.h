@@ -194,4 +194,35 @@ static inline float exp2i(int e) {
     return v.f;
 }
 
+// ---- host side: the splits an entry point takes, the way from the runtime value to the policy type, the exponent ranges
+static inline bool split_fp16(int s) { return s == SCREAM_SPLIT_H2 || s == SCREAM_SPLIT_H1; }  // carries exponents
+static inline bool split_valid(int s) { return s == SCREAM_SPLIT_BF3 || split_fp16(s); }
+
+// f(SplitTag<SplitH2 / SplitH1 / SplitBf3>{}) for a split that split_valid() accepted.  A caller whose kernel is not built for
+// every split refuses the others first and guards the instantiation with `if constexpr` on the tag's type.
+template <class SP> struct SplitTag { typedef SP type; };
+template <class F>
+auto with_split(int split, F&& f) {
+    if (split == SCREAM_SPLIT_H2) return f(SplitTag<SplitH2>{});
+    if (split == SCREAM_SPLIT_H1) return f(SplitTag<SplitH1>{});
+    return f(SplitTag<SplitBf3>{});
+}
+
+// The ranges the arithmetic was checked for: an operand's or a weight's exponent (a_exp, w_exp); the exponent of K' / V in a
+// K^T V epilogue and each exponent of the layer tail (scream_tail_exps_t).
+static inline bool operand_exp_ok(int e) { return e >= -60 && e <= 60; }
+static inline bool kv_exp_ok(int e) { return e >= -40 && e <= 40; }
+// the fp16 splits take exponents in range, the bf16 split is scale free and ignores them
+static inline bool split_exps_ok(int split, int a_exp, int w_exp) {
+    return split == SCREAM_SPLIT_BF3 || (split_fp16(split) && operand_exp_ok(a_exp) && operand_exp_ok(w_exp));
+}
+// The ring projection combines its four exponents into factors that must each stay a normal fp32 power of two (exp2i), elu1s's
+// c log2(e) included: with the ranges above only v_exp - a_exp - w_exp can leave [-126, 126] (it reaches +-160); the other two
+// sums (at most 120 and 80 today) are checked as well so that widening a range cannot let them through silently.
+static inline bool in126(int e) { return e >= -126 && e <= 126; }
+static inline bool proj_exps_ok(int a_exp, int w_exp, int k_exp, int v_exp) {
+    return operand_exp_ok(a_exp) && operand_exp_ok(w_exp) && kv_exp_ok(k_exp) && kv_exp_ok(v_exp) && in126(a_exp + w_exp) &&
+           in126(v_exp - a_exp - w_exp) && in126(k_exp + v_exp);
+}
+
 }  // namespace

@@ -52,6 +52,7 @@
 // variants of this kernel; they were removed with their switches, last present in 9d64f79 -- tools/README.md.)
 #include <type_traits>
 
+#include "matrix_front.h"
 #include "ring.h"
 
 namespace {
@@ -379,7 +380,7 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
             // still be in flight, and nothing of this stage depends on them)
             // (NQ: the previous tile ended in ring stages whose last chunk's STORES are the youngest operations in the queue -- a counted
             // wait is only sound among loads, so this one barrier per tile drains)
-            if (h == 0) { if (NQ) ring_barrier<0>(); else lds_only_barrier(); }
+            if (h == 0) { if (NQ) ring_barrier<0>(); else lds_barrier(); }
             else ring_barrier<PIECES>();
             __builtin_amdgcn_sched_barrier(0);
             f32x4 (&x_prev)[4] = (h & 1) ? xs : xs2;   // segment h - 1 (landed: requested by stage h - 1)
@@ -681,7 +682,7 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
             constexpr int PP = (PIECES + NG - 9) / (NG - 8);  // weight pieces per group from group 8 on
             auto stage_q = [&](auto jj) {
                 constexpr int j = decltype(jj)::value;
-                if (j == 0) lds_only_barrier(); else ring_barrier<PIECES>();  // (stage 0: the queue was drained in front of norm2)
+                if (j == 0) lds_barrier(); else ring_barrier<PIECES>();  // (stage 0: the queue was drained in front of norm2)
                 __builtin_amdgcn_sched_barrier(0);
                 auto flush_q = [&]() {  // the deferred groups of chunk j - 1
                     if (j > 0) {
@@ -902,17 +903,15 @@ __global__ __launch_bounds__(KVF_THREADS) void kv_finalize_image_kernel(const fl
     }
 }
 
-bool split_ok(int32_t split) { return split == SCREAM_SPLIT_BF3 || split == SCREAM_SPLIT_H2 || split == SCREAM_SPLIT_H1; }
-
 // the kernel's factors from the six exponents; false if one leaves the range the arithmetic was checked for
 bool tail_scales(const scream_tail_exps_t* ex, TailScales* sc) {
     if (!ex) return false;
     const int es[6] = {ex->e_att, ex->e_wm, ex->e_m1, ex->e_w1, ex->e_h, ex->e_w2};
     for (int e : es)
-        if (e < -40 || e > 40) return false;
+        if (!kv_exp_ok(e)) return false;
     const int e1 = ex->e_wm + ex->e_att, e2 = ex->e_w2 + ex->e_h, eh = ex->e_h - ex->e_w1 - ex->e_m1;
     if (e1 < -44 || e1 > 44 || e2 < -44 || e2 > 44 || eh < -100 || eh > 100) return false;  // c^2 and c^2 * var stay finite in fp32
-    if (ex->e_q < -40 || ex->e_q > 40) return false;
+    if (!kv_exp_ok(ex->e_q)) return false;
     sc->s_att = exp2i(ex->e_att);
     sc->e_q = ex->e_q;
     sc->e_att = ex->e_att;
@@ -922,7 +921,7 @@ bool tail_scales(const scream_tail_exps_t* ex, TailScales* sc) {
     sc->ch = exp2i(eh);
     sc->c2 = exp2i(e2);
     sc->eps2 = 1e-5f * exp2i(2 * e2);
-    if (ex->e_y < -40 || ex->e_y > 40 || ex->e_wq < -40 || ex->e_wq > 40) return false;
+    if (!kv_exp_ok(ex->e_y) || !kv_exp_ok(ex->e_wq)) return false;
     sc->s_y = exp2i(ex->e_y);
     sc->cq = exp2i(-ex->e_y - ex->e_wq);
     return true;
@@ -931,29 +930,25 @@ bool tail_scales(const scream_tail_exps_t* ex, TailScales* sc) {
 }  // namespace
 
 extern "C" int64_t scream_tail_image_bytes(int32_t split, int32_t with_next_q) {
-    if (!split_ok(split) || (with_next_q && split == SCREAM_SPLIT_BF3)) return SCREAM_EINVAL;
+    if (!split_valid(split) || (with_next_q && !split_fp16(split))) return SCREAM_EINVAL;
     return (int64_t)(TAIL_STAGES + (with_next_q ? NEXT_Q_STAGES : 0)) * split * 16 * 1024;
 }
 extern "C" int64_t scream_kv_image_bytes(void) { return KV_IMAGE_BYTES; }
 
 extern "C" int scream_pack_tail(const float* Wm, const float* W1, const float* W2, const float* Wq_next, int32_t split,
                                 const scream_tail_exps_t* exps, void* image, void* stream) {
-    SCREAM_REQUIRE(Wm && W1 && W2 && image && split_ok(split), SCREAM_EINVAL);
-    SCREAM_REQUIRE(!Wq_next || split != SCREAM_SPLIT_BF3, SCREAM_EUNSUPPORTED);
+    SCREAM_REQUIRE(Wm && W1 && W2 && image && split_valid(split), SCREAM_EINVAL);
+    SCREAM_REQUIRE(!Wq_next || split_fp16(split), SCREAM_EUNSUPPORTED);
     SCREAM_REQUIRE(aligned16(image), SCREAM_EINVAL);
     const dim3 grid((TAIL_STAGES + (Wq_next ? NEXT_Q_STAGES : 0)) * 16 * 64 / 256), block(256);
-    if (split != SCREAM_SPLIT_BF3) {
-        TailScales sc;
-        SCREAM_REQUIRE(tail_scales(exps, &sc), SCREAM_EINVAL);
-        if (split == SCREAM_SPLIT_H2)
-            pack_tail_kernel<SplitH2><<<grid, block, 0, as_stream(stream)>>>(Wm, W1, W2, Wq_next, exp2i(exps->e_wm), exp2i(exps->e_w1),
-                                                                             exp2i(exps->e_w2), exp2i(exps->e_wq), reinterpret_cast<f16x8*>(image));
-        else
-            pack_tail_kernel<SplitH1><<<grid, block, 0, as_stream(stream)>>>(Wm, W1, W2, Wq_next, exp2i(exps->e_wm), exp2i(exps->e_w1),
-                                                                             exp2i(exps->e_w2), exp2i(exps->e_wq), reinterpret_cast<f16x8*>(image));
-    } else {
-        pack_tail_kernel<SplitBf3><<<grid, block, 0, as_stream(stream)>>>(Wm, W1, W2, nullptr, 1.f, 1.f, 1.f, 1.f, reinterpret_cast<bf16x8*>(image));
-    }
+    TailScales sc;
+    SCREAM_REQUIRE(!split_fp16(split) || tail_scales(exps, &sc), SCREAM_EINVAL);
+    const scream_tail_exps_t none{}, &e = split_fp16(split) ? *exps : none;  // bf16 x 3 is scale free: factors of 1 (exps may be null)
+    with_split(split, [&](auto tag) {
+        typedef typename decltype(tag)::type SP;
+        pack_tail_kernel<SP><<<grid, block, 0, as_stream(stream)>>>(Wm, W1, W2, Wq_next, exp2i(e.e_wm), exp2i(e.e_w1), exp2i(e.e_w2),
+                                                                    exp2i(e.e_wq), reinterpret_cast<typename SP::vec*>(image));
+    });
     SCREAM_LAUNCH_CHECK();
     return 0;
 }
@@ -961,62 +956,45 @@ extern "C" int scream_pack_tail(const float* Wm, const float* W1, const float* W
 extern "C" int scream_kv_finalize_image(const float* kv_partial, const int32_t* cloud_row0, const int32_t* cloud_len,
                                         int64_t row_base, int32_t cloud_begin, int32_t n_kv, void* kv_image, int32_t n_layers,
                                         int64_t partial_layer_stride, int64_t image_layer_stride, int32_t split, void* stream) {
-    SCREAM_REQUIRE(kv_partial && cloud_row0 && cloud_len && kv_image && split_ok(split), SCREAM_EINVAL);
+    SCREAM_REQUIRE(kv_partial && cloud_row0 && cloud_len && kv_image && split_valid(split), SCREAM_EINVAL);
     SCREAM_REQUIRE(n_kv >= 0 && cloud_begin >= 0 && row_base >= 0 && n_layers >= 1 && n_layers <= 65535, SCREAM_EINVAL);
     SCREAM_REQUIRE(n_layers == 1 || (partial_layer_stride > 0 && image_layer_stride > 0 && image_layer_stride % 16 == 0), SCREAM_EINVAL);
     SCREAM_REQUIRE(aligned16(kv_image) && aligned16(kv_partial) && partial_layer_stride % 4 == 0, SCREAM_EINVAL);
     if (n_kv == 0) return 0;
     const dim3 grid(n_kv * SCREAM_NHEAD, n_layers), block(KVF_THREADS);
-    if (split != SCREAM_SPLIT_BF3)
-        kv_finalize_image_kernel<true><<<grid, block, 0, as_stream(stream)>>>(kv_partial, cloud_row0, cloud_len, row_base, cloud_begin,
-                                                                              reinterpret_cast<char*>(kv_image), partial_layer_stride, image_layer_stride);
-    else
-        kv_finalize_image_kernel<false><<<grid, block, 0, as_stream(stream)>>>(kv_partial, cloud_row0, cloud_len, row_base, cloud_begin,
-                                                                               reinterpret_cast<char*>(kv_image), partial_layer_stride, image_layer_stride);
+    with_split(split, [&](auto tag) {
+        kv_finalize_image_kernel<decltype(tag)::type::SCALED><<<grid, block, 0, as_stream(stream)>>>(
+            kv_partial, cloud_row0, cloud_len, row_base, cloud_begin, reinterpret_cast<char*>(kv_image), partial_layer_stride, image_layer_stride);
+    });
     SCREAM_LAUNCH_CHECK();
     return 0;
 }
-
-namespace {
-template <class SP, bool NQ>
-void launch_tail(unsigned grid, hipStream_t st, const float* Q, const void* kv_image, const int32_t* tile_cloud, int32_t kv_cloud_offset,
-                 const int32_t* cloud_len, const float* x, const void* tail_image, const float* g1, const float* b1, const float* g2,
-                 const float* b2, float* y, float* q_next, int tiles, const TailScales& sc) {
-    tail_kernel<SP, NQ><<<dim3(grid), dim3(TT), 0, st>>>(Q, reinterpret_cast<const char*>(kv_image), tile_cloud, kv_cloud_offset, cloud_len, x,
-                                                     reinterpret_cast<const char*>(tail_image), g1, b1, g2, b2, y, q_next, tiles, sc);
-}
-}  // namespace
 
 extern "C" int scream_layer_tail_f32(const float* Q, const void* kv_image, const int32_t* tile_cloud,
                                      int32_t kv_cloud_offset, const int32_t* cloud_len, const float* x,
                                      const void* tail_image, const float* g1, const float* b1, const float* g2,
                                      const float* b2, float* y, float* q_next, int64_t M, int32_t split,
                                      const scream_tail_exps_t* exps, void* stream) {
-    SCREAM_REQUIRE(Q && kv_image && tile_cloud && cloud_len && x && tail_image && g1 && b1 && g2 && b2 && y && split_ok(split), SCREAM_EINVAL);
+    SCREAM_REQUIRE(Q && kv_image && tile_cloud && cloud_len && x && tail_image && g1 && b1 && g2 && b2 && y && split_valid(split), SCREAM_EINVAL);
     SCREAM_REQUIRE(M >= 0 && M % SCREAM_ROW_TILE == 0, SCREAM_EUNSUPPORTED);
     SCREAM_REQUIRE(aligned16(Q) && aligned16(kv_image) && aligned16(x) && aligned16(tail_image) && aligned16(g1) && aligned16(b1) &&
                        aligned16(g2) && aligned16(b2) && aligned16(y) && aligned16(q_next), SCREAM_EINVAL);
     SCREAM_REQUIRE(x != y, SCREAM_EINVAL);  // the residual of a row is read twice, long after its neighbours were written
     // q_next (the image then has its eight query stages): fp16 splits only; it may be Q itself, never x or y
-    SCREAM_REQUIRE(!q_next || (split != SCREAM_SPLIT_BF3 && q_next != x && q_next != y), SCREAM_EINVAL);
+    SCREAM_REQUIRE(!q_next || (split_fp16(split) && q_next != x && q_next != y), SCREAM_EINVAL);
     TailScales sc{1.f, 0, 0, 1.f, 1e-5f, 1.f, 1.f, 1.f, 1e-5f, 1.f, 1.f};
-    if (split != SCREAM_SPLIT_BF3) SCREAM_REQUIRE(tail_scales(exps, &sc), SCREAM_EINVAL);
+    SCREAM_REQUIRE(!split_fp16(split) || tail_scales(exps, &sc), SCREAM_EINVAL);
     const int64_t tiles = M / SCREAM_ROW_TILE;
-    if (tiles == 0) return 0;
-    SCREAM_REQUIRE(tiles < (1ll << 31), SCREAM_EUNSUPPORTED);
-    const unsigned grid = tiles < T_MAX_GRID ? (unsigned)tiles : (unsigned)T_MAX_GRID;
-    hipStream_t st = as_stream(stream);
-#define TAIL_ARGS grid, st, Q, kv_image, tile_cloud, kv_cloud_offset, cloud_len, x, tail_image, g1, b1, g2, b2, y, q_next, (int)tiles, sc
-    if (split == SCREAM_SPLIT_H2) {
-        if (q_next) launch_tail<SplitH2, true>(TAIL_ARGS);
-        else launch_tail<SplitH2, false>(TAIL_ARGS);
-    } else if (split == SCREAM_SPLIT_H1) {
-        if (q_next) launch_tail<SplitH1, true>(TAIL_ARGS);
-        else launch_tail<SplitH1, false>(TAIL_ARGS);
-    } else {
-        launch_tail<SplitBf3, false>(TAIL_ARGS);
-    }
-#undef TAIL_ARGS
+    const int grid = persistent_grid(tiles, SCREAM_MAX_GRID);
+    if (grid <= 0) return grid;
+    with_split(split, [&](auto tag) {
+        typedef typename decltype(tag)::type SP;
+        auto kernel = tail_kernel<SP, false>;
+        if constexpr (SP::SCALED) kernel = q_next ? tail_kernel<SP, true> : kernel;  // (on bf16 x 3 q_next was refused above: not built)
+        kernel<<<dim3(grid), dim3(TT), 0, as_stream(stream)>>>(Q, reinterpret_cast<const char*>(kv_image), tile_cloud, kv_cloud_offset, cloud_len,
+                                                               x, reinterpret_cast<const char*>(tail_image), g1, b1, g2, b2, y, q_next,
+                                                               (int)tiles, sc);
+    });
     SCREAM_LAUNCH_CHECK();
     return 0;
 }

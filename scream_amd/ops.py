@@ -215,6 +215,26 @@ def layer_tail(Q: torch.Tensor, kv_image: torch.Tensor, tile_cloud, kv_cloud_off
     return out
 
 
+def _qkv_outputs(x: torch.Tensor, N: int, n_q: int):
+    """(Q' or None, kv_partial) for N = n_q + 512 L columns; L > 1 key/value tile pairs (several layers, n_q == 0): [L,M/128,8,1056]."""
+    M, L = x.shape[0], (N - n_q) // 512
+    Q = torch.empty(M, n_q, device=x.device, dtype=torch.float32) if n_q else None
+    part = torch.empty((L, M // ROW_TILE, 8, KV_ELEMS) if L > 1 else (M // ROW_TILE, 8, KV_ELEMS), device=x.device, dtype=torch.float32)
+    return Q, part
+
+
+def _qkv_exps(x: torch.Tensor, row_l1: torch.Tensor, n_q: int, a_exp, k_exp, v_exp):
+    """Exponents left at None are measured (a device sync: tests and tools only, as for _a_exp): |k|, |v| <= max|x| * (L1 norm of
+    their weight rows); key rows are the first 128 of every 256 behind the queries (include/scream_hip.h)."""
+    if a_exp is None or k_exp is None or v_exp is None:
+        amax = float(x.abs().max().item())
+        rl = row_l1[n_q:].view(-1, 2, 128)
+        a_exp = scales.exp_for(amax) if a_exp is None else a_exp
+        k_exp = scales.exp_for(1.0 + amax * float(rl[:, 0].max())) if k_exp is None else k_exp
+        v_exp = scales.exp_for(amax * float(rl[:, 1].max())) if v_exp is None else v_exp
+    return int(a_exp), int(k_exp), int(v_exp)
+
+
 def gemm_qkv(A: torch.Tensor, W, n_q: int, tile_cloud, cloud_row0, cloud_len, row_base: int, layout: int = 0,
              a_exp: Optional[int] = None, k_exp: Optional[int] = None, v_exp: Optional[int] = None):
     """Fused q/k/v projection (scream_gemm_qkv_f32 / scream_gemm_qkv_split_f32 for W = pack_w(...)).  Returns
@@ -222,21 +242,13 @@ def gemm_qkv(A: torch.Tensor, W, n_q: int, tile_cloud, cloud_row0, cloud_len, ro
     M, K = A.shape
     sp = isinstance(W, PackedW)  # packed operand planes -> the split kernel
     N = W.N if sp else W.shape[0]
-    Q = torch.empty(M, n_q, device=A.device, dtype=torch.float32) if n_q else None
-    L = (N - n_q) // 512  # key/value tile pairs: > 1 for a batched projection of several layers (split kernel, n_q == 0)
-    part = torch.empty((L, M // ROW_TILE, 8, KV_ELEMS) if L > 1 else (M // ROW_TILE, 8, KV_ELEMS), device=A.device, dtype=torch.float32)
+    Q, part = _qkv_outputs(A, N, n_q)
     args = (_p(A), A.stride(0), W.data_ptr() if sp else _p(W), _p(Q), n_q, M, N, K, n_q,
             _p(tile_cloud, torch.int32), _p(cloud_row0, torch.int32), _p(cloud_len, torch.int32), row_base, _p(part))
     if sp:
-        if W.split != SPLIT_BF3 and (k_exp is None or v_exp is None):
-            # the K^T V epilogue's operands: |k|, |v| <= max|A| * (L1 norm of their weight rows); key rows are the first 128 of
-            # every 256 behind the queries (include/scream_hip.h).  Convenience default (a device sync), as for a_exp.
-            amax = float(A.abs().max().item())
-            rl = W.row_l1[n_q:].view(-1, 2, 128)
-            k_exp = scales.exp_for(1.0 + amax * float(rl[:, 0].max())) if k_exp is None else k_exp
-            v_exp = scales.exp_for(amax * float(rl[:, 1].max())) if v_exp is None else v_exp
-        check(_lib.load().scream_gemm_qkv_split_f32(*args, layout, W.split, _a_exp(A, W, a_exp), W.w_exp, int(k_exp or 0),
-                                                    int(v_exp or 0), _stream()),
+        # (bf16 x 3 is scale free: no exponent is read)
+        a_exp, k_exp, v_exp = (0, 0, 0) if W.split == SPLIT_BF3 else _qkv_exps(A, W.row_l1, n_q, a_exp, k_exp, v_exp)
+        check(_lib.load().scream_gemm_qkv_split_f32(*args, layout, W.split, a_exp, W.w_exp, k_exp, v_exp, _stream()),
               "scream_gemm_qkv_split_f32")
     else:
         assert layout == 0
@@ -279,18 +291,11 @@ def proj_qkv(x_frag: torch.Tensor, P: PackedProj, tile_cloud, cloud_row0, cloud_
     """The fused q/k/v projection on the ring kernel (scream_proj_qkv_f32): x and Q' fragment-major.  Returns (Q' or None,
     kv_partial) like gemm_qkv."""
     M = x_frag.shape[0]
-    Q = torch.empty(M, D_MODEL, device=x_frag.device, dtype=torch.float32) if P.n_q else None
-    L = (P.N - P.n_q) // 512
-    part = torch.empty((L, M // ROW_TILE, 8, KV_ELEMS) if L > 1 else (M // ROW_TILE, 8, KV_ELEMS), device=x_frag.device, dtype=torch.float32)
-    if a_exp is None or k_exp is None or v_exp is None:  # convenience defaults (a device sync): tests and tools only
-        amax = float(x_frag.abs().max().item())
-        rl = P.row_l1[P.n_q:].view(-1, 2, 128)
-        a_exp = scales.exp_for(amax) if a_exp is None else a_exp
-        k_exp = scales.exp_for(1.0 + amax * float(rl[:, 0].max())) if k_exp is None else k_exp
-        v_exp = scales.exp_for(amax * float(rl[:, 1].max())) if v_exp is None else v_exp
+    Q, part = _qkv_outputs(x_frag, P.N, P.n_q)  # (n_q is 0 or the model width)
+    a_exp, k_exp, v_exp = _qkv_exps(x_frag, P.row_l1, P.n_q, a_exp, k_exp, v_exp)
     check(_lib.load().scream_proj_qkv_f32(_p(x_frag), P.data_ptr(), _p(Q), M, P.N, P.n_q, _p(tile_cloud, torch.int32),
                                           _p(cloud_row0, torch.int32), _p(cloud_len, torch.int32), row_base, _p(part), P.split,
-                                          int(a_exp), P.w_exp, int(k_exp), int(v_exp), _stream()), "scream_proj_qkv_f32")
+                                          a_exp, P.w_exp, k_exp, v_exp, _stream()), "scream_proj_qkv_f32")
     return Q, part
 
 

@@ -182,6 +182,23 @@ def test_no_size_is_a_formula_and_no_alignment_check_is_spelled_out():
         assert not re.search(r"reinterpret_cast<uintptr_t>[^;]*&\s*15\b", text), f
 
 
+def test_the_matrix_front_end_is_written_once():
+    """In csrc the epilogue switch stands in one file (matrix_front.h), the split values are named in one file (split.h: the
+    predicates and with_split), the counted barrier, the 16-byte load and the lgkmcnt(0) barrier are defined once, the operand
+    exponent range is spelled once, and the layer tail's launch needs no argument macro.  In ops.py the default K' exponent of the
+    fused q/k/v projections is derived in one place."""
+    d = os.path.join(REPO, "scream_amd", "csrc")
+    texts = {f: open(os.path.join(d, f)).read() for f in sorted(os.listdir(d))}
+    files_with = lambda needle: [f for f, t in texts.items() if needle in t]
+    count = lambda needle: sum(t.count(needle) for t in texts.values())
+    assert files_with("case SCREAM_EPI_") == ["matrix_front.h"]
+    assert files_with("SCREAM_SPLIT_H1") == ["split.h"]
+    for needle in ("void ring_barrier(", "f32x4 ld4(", "0xC07F", ">= -60"):
+        assert count(needle) == 1, needle
+    assert count("TAIL_ARGS") == 0
+    assert open(os.path.join(REPO, "scream_amd", "ops.py")).read().count("exp_for(1.0 + amax") == 1
+
+
 def test_train_wrappers_size_their_scratch_through_ops_workspace():
     """train.wgrad_split stays importable (wgrad with split=SPLIT_BF3), and a weight gradient whose N the library refuses raises
     from the size function, with the arguments in the message, before any tensor is touched."""

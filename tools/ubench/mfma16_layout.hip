@@ -1,4 +1,4 @@
-// Layout check for the 16x16x32 path of tail_x3.hip: E-form operand planes -> v_permlane16_swap -> v_mfma_f32_16x16x32_bf16 ->
+// Layout check for the 16x16x32 path of tail_split.hip: E-form operand planes -> v_permlane16_swap -> v_mfma_f32_16x16x32_bf16 ->
 // swap back must give Y[row][feature] = sum_k W[feature][k] X[row][k] in the kernel's register convention.
 #include <hip/hip_runtime.h>
 #include <stdio.h>

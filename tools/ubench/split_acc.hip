@@ -1,5 +1,5 @@
 // Accuracy of operand-split GEMMs with the HARDWARE's own MFMA accumulation (round 3, step (b) of the fp16 plan):
-//   mode 0: 3 x bf16 planes, 6 products  (what gemm_x3.hip / tail_x3.hip do)
+//   mode 0: 3 x bf16 planes, 6 products  (what gemm_split.hip / tail_split.hip do with SplitBf3)
 //   mode 1: 2 x fp16 planes, 3 products  a1w0 + a0w1 + a0w0, operands pre-scaled by exact powers of two
 //   mode 2: 2 x fp16 planes, 4 products  (+ a1w1): how much the dropped term matters
 //   mode 3: 1 x fp16 plane               (the autocast mirror)
