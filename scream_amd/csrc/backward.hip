@@ -381,7 +381,7 @@ __global__ __launch_bounds__(512) void attn_bwd_partial_kernel(const float* __re
     float* out = part + (((int64_t)blockIdx.y * max_chunks + blockIdx.x) * NH + (threadIdx.x >> 6)) * KV_ELEMS;
     const int lane = threadIdx.x & 63, h = threadIdx.x >> 6;
     const int d = lane & 31, half = lane >> 5;
-    if (t0 >= len) {  // block-uniform: an empty chunk of a shorter cloud still leaves zeros (the final sum reads only real chunks)
+    if (t0 >= len) {  // block-uniform: an empty chunk of a shorter cloud writes nothing; attn_bwd_final_kernel reads only the real chunks
         return;
     }
     const int t1 = min(len, t0 + CHUNK);
