@@ -812,6 +812,99 @@ int scream_adam_step(const void* tensors, int32_t n_tensors, const int32_t* chun
                      const float* grad_scale, const float* found_inf, double lr, double beta1, double beta2, double eps,
                      void* stream);
 
+/* ---- The adversarial loss: the PatchGAN discriminator NLayerDiscriminator(input_nc, ndf, n_layers = 3) of models/gan.py:15-65,
+ * its backward, and the hinge losses of loss.py:31-35,53-66 (csrc/gan.hip; scream_amd/gan.py is the host layer, tests/gan_ref.py
+ * the float64 restatement).  Every tensor is contiguous NCHW fp32, weights are torch's [Cout,Cin,4,4]; no image of either is kept.
+ *
+ * Convolution (kernel 4, padding 1, stride s in {1, 2}):
+ *   y[n,co,oh,ow] = b[co] + sum over (ci, kh, kw) of w[co,ci,kh,kw] x[n,ci,oh s - 1 + kh,ow s - 1 + kw],  zero outside the image,
+ *   Ho = floor((H - 2) / s) + 1, Wo likewise from W; H and W independent, odd allowed, both >= 2.
+ * Forward, data gradient and weight gradient are implicit GEMMs on v_mfma_f32_32x32x2_f32: fp32 products, fp32 fma chains.  The
+ * contraction -- (ci,kh,kw) forward, (co,kh,kw) for dx, the pixels (n,oh,ow) for dw -- is cut into z equal ranges of whole
+ * 8-element steps, z a function of the shape alone; each range is summed in ascending index from 0, and a second launch adds
+ * the z partial results of an element in ascending range order, then the bias.  dbias[co] is the float64 block sum (below) of dy
+ * over n and the pixels.  No float atomics anywhere: two identical calls give identical bits.
+ *   scream_gan_conv_fwd    y = conv(x) (+ bias unless NULL), then x > 0 ? x : 0.2 x when leaky != 0
+ *   scream_gan_conv_dgrad  dx = the gradient of x for dy; with mask [n,cin,h,w] != NULL, dx *= (mask > 0 ? 1 : 0.2)
+ *   scream_gan_conv_wgrad  dw [cout,cin,4,4] and, unless NULL, dbias [cout]
+ * workspace: scream_gan_conv_workspace_bytes(mode, ...) bytes (mode 0 forward, 1 dgrad, 2 wgrad), 16-byte aligned, as must be w.
+ * SCREAM_EINVAL: null pointers, sizes not positive, a stride other than 1 or 2, a tensor of 2^30 elements or more, a short
+ * workspace.
+ *
+ * Float64 block sum of a channel (or of a whole tensor): the elements in the order n-major, pixel-minor; thread t of 256 adds
+ * elements t, t + 256, ... from 0.0; then v[t] += v[t + 128], v[t] += v[t + 64], ... v[0] += v[1].
+ *
+ * BatchNorm2d in training mode, fused with LeakyReLU(0.2) (scream_gan_bn_fwd), per channel over cnt = n hw values:
+ *   m = (sum x) / cnt, var = max((sum x^2) / cnt - m^2, 0) in float64 from the block sums; mean = fp32(m),
+ *   invstd = fp32(1 / sqrt(var + 1e-5));  z = ((x - mean) invstd) gamma + beta, each operation rounded to fp32;  y = z > 0 ? z : 0.2 z
+ *   running_mean = fp32(0.9 running_mean + 0.1 m), running_var = fp32(0.9 running_var + 0.1 var cnt / (cnt - 1)),
+ *   *num_batches_tracked += 1 (int64 on the device; may be NULL).  cnt == 1 is SCREAM_EINVAL, as torch refuses it.
+ * training == 0: mean = running_mean, invstd = fp32(1 / sqrt(running_var + 1e-5)), nothing is updated.
+ * scream_gan_bn_bwd, for dy the gradient of y: dz = dy (y > 0 ? 1 : 0.2) -- the mask is the saved output's sign --
+ *   dbeta = sum dz, dgamma = sum dz xhat (float64 block sums, xhat = fp32((x - mean) invstd) as the forward rounds it),
+ *   dx = fp32(gamma invstd ((dz - dbeta / cnt) - xhat (dgamma / cnt))) in float64.  sums: 2 c doubles of scratch, 8-byte aligned;
+ *   dgamma / dbeta may be NULL; dx may be dy.
+ *
+ * Losses, float64 block sums over all elements, one fp32 result on the device:
+ *   scream_gan_loss_g   loss = fp32(-(sum logits) / cnt);                 bwd: dlogits = fp32(-dout / cnt)
+ *   scream_gan_loss_d   loss = fp32(0.5 ((sum max(1 - real, 0)) / cnt_r + (sum max(1 + fake, 0)) / cnt_f)), 1 -+ x in fp32;
+ *                       bwd: dreal = 1 - real > 0 ? fp32(-(0.5 dout) / cnt_r) : 0,  dfake = 1 + fake > 0 ? fp32((0.5 dout) / cnt_f) : 0
+ *   (relu'(0) = 0).  dout: one fp32 on the DEVICE.
+ *
+ * The whole network on [n,cin,h,w] images: conv(s2, bias) leaky | conv(s2) bn leaky | conv(s2) bn leaky | conv(s1) bn leaky |
+ * conv(s1, bias) -> logits [n,1,.,.]; channels cin -> ndf -> 2 ndf -> 4 ndf -> 8 ndf -> 1.  Supported: 1 <= cin <= 4,
+ * ndf % 32 == 0, h and w >= 24 (SCREAM_EUNSUPPORTED otherwise).  workspace: scream_gan_workspace_bytes(n, cin, ndf, h, w) bytes,
+ * 16-byte aligned, one carve: the activations a pass keeps (each layer's convolution output and activated output, mean and
+ * invstd), two gradient buffers and the partial tiles of the convolution in flight.  scream_gan_backward takes the workspace
+ * of the forward pass it differentiates, untouched in its activation part, with the same x and parameters; several passes may be
+ * alive at once, each in its own workspace.  dx (may be NULL) and grads (may be NULL: then no weight gradient is computed) are
+ * written, not accumulated.  scream_gan_backward differentiates a training-mode forward only. */
+typedef struct {
+    const float* w[5];                /* main.0, main.2, main.5, main.8, main.11 .weight */
+    const float* b0;                  /* main.0.bias [ndf] */
+    const float* b4;                  /* main.11.bias [1] */
+    const float* gamma[3];            /* main.3, main.6, main.9 .weight */
+    const float* beta[3];             /*                        .bias */
+    float* running_mean[3];
+    float* running_var[3];
+    int64_t* num_batches_tracked[3];  /* each may be NULL */
+} scream_gan_params_t;
+typedef struct {
+    float* w[5];
+    float* b0;
+    float* b4;
+    float* gamma[3];
+    float* beta[3];
+} scream_gan_grads_t;
+int64_t scream_gan_conv_workspace_bytes(int32_t mode, int32_t n, int32_t cin, int32_t cout, int32_t h, int32_t w, int32_t stride);
+int scream_gan_conv_fwd(const float* x, const float* wt, const float* bias, int32_t n, int32_t cin, int32_t cout, int32_t h,
+                        int32_t w, int32_t stride, int32_t leaky, float* y, void* workspace, int64_t workspace_bytes, void* stream);
+int scream_gan_conv_dgrad(const float* dy, const float* wt, const float* mask, int32_t n, int32_t cin, int32_t cout, int32_t h,
+                          int32_t w, int32_t stride, float* dx, void* workspace, int64_t workspace_bytes, void* stream);
+int scream_gan_conv_wgrad(const float* x, const float* dy, int32_t n, int32_t cin, int32_t cout, int32_t h, int32_t w,
+                          int32_t stride, float* dw, float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
+int scream_gan_bn_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                      int64_t* num_batches_tracked, int32_t n, int32_t c, int32_t hw, int32_t training, float* y, float* mean,
+                      float* invstd, void* stream);
+int scream_gan_bn_bwd(const float* dy, const float* y, const float* x, const float* gamma, const float* mean, const float* invstd,
+                      int32_t n, int32_t c, int32_t hw, double* sums, float* dx, float* dgamma, float* dbeta, void* stream);
+int scream_gan_loss_g(const float* logits, int64_t cnt, float* loss, void* stream);
+int scream_gan_loss_g_bwd(const float* dout, int64_t cnt, float* dlogits, void* stream);
+int scream_gan_loss_d(const float* real, int64_t cnt_r, const float* fake, int64_t cnt_f, float* loss, void* stream);
+int scream_gan_loss_d_bwd(const float* dout, const float* real, int64_t cnt_r, const float* fake, int64_t cnt_f, float* dreal,
+                          float* dfake, void* stream);
+/* The ground-truth source rows that the `real` images are rendered from (train_3d_match.py:198), for every pair of a packed
+ * batch in one launch: out[row] = ((R[k][0] x + R[k][1] y) + R[k][2] z) + t[k] in fp32, R = rot [n_pairs,9] and t = trans
+ * [n_pairs,3] of pair tile_cloud[row / 128], over the rows_src packed source rows (a multiple of 128) of xyz. */
+int scream_pairs_transform(const float* xyz, const float* rot, const float* trans, const int32_t* tile_cloud, int32_t n_pairs,
+                           int64_t rows_src, float* out, void* stream);
+int64_t scream_gan_workspace_bytes(int32_t n, int32_t cin, int32_t ndf, int32_t h, int32_t w);
+int scream_gan_forward(const float* x, const scream_gan_params_t* params, int32_t n, int32_t cin, int32_t ndf, int32_t h, int32_t w,
+                       int32_t training, float* logits, void* workspace, int64_t workspace_bytes, void* stream);
+int scream_gan_backward(const float* dlogits, const float* x, const scream_gan_params_t* params, int32_t n, int32_t cin,
+                        int32_t ndf, int32_t h, int32_t w, void* workspace, int64_t workspace_bytes, float* dx,
+                        const scream_gan_grads_t* grads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

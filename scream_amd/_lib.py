@@ -51,6 +51,15 @@ class BatchT(C.Structure):
                 ("tile_cloud", C.c_void_p), ("cloud_row0", C.c_void_p), ("cloud_len", C.c_void_p)]
 
 
+class GanParamsT(C.Structure):
+    _fields_ = [("w", C.c_void_p * 5), ("b0", C.c_void_p), ("b4", C.c_void_p), ("gamma", C.c_void_p * 3), ("beta", C.c_void_p * 3),
+                ("running_mean", C.c_void_p * 3), ("running_var", C.c_void_p * 3), ("num_batches_tracked", C.c_void_p * 3)]
+
+
+class GanGradsT(C.Structure):
+    _fields_ = [("w", C.c_void_p * 5), ("b0", C.c_void_p), ("b4", C.c_void_p), ("gamma", C.c_void_p * 3), ("beta", C.c_void_p * 3)]
+
+
 # name -> (restype, argtypes); every symbol include/scream_hip.h declares
 V, I32, I64, F32, F64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 SIGNATURES = {
@@ -131,6 +140,20 @@ SIGNATURES = {
     "scream_icp_raw_range": (C.c_int, [V, V, V, V, V, V, I32, I32, I32, I64, I64, F64, I32, F64, F64, V, V, V, I32, I32, V, V, I64, V]),
     "scream_icp_raw_nn": (C.c_int, [V, V, V, V, V, V, I32, I32, I32, I64, I64, F64, V, V, V, V, V, I64, V]),
     "scream_adam_step": (C.c_int, [V, I32, V, I64, V, V, V, F64, F64, F64, F64, V]),
+    "scream_gan_conv_workspace_bytes": (C.c_int64, [I32, I32, I32, I32, I32, I32, I32]),
+    "scream_gan_conv_fwd": (C.c_int, [V, V, V, I32, I32, I32, I32, I32, I32, I32, V, V, I64, V]),
+    "scream_gan_conv_dgrad": (C.c_int, [V, V, V, I32, I32, I32, I32, I32, I32, V, V, I64, V]),
+    "scream_gan_conv_wgrad": (C.c_int, [V, V, I32, I32, I32, I32, I32, I32, V, V, V, I64, V]),
+    "scream_gan_bn_fwd": (C.c_int, [V, V, V, V, V, V, I32, I32, I32, I32, V, V, V, V]),
+    "scream_gan_bn_bwd": (C.c_int, [V, V, V, V, V, V, I32, I32, I32, V, V, V, V, V]),
+    "scream_gan_loss_g": (C.c_int, [V, I64, V, V]),
+    "scream_gan_loss_g_bwd": (C.c_int, [V, I64, V, V]),
+    "scream_gan_loss_d": (C.c_int, [V, I64, V, I64, V, V]),
+    "scream_gan_loss_d_bwd": (C.c_int, [V, V, I64, V, I64, V, V, V]),
+    "scream_pairs_transform": (C.c_int, [V, V, V, V, I32, I64, V, V]),
+    "scream_gan_workspace_bytes": (C.c_int64, [I32, I32, I32, I32, I32]),
+    "scream_gan_forward": (C.c_int, [V, C.POINTER(GanParamsT), I32, I32, I32, I32, I32, I32, V, V, I64, V]),
+    "scream_gan_backward": (C.c_int, [V, V, C.POINTER(GanParamsT), I32, I32, I32, I32, I32, V, I64, V, C.POINTER(GanGradsT), V]),
 }
 
 _lib: Optional[C.CDLL] = None

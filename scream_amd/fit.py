@@ -11,19 +11,27 @@ PreparedPairs (PointTransformer: the loss is net.loss_packed(pred, prepared)) or
 (DEMTransformer: net.loss_packed(pred, batch, target)).  The per-step losses of an epoch are written into a device vector and
 copied to the host once, when the epoch ends; its mean is taken in float64 on the host.  The mean is over steps, as in the
 reference (which runs batch_size = 1): with a short last batch it is the mean of the batch means.
+
+The reference's use_GAN = True is fit(..., gan=GanTraining(AdversarialLoss().to(dev), opt_d, pair_real_rows)): train_epoch_gan adds
+the rendered images, the HIP discriminator of scream_amd/gan.py and its own optimiser step to every step, still with nothing read
+back inside an epoch.
 """
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
 from typing import Callable, Iterable, List, Optional, Tuple
 
 import numpy as np
 import torch
 
+from . import ops
 from .packing import PackedBatch
 from .prep import PreparedPairs, prepare_3dmatch_train, prepare_3dmatch_val, prepare_kitti_train, prepare_kitti_val
+from .render import render_packed_train
 
-__all__ = ["lr_after_epoch", "train_epoch", "val_loss", "fit", "pair_preparer", "dem_preparer"]
+__all__ = ["lr_after_epoch", "train_epoch", "train_epoch_gan", "val_loss", "fit", "pair_preparer", "dem_preparer", "render_rows",
+           "pair_real_rows", "dem_real_rows", "GanTraining", "gan_training"]
 
 
 def lr_after_epoch(lr: float, epoch: int, gamma: float = 0.5, every: int = 15, floor: float = 1e-5) -> float:
@@ -66,6 +74,18 @@ def _batch_of(prepared) -> PackedBatch:
     return prepared.batch if isinstance(prepared, PreparedPairs) else prepared[0]
 
 
+def _step(loss, opt, scaler):
+    """zero_grad, backward, step; through `scaler` (scale, step, update) when one is given."""
+    opt.zero_grad()
+    if scaler is None:
+        loss.backward()
+        opt.step()
+    else:
+        scaler.scale(loss).backward()
+        scaler.step(opt)
+        scaler.update()
+
+
 def train_epoch(net, opt, batches: Iterable, prepare: Callable, scaler=None) -> Tuple[float, np.ndarray]:
     """One pass over `batches`: prepare, forward_packed_train, loss_packed, zero_grad, backward, step (through `scaler`, a
     torch.amp.GradScaler, when one is given).  Returns (the float64 mean of the per-step losses, the fp32 losses)."""
@@ -74,14 +94,7 @@ def train_epoch(net, opt, batches: Iterable, prepare: Callable, scaler=None) -> 
     for raw in batches:
         prepared = prepare(raw)
         loss = _loss(net, net.forward_packed_train(_batch_of(prepared)), prepared)
-        opt.zero_grad()
-        if scaler is None:
-            loss.backward()
-            opt.step()
-        else:
-            scaler.scale(loss).backward()
-            scaler.step(opt)
-            scaler.update()
+        _step(loss, opt, scaler)
         log.add(loss)
     losses = log.host()
     return _mean(losses), losses
@@ -99,28 +112,113 @@ def val_loss(net, batches: Iterable, prepare: Callable) -> Tuple[float, np.ndarr
     return _mean(losses), losses
 
 
+def render_rows(net, rows: torch.Tensor, prepared) -> torch.Tensor:
+    """The depth images of the packed source rows `rows` [rows_src,3] against the batch's target clouds, through net.generator's
+    views: [B*V, 2, w, w], with a grad_fn into `rows` when they carry one (pointnet.py:62-65 for every pair of the batch)."""
+    batch, gen = _batch_of(prepared), net.generator
+    return render_packed_train(rows, batch.src_row0, batch.src_len_dev, batch.xyz, batch.tgt_row0, batch.tgt_len_dev, max(batch.src_len),
+                               max(batch.tgt_len), gen.eulers, gen.w, gen.rho, rot=gen.view_matrices(rows.device))
+
+
+def pair_real_rows(prepared: PreparedPairs) -> torch.Tensor:
+    """real_rows of PointTransformer: the ground-truth source R x + t of every pair over the packed rows (train_3d_match.py:198),
+    one launch."""
+    b = prepared.batch
+    return ops.pairs_transform(b.xyz, prepared.rot, prepared.trans, b.tile_cloud, b.n_pairs, b.rows_src)
+
+
+def dem_real_rows(prepared) -> torch.Tensor:
+    """real_rows of DEMTransformer: the packed ground-truth DEM as it is (train_open_gf.py's real = generator(dem, dem_coarse))."""
+    return prepared[1]
+
+
+@dataclass
+class GanTraining:
+    """What fit(gan=...) needs besides the generator's: the AdversarialLoss, the discriminator's optimiser, real_rows(prepared)
+    (pair_real_rows / dem_real_rows), where to save the discriminator (whenever the generator checkpoint is written; None:
+    nowhere) and the weight of g_loss (0.1, train_3d_match.py:189)."""
+    loss: torch.nn.Module
+    opt: torch.optim.Optimizer
+    real_rows: Callable
+    save_path: Optional[str] = None
+    g_weight: float = 0.1
+
+
+def gan_training(device, real_rows: Callable, lr_d: float = 1e-4, betas=(0.5, 0.999), save_path: Optional[str] = None) -> GanTraining:
+    """What the reference's drivers build under use_GAN (train_3d_match.py:24-26,40-41): an AdversarialLoss on `device` and Adam
+    at lr_d with betas (0.5, 0.999) over its parameters, here a FusedAdam."""
+    from .gan import AdversarialLoss
+    from .optim import FusedAdam
+    loss = AdversarialLoss().to(device)
+    return GanTraining(loss, FusedAdam(loss.parameters(), lr=lr_d, betas=betas), real_rows, save_path)
+
+
+def train_epoch_gan(net, gan_loss, opt_g, opt_d, batches: Iterable, prepare: Callable, real_rows: Callable, scaler=None,
+                    g_weight: float = 0.1) -> Tuple[float, np.ndarray]:
+    """train_epoch with the adversarial loss, in the reference's order (train_3d_match.py:171-205), every step:
+      1. forward_packed_train;
+      2. the prediction's images through render_rows;
+      3. loss = point_loss + g_weight * g_loss, g_loss = gan_loss(imgs, None, 0); opt_g.zero_grad(), backward, opt_g.step();
+      4. real = the images of real_rows(prepared), the ground-truth source rows, rendered under no_grad;
+      5. d_loss = gan_loss(imgs.detach(), real, 1); opt_d.zero_grad(), backward, opt_d.step().
+    With a `scaler` both updates go scale(loss).backward(), step(opt), update(), as train_kitti.py:185-204 writes them.
+    With B pairs and V views the discriminator sees B * V images per call and its batch statistics run over all of them: the
+    batch form of the reference's loop, which runs batch size 1 (V images per call); at B = 1 the two coincide.
+    Returns (the float64 mean of the per-step generator losses -- point_loss + g_weight * g_loss, what the reference reports --
+    and the fp32 losses [steps,3]: that loss, g_loss, d_loss), copied to the host once, when the epoch ends."""
+    net.train()
+    gan_loss.train()
+    logs = [_LossLog(batches) for _ in range(3)]
+    for raw in batches:
+        prepared = prepare(raw)
+        pred = net.forward_packed_train(_batch_of(prepared))
+        imgs = render_rows(net, pred, prepared)
+        g = gan_loss(imgs, None, 0)
+        loss = _loss(net, pred, prepared) + g_weight * g
+        _step(loss, opt_g, scaler)
+        with torch.no_grad():
+            real = render_rows(net, real_rows(prepared), prepared)
+        d = gan_loss(imgs.detach(), real, 1)
+        _step(d, opt_d, scaler)
+        for lg, v in zip(logs, (loss, g, d)):
+            lg.add(v)
+    losses = np.stack([lg.host() for lg in logs], axis=1)
+    return _mean(losses[:, 0]), losses
+
+
 def fit(net, opt, train_batches: Iterable, val_batches: Iterable, prepare_train: Callable, prepare_val: Callable, epochs: int,
-        save_path: str, scaler=None, gamma: float = 0.5, every: int = 15, floor: float = 1e-5, log: Optional[Callable] = print) -> List[dict]:
+        save_path: str, scaler=None, gamma: float = 0.5, every: int = 15, floor: float = 1e-5, log: Optional[Callable] = print,
+        gan: Optional[GanTraining] = None) -> List[dict]:
     """The reference's train(): for epoch in range(1, epochs) -- as it writes it, epochs - 1 passes -- a training epoch, the
     validation loss, a checkpoint (net.state_dict(), what the reference's models load) whenever that loss improves on the best so
     far, then the learning-rate rule.  Returns one dict per epoch: epoch, train_loss, val_loss, saved, lr (the rate after the
-    epoch)."""
+    epoch).  gan: a GanTraining turns the epoch into train_epoch_gan (the reference's use_GAN = True); the dicts then also carry
+    g_loss and d_loss (epoch means), the discriminator is saved with the generator, and its rate is left alone, as the reference
+    only ever updates optimizer_G's."""
     best = 1e8  # train_3d_match.py:157
     history = []
     for epoch in range(1, epochs):
-        train_loss, _ = train_epoch(net, opt, train_batches, prepare_train, scaler)
+        extra = {}
+        if gan is None:
+            train_loss, _ = train_epoch(net, opt, train_batches, prepare_train, scaler)
+        else:
+            train_loss, steps = train_epoch_gan(net, gan.loss, opt, gan.opt, train_batches, prepare_train, gan.real_rows, scaler, gan.g_weight)
+            extra = dict(g_loss=_mean(steps[:, 1]), d_loss=_mean(steps[:, 2]))
         v, _ = val_loss(net, val_batches, prepare_val)
         saved = v < best
         if saved:
             best = v
-            if os.path.dirname(save_path):
-                os.makedirs(os.path.dirname(save_path), exist_ok=True)
-            torch.save(net.state_dict(), save_path)
+            for path, module in ((save_path, net),) + (((gan.save_path, gan.loss.discriminator),) if gan is not None and gan.save_path else ()):
+                if os.path.dirname(path):
+                    os.makedirs(os.path.dirname(path), exist_ok=True)
+                torch.save(module.state_dict(), path)
         for group in opt.param_groups:
             group["lr"] = lr_after_epoch(group["lr"], epoch, gamma, every, floor)
-        history.append(dict(epoch=epoch, train_loss=train_loss, val_loss=v, saved=saved, lr=opt.param_groups[0]["lr"]))
+        history.append(dict(epoch=epoch, train_loss=train_loss, val_loss=v, saved=saved, lr=opt.param_groups[0]["lr"], **extra))
         if log is not None:
-            log("epoch: %d  loss: %.5f  val loss: %.5f  lr: %.6f%s" % (epoch, train_loss, v, opt.param_groups[0]["lr"], "  saved" if saved else ""))
+            log("epoch: %d  loss: %.5f  val loss: %.5f  lr: %.6f%s%s" % (epoch, train_loss, v, opt.param_groups[0]["lr"],
+                                                                       "".join("  %s: %.5f" % kv for kv in extra.items()),
+                                                                       "  saved" if saved else ""))
     return history
 
 

@@ -719,3 +719,162 @@ class IcpRun(PiecewiseRun):
     def _enqueue(self, begin: int, end: int) -> None:
         check(self._fn(*self._args, begin, end, _p(self.flags, torch.int32), self.ws.data_ptr(), self.ws.numel(), _stream()),
               self._fn_name)
+
+
+# ---- the adversarial loss (csrc/gan.hip): contiguous NCHW fp32 tensors, torch's [Cout,Cin,4,4] weights
+GAN_FWD, GAN_DGRAD, GAN_WGRAD = 0, 1, 2
+
+
+def _conv_out(h: int, w: int, stride: int) -> Tuple[int, int]:
+    return (h - 2) // stride + 1, (w - 2) // stride + 1
+
+
+def _gan_conv_ws(mode: int, n, cin, cout, h, w, stride, device) -> torch.Tensor:
+    return _workspace(_lib.load().scream_gan_conv_workspace_bytes, "scream_gan_conv_workspace_bytes", mode, n, cin, cout, h, w, stride,
+                      device=device)
+
+
+def gan_conv_fwd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], stride: int, leaky: bool = False) -> torch.Tensor:
+    """scream_gan_conv_fwd: conv(k4, p1, stride) of x [n,cin,h,w] (+ bias, then LeakyReLU 0.2 when asked) -> [n,cout,ho,wo]."""
+    n, cin, h, w = x.shape
+    cout = weight.shape[0]
+    ho, wo = _conv_out(h, w, stride)
+    y = torch.empty(n, cout, ho, wo, device=x.device, dtype=torch.float32)
+    ws = _gan_conv_ws(GAN_FWD, n, cin, cout, h, w, stride, x.device)
+    check(_lib.load().scream_gan_conv_fwd(_p(x), _p(weight), _p(bias), n, cin, cout, h, w, stride, int(leaky), _p(y), ws.data_ptr(),
+                                          ws.numel(), _stream()), "scream_gan_conv_fwd")
+    return y
+
+
+def gan_conv_dgrad(dy: torch.Tensor, weight: torch.Tensor, h: int, w: int, stride: int, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """scream_gan_conv_dgrad: the gradient of the [n,cin,h,w] input for dy; `mask` (the input's shape): times (mask > 0 ? 1 : 0.2)."""
+    n, cout = dy.shape[0], dy.shape[1]
+    cin = weight.shape[1]
+    dx = torch.empty(n, cin, h, w, device=dy.device, dtype=torch.float32)
+    ws = _gan_conv_ws(GAN_DGRAD, n, cin, cout, h, w, stride, dy.device)
+    check(_lib.load().scream_gan_conv_dgrad(_p(dy), _p(weight), _p(mask), n, cin, cout, h, w, stride, _p(dx), ws.data_ptr(), ws.numel(),
+                                            _stream()), "scream_gan_conv_dgrad")
+    return dx
+
+
+def gan_conv_wgrad(x: torch.Tensor, dy: torch.Tensor, stride: int, want_bias: bool = False):
+    """scream_gan_conv_wgrad: (dw [cout,cin,4,4], dbias [cout] or None)."""
+    n, cin, h, w = x.shape
+    cout = dy.shape[1]
+    dw = torch.empty(cout, cin, 4, 4, device=x.device, dtype=torch.float32)
+    db = torch.empty(cout, device=x.device, dtype=torch.float32) if want_bias else None
+    ws = _gan_conv_ws(GAN_WGRAD, n, cin, cout, h, w, stride, x.device)
+    check(_lib.load().scream_gan_conv_wgrad(_p(x), _p(dy), n, cin, cout, h, w, stride, _p(dw), _p(db), ws.data_ptr(), ws.numel(),
+                                            _stream()), "scream_gan_conv_wgrad")
+    return dw, db
+
+
+def gan_bn_fwd(x: torch.Tensor, gamma, beta, running_mean, running_var, num_batches_tracked, training: bool = True):
+    """scream_gan_bn_fwd: BatchNorm2d + LeakyReLU(0.2) of x [n,c,h,w]; the running statistics are updated in place in training
+    mode.  Returns (y, mean [c], invstd [c])."""
+    n, c = x.shape[0], x.shape[1]
+    hw = x.shape[2] * x.shape[3]
+    if training and n * hw == 1:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
+    y = torch.empty_like(x)
+    mean = torch.empty(c, device=x.device, dtype=torch.float32)
+    invstd = torch.empty(c, device=x.device, dtype=torch.float32)
+    check(_lib.load().scream_gan_bn_fwd(_p(x), _p(gamma), _p(beta), _p(running_mean), _p(running_var),
+                                        _p(num_batches_tracked, torch.int64), n, c, hw, int(training), _p(y), _p(mean), _p(invstd),
+                                        _stream()), "scream_gan_bn_fwd")
+    return y, mean, invstd
+
+
+def gan_bn_bwd(dy: torch.Tensor, y: torch.Tensor, x: torch.Tensor, gamma, mean, invstd):
+    """scream_gan_bn_bwd: (dx, dgamma, dbeta) for dy, the gradient of gan_bn_fwd's y."""
+    n, c = x.shape[0], x.shape[1]
+    dx = torch.empty_like(x)
+    dgamma, dbeta = torch.empty_like(mean), torch.empty_like(mean)
+    sums = torch.empty(2 * c, device=x.device, dtype=torch.float64)
+    check(_lib.load().scream_gan_bn_bwd(_p(dy), _p(y), _p(x), _p(gamma), _p(mean), _p(invstd), n, c, x.shape[2] * x.shape[3],
+                                        _p(sums, torch.float64), _p(dx), _p(dgamma), _p(dbeta), _stream()), "scream_gan_bn_bwd")
+    return dx, dgamma, dbeta
+
+
+def gan_loss_g(logits: torch.Tensor) -> torch.Tensor:
+    loss = torch.empty((), device=logits.device, dtype=torch.float32)
+    check(_lib.load().scream_gan_loss_g(_p(logits), logits.numel(), _p(loss), _stream()), "scream_gan_loss_g")
+    return loss
+
+
+def gan_loss_g_bwd(dout: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    d = torch.empty_like(like)
+    check(_lib.load().scream_gan_loss_g_bwd(_p(dout), d.numel(), _p(d), _stream()), "scream_gan_loss_g_bwd")
+    return d
+
+
+def gan_loss_d(real: torch.Tensor, fake: torch.Tensor) -> torch.Tensor:
+    loss = torch.empty((), device=real.device, dtype=torch.float32)
+    check(_lib.load().scream_gan_loss_d(_p(real), real.numel(), _p(fake), fake.numel(), _p(loss), _stream()), "scream_gan_loss_d")
+    return loss
+
+
+def gan_loss_d_bwd(dout: torch.Tensor, real: torch.Tensor, fake: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    dr, df = torch.empty_like(real), torch.empty_like(fake)
+    check(_lib.load().scream_gan_loss_d_bwd(_p(dout), _p(real), real.numel(), _p(fake), fake.numel(), _p(dr), _p(df), _stream()),
+          "scream_gan_loss_d_bwd")
+    return dr, df
+
+
+def pairs_transform(xyz: torch.Tensor, rot: torch.Tensor, trans: torch.Tensor, tile_cloud: torch.Tensor, n_pairs: int,
+                    rows_src: int) -> torch.Tensor:
+    """scream_pairs_transform: R_p x + t_p on the packed source rows of every pair, one launch -> [rows_src,3]."""
+    out = torch.empty(rows_src, 3, device=xyz.device, dtype=torch.float32)
+    check(_lib.load().scream_pairs_transform(_p(xyz), _p(rot.reshape(n_pairs, 9)), _p(trans.reshape(n_pairs, 3)),
+                                             _p(tile_cloud, torch.int32), int(n_pairs), int(rows_src), _p(out), _stream()),
+          "scream_pairs_transform")
+    return out
+
+
+def _gan_struct(cls, fields: dict):
+    s = cls()
+    for name, value in fields.items():
+        if isinstance(value, (list, tuple)):
+            arr = getattr(s, name)
+            for i, t in enumerate(value):
+                arr[i] = t
+        else:
+            setattr(s, name, value)
+    return s
+
+
+def gan_params(weights, b0, b4, gammas, betas, running_means, running_vars, nbts) -> "_lib.GanParamsT":
+    """The scream_gan_params_t of a discriminator's tensors (the caller keeps them alive)."""
+    return _gan_struct(_lib.GanParamsT, dict(w=[_p(t) for t in weights], b0=_p(b0), b4=_p(b4), gamma=[_p(t) for t in gammas],
+                                             beta=[_p(t) for t in betas], running_mean=[_p(t) for t in running_means],
+                                             running_var=[_p(t) for t in running_vars],
+                                             num_batches_tracked=[_p(t, torch.int64) for t in nbts]))
+
+
+def gan_workspace(n: int, cin: int, ndf: int, h: int, w: int, device) -> torch.Tensor:
+    return _workspace(_lib.load().scream_gan_workspace_bytes, "scream_gan_workspace_bytes", n, cin, ndf, h, w, device=device)
+
+
+def gan_forward(x: torch.Tensor, params, ndf: int, training: bool, workspace: torch.Tensor) -> torch.Tensor:
+    """scream_gan_forward: logits [n,1,h5,w5]; the workspace keeps the pass's activations for gan_backward."""
+    n, cin, h, w = x.shape
+    for s in (2, 2, 2, 1, 1):
+        h, w = _conv_out(h, w, s)
+    logits = torch.empty(n, 1, h, w, device=x.device, dtype=torch.float32)
+    check(_lib.load().scream_gan_forward(_p(x), C.byref(params), n, cin, int(ndf), x.shape[2], x.shape[3], int(training), _p(logits),
+                                         workspace.data_ptr(), workspace.numel(), _stream()), "scream_gan_forward")
+    return logits
+
+
+def gan_backward(dlogits: torch.Tensor, x: torch.Tensor, params, ndf: int, workspace: torch.Tensor, want_dx: bool, grads):
+    """scream_gan_backward: dx (or None); `grads` is a list of the 13 gradient tensors in the order (w x 5, b0, b4, gamma x 3,
+    beta x 3) to be written, or None for no parameter gradient."""
+    n, cin, h, w = x.shape
+    dx = torch.empty_like(x) if want_dx else None
+    g = None
+    if grads is not None:
+        g = C.byref(_gan_struct(_lib.GanGradsT, dict(w=[_p(t) for t in grads[0:5]], b0=_p(grads[5]), b4=_p(grads[6]),
+                                                     gamma=[_p(t) for t in grads[7:10]], beta=[_p(t) for t in grads[10:13]])))
+    check(_lib.load().scream_gan_backward(_p(dlogits), _p(x), C.byref(params), n, cin, int(ndf), h, w, workspace.data_ptr(),
+                                          workspace.numel(), _p(dx), g, _stream()), "scream_gan_backward")
+    return dx

@@ -137,3 +137,39 @@ def render_packed(src: torch.Tensor, s_row0, s_len, tgt: torch.Tensor, t_row0, t
     """B pairs in one launch set (no autograd): packed rows as ops.render_depth takes them -> imgs [B, V, 2, w, w]."""
     rot = torch.stack([rotation_matrix(e) for e in eulers]).to(src.device)
     return ops.render_depth(src, s_row0, s_len, tgt, t_row0, t_len, max_s_len, max_t_len, rot, w, rho)[0]
+
+
+class _RenderPackedFn(torch.autograd.Function):
+    """imgs [B*V,2,w,w] of B packed pairs; the backward is the packed scream_render_depth_bwd."""
+
+    @staticmethod
+    def forward(ctx, src, s_row0, s_len, tgt, t_row0, t_len, max_s_len, max_t_len, rot, w, rho):
+        src = src.detach().to(torch.float32).contiguous()
+        tgt = tgt.detach().to(torch.float32).contiguous()
+        B, V = s_row0.shape[0], rot.shape[0]
+        ws = ops.render_workspace(B, V, w, src.shape[0], src.device)
+        imgs, argmax = ops.render_depth(src, s_row0, s_len, tgt, t_row0, t_len, max_s_len, max_t_len, rot, w, rho, ws)
+        ctx.save_for_backward(src, s_row0, s_len, rot, argmax, ws)
+        ctx.geo = (B, V, int(max_s_len), int(w), float(rho))
+        return imgs.view(B * V, 2, w, w)
+
+    @staticmethod
+    def backward(ctx, dimgs):
+        src, s_row0, s_len, rot, argmax, ws = ctx.saved_tensors
+        B, V, max_s_len, w, rho = ctx.geo
+        dsrc = ops.render_depth_bwd(dimgs.to(torch.float32).contiguous().view(B, V, 2, w, w), argmax, src, s_row0, s_len, max_s_len, rot,
+                                    w, rho, ws)
+        return (dsrc,) + (None,) * 10
+
+
+def render_packed_train(src: torch.Tensor, s_row0, s_len, tgt: torch.Tensor, t_row0, t_len, max_s_len: int, max_t_len: int,
+                        eulers: Sequence, w: int = 64, rho: float = 24.0, rot: torch.Tensor = None) -> torch.Tensor:
+    """render_packed with a grad_fn into the packed source rows `src` (a packed prediction): imgs [B*V, 2, w, w], the batch a
+    discriminator takes, pair-major.  The target is data.  rot: the [V,3,3] view matrices already on the device
+    (RegistrationRender.view_matrices), instead of building and uploading them from `eulers`."""
+    if not src.is_cuda or not tgt.is_cuda:
+        raise _lib.ScreamHipError("render_packed_train needs tensors on the MI355X (got %s, %s); there is no CPU path"
+                                  % (src.device, tgt.device))
+    if rot is None:
+        rot = torch.stack([rotation_matrix(e) for e in eulers]).to(src.device)
+    return _RenderPackedFn.apply(src, s_row0, s_len, tgt, t_row0, t_len, int(max_s_len), int(max_t_len), rot, int(w), float(rho))

@@ -1,14 +1,15 @@
 """Drop-in for the reference's ``train_kitti.py``: the same names (update_lr, evaluate, train), path and hyper-parameters, over
 the loops of scream_amd/fit.py -- batches prepared on the GPU, the HIP forward / backward, FusedAdam under a GradScaler.
 
-    python train_kitti.py [--batch 1] [--synthetic N] [--train-backend f32|split] [--epochs 120]
+    python train_kitti.py [--batch 1] [--synthetic N] [--train-backend f32|split] [--gan] [--epochs 120]
 
 With the reference's on-disk splits present (``KITTI_train/`` and ``KITTI_val/``: src%d.npy, tgt%d.npy, T%d.npy, raw metric
 clouds) it trains on them; ``--synthetic N`` trains on N seeded synthetic pairs and validates on N / 4 others.  Nothing runs at
 import.  The reference keeps the checkpoint with the best registration recall (train_kitti.py:223-229, open3d ICP inside the
 loop); here, as in the other two drivers, it is the one with the best validation loss, and evaluate() returns that loss: pose
-metrics with the GPU ICP are evaluate_kitti.py's.  use_GAN stays False: the reference's use_GAN=True loop does not run as written
-(DESIGN.md section 7).
+metrics with the GPU ICP are evaluate_kitti.py's.  ``--gan`` turns on use_GAN: the adversarial loss of
+scream_amd/gan.py (a 2-channel HIP discriminator, FusedAdam at lr_d with betas (0.5, 0.999)) through fit(gan=...); the
+discriminator is saved to discriminator_save_path whenever the generator is.
 """
 import argparse
 import os
@@ -18,12 +19,14 @@ from torch.utils import data
 
 from scream_amd import FusedAdam
 from scream_amd.data import RawPairFiles, SyntheticRawPairs
-from scream_amd.fit import fit, pair_preparer, val_loss
+from scream_amd.fit import fit, gan_training, pair_preparer, pair_real_rows, val_loss
 
 use_GAN = False
 generator_save_path = "params/kitti-generator.pth"
+discriminator_save_path = "params/discriminator.pth"
 
 lr_g = 0.00032
+lr_d = 0.0001
 min_learning_rate = 0.00001
 learning_rate_decay_gamma = 0.5
 lr_update_epoch = 10
@@ -57,7 +60,12 @@ def evaluate(net, val_loader, prepare_val):
     return val_loss(net, val_loader, prepare_val)[0]
 
 
-def train(synthetic=0, batch=1, train_backend=None, layers=(6, 6), n_epochs=None, save_path=None, device=None, log=print, scaler=None):
+def _gan(device):
+    """What use_GAN adds: this driver's lr_d, ground-truth rows and discriminator_save_path."""
+    return gan_training(device, pair_real_rows, lr_d=lr_d, save_path=discriminator_save_path)
+
+
+def train(synthetic=0, batch=1, train_backend=None, layers=(6, 6), n_epochs=None, save_path=None, device=None, log=print, scaler=None, gan=None):
     """train_kitti.py:138-233.  Returns fit()'s history."""
     from models.pointnet import PointTransformer
     device = torch.device(device if device is not None else "cuda:0")
@@ -74,7 +82,8 @@ def train(synthetic=0, batch=1, train_backend=None, layers=(6, 6), n_epochs=None
     train_loader, val_loader = _loaders(synthetic, batch)
     return fit(net, optimizer_G, train_loader, val_loader, pair_preparer("kitti", True, device), pair_preparer("kitti", False, device),
                epochs if n_epochs is None else n_epochs, save_path or generator_save_path, scaler=scaler, gamma=learning_rate_decay_gamma,
-               every=lr_update_epoch, floor=min_learning_rate, log=log)
+               every=lr_update_epoch, floor=min_learning_rate, log=log,
+               gan=_gan(device) if (use_GAN if gan is None else gan) else None)
 
 
 def main(argv=None):
@@ -83,7 +92,10 @@ def main(argv=None):
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--train-backend", choices=("f32", "split"), default=None)
     ap.add_argument("--epochs", type=int, default=epochs)
+    ap.add_argument("--gan", action="store_true", help="train with the adversarial loss (use_GAN)")
     a = ap.parse_args(argv)
+    global use_GAN
+    use_GAN = use_GAN or a.gan
     train(a.synthetic, a.batch, a.train_backend, n_epochs=a.epochs)
 
 
