@@ -470,6 +470,33 @@ int64_t scream_wgrad_split_workspace_bytes(int64_t rows, int32_t N, int32_t K);
 int scream_gemm_wgrad_split_f32(const float* dY, int64_t ldy, const float* X, int64_t ldx, int64_t rows, int32_t N,
                                 int32_t K, float* dW, int32_t accumulate, float* colsum, int32_t split, void* workspace,
                                 int64_t workspace_bytes, void* stream);
+/* ---- train_backend "bf16": ONE bf16 product per training GEMM, fp32 accumulation (csrc/gemm_bf16.hip).
+ * The arithmetic of all three entry points: sum_k bf16(a_k) * bf16(b_k).  Both operands are fp32 in memory and are rounded to
+ * bf16 by round-to-nearest-even on their way into the kernel (v_cvt_pk_bf16_f32, in registers); the products of two bf16
+ * values are exact; the sum is accumulated in fp32 on v_mfma_f32_32x32x16_bf16 and stored as fp32.  bf16, not fp16: it keeps
+ * fp32's exponent range, so no operand carries an exponent that would have to follow the weights after every optimizer step,
+ * gradients of any magnitude pass (a GradScaler's 2^16 included), and a power of two on one operand comes out of the result
+ * bit for bit as long as nothing leaves fp32's normal range.  No float atomics, every output element is one fixed-order sum:
+ * two identical calls are bitwise identical.  Nothing is packed or transposed beforehand: W is torch's [N,K] fp32 matrix.
+ *
+ * Forward: C[M,N] = epilogue(A[M,K] . W[N,K]^T).  M % 128 == 0, N % 256 == 0, K % 64 == 0 (SCREAM_EUNSUPPORTED otherwise);
+ * lda >= K, ldc >= N, both multiples of 4, pointers 16-byte aligned (SCREAM_EINVAL otherwise).  epilogue: SCREAM_EPI_NONE,
+ * SCREAM_EPI_ELU1 (n_act % 256 == 0), SCREAM_EPI_RELU or SCREAM_EPI_BIAS_RELU (bias [N]), applied in fp32 to the fp32 sum;
+ * SCREAM_EPI_RES_LN is SCREAM_EUNSUPPORTED. */
+int scream_gemm_bf16_f32(const float* A, int64_t lda, const float* W, float* C, int64_t ldc, int64_t M, int32_t N, int32_t K,
+                         int32_t epilogue, int32_t n_act, const float* bias, void* stream);
+/* Data gradient: dX[M,K] = dY[M,N] . W[N,K], summed over all of N in one launch (W is transposed inside the kernel, on its way
+ * into LDS).  M % 128 == 0, K % 256 == 0, N % 64 == 0; ldy >= N, ldx >= K, multiples of 4.  Zero rows of dY (padded rows) give
+ * zero rows of dX. */
+int scream_gemm_dgrad_bf16_f32(const float* dY, int64_t ldy, const float* W, float* dX, int64_t ldx, int64_t M, int32_t N,
+                               int32_t K, void* stream);
+/* Weight gradient: the contract of scream_gemm_wgrad_f32 (rows >= 0, N % 128 == 0, K % 128 == 0, accumulate, colsum, ldy, ldx,
+ * fixed-order row-slice partials in the workspace and the index-order reduce launch) in the arithmetic above.  colsum is an fp32
+ * sum of the UNROUNDED dY.  workspace: scream_wgrad_bf16_workspace_bytes(rows, N, K) bytes, 16-byte aligned. */
+int64_t scream_wgrad_bf16_workspace_bytes(int64_t rows, int32_t N, int32_t K);
+int scream_gemm_wgrad_bf16_f32(const float* dY, int64_t ldy, const float* X, int64_t ldx, int64_t rows, int32_t N, int32_t K,
+                               float* dW, int32_t accumulate, float* colsum, void* workspace, int64_t workspace_bytes,
+                               void* stream);
 /* y = LayerNorm(a + b) * gamma + beta over rows of 256 (b may be NULL), with the per-row mean and rstd = 1/sqrt(var + 1e-5). */
 int scream_ln_fwd(const float* a, const float* b, const float* gamma, const float* beta, float* y, float* mean,
                   float* rstd, int64_t rows, void* stream);

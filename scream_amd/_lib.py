@@ -104,6 +104,10 @@ SIGNATURES = {
     "scream_gemm_wgrad_f32": (C.c_int, [V, I64, V, I64, I64, I32, I32, V, I32, V, V, I64, V]),
     "scream_wgrad_split_workspace_bytes": (C.c_int64, [I64, I32, I32]),
     "scream_gemm_wgrad_split_f32": (C.c_int, [V, I64, V, I64, I64, I32, I32, V, I32, V, I32, V, I64, V]),
+    "scream_gemm_bf16_f32": (C.c_int, [V, I64, V, V, I64, I64, I32, I32, I32, I32, V, V]),
+    "scream_gemm_dgrad_bf16_f32": (C.c_int, [V, I64, V, V, I64, I64, I32, I32, V]),
+    "scream_wgrad_bf16_workspace_bytes": (C.c_int64, [I64, I32, I32]),
+    "scream_gemm_wgrad_bf16_f32": (C.c_int, [V, I64, V, I64, I64, I32, I32, V, I32, V, V, I64, V]),
     "scream_ln_fwd": (C.c_int, [V, V, V, V, V, V, V, I64, V]),
     "scream_ln_bwd_workspace_bytes": (C.c_int64, [I64]),
     "scream_ln_bwd": (C.c_int, [V, V, V, V, V, V, V, V, V, V, I32, I64, V, I64, V]),

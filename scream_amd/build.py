@@ -17,6 +17,8 @@ ARCH = "gfx950"
 SOURCES = {
     "gemm_f32.hip": [],
     "gemm_split.hip": [],
+    # train_backend "bf16": one bf16 product per GEMM (forward, data gradient, weight gradient)
+    "gemm_bf16.hip": [],
     # the MFMA results of this kernel are consumed by vector instructions (every chunk's epilogue rides under the next chunk's
     # matrix instructions) while its row operand planes fill the whole AGPR file: accumulators in VGPRs, no moves between the files
     "proj_ring.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
@@ -49,7 +51,9 @@ ASM_LOADS = ("gemm_split.hip", "tail_split.hip", "proj_ring.hip")  # verified af
 NO_SCRATCH = {"proj_ring.hip": ("proj_ring_kernel",), "tail_split.hip": ("tail_kernelINS_7SplitH2", "tail_kernelINS_7SplitH1")}
 # kernels outside ASM_LOADS that must not touch scratch either: the raw-scan ICP search keeps its eight stepped binary searches
 # and its best candidate in registers (a spill would sit inside the dependent-load chain that bounds it)
-NO_SCRATCH_PLAIN = {"icp_raw.hip": ("raw_search_kernel", "raw_nn_kernel")}
+NO_SCRATCH_PLAIN = {"icp_raw.hip": ("raw_search_kernel", "raw_nn_kernel"),
+                    # the bf16 training GEMMs hold a 32 x 256 accumulator tile and both operands' next k-tile in registers
+                    "gemm_bf16.hip": ("gemm_bf16_kernel", "wgrad_split_partial_kernel")}
 
 
 def _hipcc() -> str:

@@ -114,9 +114,11 @@ class PointTransformer(nn.Module):
 
     # Arithmetic of the TRAINING matrix products (scream_amd/train.py); inference never looks at it.  "f32" (default): the
     # fp32-input MFMA everywhere.  "split": fp32-accurate products on the bf16 matrix cores (three planes, six products, scale
-    # free -- safe under a GradScaler) for the forward GEMMs, the data gradients and the weight gradients.  SCREAM_TRAIN_GEMM
+    # free -- safe under a GradScaler) for the forward GEMMs, the data gradients and the weight gradients.  "bf16": mixed
+    # precision, ONE bf16 product per GEMM with fp32 accumulation (operands rounded to nearest even on the way in; the mirror
+    # of the reference's autocast training, in bf16 rather than fp16) -- NOT fp32-accurate, opt-in only.  SCREAM_TRAIN_GEMM
     # sets the class default; an assignment validates at once, a bad environment value raises at the first train().
-    TRAIN_BACKENDS = ("f32", "split")
+    TRAIN_BACKENDS = ("f32", "split", "bf16")
     _train_backend_default = os.environ.get("SCREAM_TRAIN_GEMM", "f32")
 
     @classmethod

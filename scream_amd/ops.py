@@ -64,6 +64,39 @@ def gemm_f32(A: torch.Tensor, W: torch.Tensor, epilogue: int = EPI_NONE, n_act: 
     return out
 
 
+def _rows(t: torch.Tensor) -> int:
+    """Address of a 2-D fp32 device matrix whose rows may be column slices of a wider one (unit column stride; the row
+    stride goes to the library as ld*)."""
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError("matrix rows must be contiguous")
+    return _p(t) if t.is_contiguous() else _p(t[:1]) if t.shape[0] else t.data_ptr()
+
+
+def gemm_bf16(A: torch.Tensor, W: torch.Tensor, epilogue: int = EPI_NONE, n_act: int = 0,
+              bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """C = epilogue(bf16(A) @ bf16(W).T), fp32 accumulation (train_backend "bf16"); shapes as gemm_f32, W torch's [N,K] fp32."""
+    M, K = A.shape
+    N = W.shape[0]
+    assert W.shape[1] == K and W.is_contiguous()
+    if out is None:
+        out = torch.empty(M, N, device=A.device, dtype=torch.float32)
+    check(_lib.load().scream_gemm_bf16_f32(_rows(A), A.stride(0), _p(W), _rows(out), out.stride(0), M, N, K, epilogue, n_act,
+                                           _p(bias), _stream()), "scream_gemm_bf16_f32")
+    return out
+
+
+def gemm_dgrad_bf16(dY: torch.Tensor, W: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dX = bf16(dY) @ bf16(W) for W [N,K] (torch's layout, read as it is), summed over N in one launch."""
+    M, N = dY.shape
+    K = W.shape[1]
+    assert W.shape[0] == N and W.is_contiguous()
+    if out is None:
+        out = torch.empty(M, K, device=dY.device, dtype=torch.float32)
+    check(_lib.load().scream_gemm_dgrad_bf16_f32(_rows(dY), dY.stride(0), _p(W), _rows(out), out.stride(0), M, N, K, _stream()),
+          "scream_gemm_dgrad_bf16_f32")
+    return out
+
+
 @dataclass
 class PackedW:
     """A weight matrix [N,K] in the split GEMM's operand image (scream_pack_w_split): `split` planes of 16-bit values,

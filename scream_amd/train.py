@@ -1,7 +1,7 @@
 """Training of PointTransformer and DEMTransformer: a forward that keeps its activations, and the backward pass on the
 HIP kernels of csrc/backward.hip, wired into torch.autograd.
 
-Two arithmetics for the matrix products, chosen per model by net.train_backend (every other kernel is the same fp32 code):
+Three arithmetics for the matrix products, chosen per model by net.train_backend (every other kernel is the same fp32 code):
   "f32"    (default) every product on the fp32-input MFMA: scream_gemm_f32 forward and data gradients, scream_gemm_wgrad_f32.
   "split"  fp32-accurate products on the 16-bit matrix cores with fp32 accumulation (csrc/split.h, SplitBf3: three bf16 planes,
            six products, scale free -- gradients of any magnitude, a GradScaler's 2^16 included, need no exponent): forward and
@@ -10,6 +10,11 @@ Two arithmetics for the matrix products, chosen per model by net.train_backend (
            gradients read) are made per step, each once (_Gemms).  A data gradient
            whose summed dimension the split GEMM does not take (K = 768 of the self layers' q|k|v, K = 512 of the cross
            layers' k|v) runs as K = 256 products added in column order.
+  "bf16"   mixed precision: ONE bf16 product per GEMM with fp32 accumulation (csrc/gemm_bf16.hip; include/scream_hip.h states
+           the arithmetic), the mirror of the reference's autocast training in bf16 instead of fp16.  NOT fp32-accurate.  The
+           operands stay fp32 in memory (saved activations included) and are rounded in registers; the weights are read in
+           torch's [N,K] layout by all three products, so nothing is packed or transposed per step and every data gradient
+           is one launch: scream_gemm_bf16_f32, scream_gemm_dgrad_bf16_f32, scream_gemm_wgrad_bf16_f32.
 
 The forward is the unfused fp32 chain of the existing kernels (scream_pe_embed + scream_ln_fwd, scream_gemm_f32 with the
 elu + 1 / relu / bias + relu epilogues, scream_kv_reduce, scream_attn_apply, scream_ln_fwd, scream_coor_head).  The layers
@@ -56,10 +61,14 @@ def transpose(W: torch.Tensor) -> torch.Tensor:
 def wgrad(dY: torch.Tensor, X: torch.Tensor, dW: torch.Tensor, colsum: torch.Tensor = None, accumulate: bool = False,
           ldy: int = None, ldx: int = None, rows: int = None, split: int = None) -> torch.Tensor:
     """dW[N,K] (+)= dY^T X over rows; dW any contiguous tensor of N * K floats.  split None: the fp32-input MFMA
-    (scream_gemm_wgrad_f32); SPLIT_BF3: the 16-bit matrix cores, fp32-accurate by operand splitting (scream_gemm_wgrad_split_f32)."""
+    (scream_gemm_wgrad_f32); SPLIT_BF3: the 16-bit matrix cores, fp32-accurate by operand splitting (scream_gemm_wgrad_split_f32);
+    "bf16": one bf16 product, fp32 accumulation (scream_gemm_wgrad_bf16_f32)."""
     lib = _lib.load()
-    name = "scream_gemm_wgrad_f32" if split is None else "scream_gemm_wgrad_split_f32"
-    sizer = "scream_wgrad_workspace_bytes" if split is None else "scream_wgrad_split_workspace_bytes"
+    if split == "bf16":  # one bf16 product (scream_gemm_wgrad_bf16_f32): the fp32 entry point's arguments
+        name, sizer, split = "scream_gemm_wgrad_bf16_f32", "scream_wgrad_bf16_workspace_bytes", None
+    else:
+        name = "scream_gemm_wgrad_f32" if split is None else "scream_gemm_wgrad_split_f32"
+        sizer = "scream_wgrad_workspace_bytes" if split is None else "scream_wgrad_split_workspace_bytes"
     rows = dY.shape[0] if rows is None else rows
     N, K = dY.shape[1], X.shape[1]
     ws = _workspace(getattr(lib, sizer), sizer, rows, N, K, device=dY.device)
@@ -67,6 +76,10 @@ def wgrad(dY: torch.Tensor, X: torch.Tensor, dW: torch.Tensor, colsum: torch.Ten
                              rows, N, K, _p(dW), int(accumulate), _p(colsum), *(() if split is None else (split,)),
                              ws.data_ptr(), ws.numel(), _stream()), name)
     return dW
+
+
+def wgrad_bf16(dY, X, dW, colsum=None, accumulate=False, ldy=None, ldx=None, rows=None) -> torch.Tensor:
+    return wgrad(dY, X, dW, colsum, accumulate, ldy, ldx, rows, "bf16")
 
 
 def wgrad_split(dY, X, dW, colsum=None, accumulate=False, ldy=None, ldx=None, rows=None, split: int = SPLIT_BF3) -> torch.Tensor:
@@ -81,17 +94,24 @@ class _Gemms:
     forward GEMMs, the data gradients and the weight gradients.  Every weight matrix enters one forward product and one
     data-gradient product per step, so "split" packs each (and each transpose) exactly once per step, where it is used."""
 
+    split = bf16 = False  # the "f32" arm
+
     def __init__(self, net):
-        self.split = net._check_train_backend(net.train_backend) == "split"
+        backend = net._check_train_backend(net.train_backend)
+        self.split, self.bf16 = backend == "split", backend == "bf16"
 
     def fwd(self, A, W, epilogue: int = EPI_NONE, n_act: int = 0, bias=None):
         """epilogue(A W^T) for W [N,K]."""
+        if self.bf16:
+            return ops.gemm_bf16(A, W, epilogue, n_act=n_act, bias=bias)
         if not self.split:
             return gemm_f32(A, W, epilogue, n_act=n_act, bias=bias)
         return ops.gemm_split(A, ops.pack_w(W, SPLIT_BF3), epilogue, n_act=n_act, bias=bias)
 
     def dgrad(self, dY, W, out=None):
-        """dX = dY W for W [N,K]: a GEMM against the transposed weight [K,N], which sums over N."""
+        """dX = dY W for W [N,K]: a GEMM against the transposed weight [K,N], which sums over N ("bf16": W as it is)."""
+        if self.bf16:
+            return ops.gemm_dgrad_bf16(dY, W, out=out)
         Wt = transpose(W)
         if not self.split:
             return gemm_f32(dY, Wt, out=out)
@@ -114,7 +134,7 @@ class _Gemms:
         return out
 
     def wgrad(self, dY, X, dW, colsum=None):
-        return wgrad(dY, X, dW, colsum, split=SPLIT_BF3 if self.split else None)
+        return wgrad(dY, X, dW, colsum, split="bf16" if self.bf16 else SPLIT_BF3 if self.split else None)
 
 
 def ln_fwd(a: torch.Tensor, b, gamma, beta, out: torch.Tensor = None):

@@ -2,8 +2,8 @@
 """Training throughput of PointTransformer (6 + 6 layers) on 3DMatch-like pairs, and the weight-gradient GEMM's rate; or, with
 --model dem, of DEMTransformer (6 + 6 layers) on OpenGF-like terrain.
 
-    python tools/train_bench.py [--batches 4,32] [--steps 3] [--warmup 1] [--train-backend f32|split] [--wgrad-only] [--json OUT]
-    python tools/train_bench.py --model dem [--batches 1,8] [--points 4000,16000] [--train-backend f32|split] [--json OUT]
+    python tools/train_bench.py [--batches 4,32] [--steps 3] [--warmup 1] [--train-backend f32|split|bf16] [--wgrad-only | --no-wgrad] [--json OUT]
+    python tools/train_bench.py --model dem [--batches 1,8] [--points 4000,16000] [--train-backend f32|split|bf16] [--json OUT]
 
 One step = training forward + loss + backward + Adam (lr 2e-4) over a packed batch of B pairs; pairs/s = B / step time
 (wall clock around torch.cuda.synchronize) in the arithmetic of --train-backend (net.train_backend).  The wgrad part times
@@ -66,13 +66,16 @@ def bench_training(B, steps, warmup, backend):
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
+    times = []  # per step, each ended by a synchronise: the median is what two legs of a comparison are compared by
     t0 = time.perf_counter()
     for _ in range(steps):
+        t1 = time.perf_counter()
         loss = step()
-    torch.cuda.synchronize()
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t1)
     dt = (time.perf_counter() - t0) / steps
     pts = sum(p[0].shape[0] + p[1].shape[0] for p in pairs) / B
-    return dict(B=B, train_backend=backend, step_s=dt, pairs_per_s=B / dt, mean_points_per_pair=pts, rows_total=batch.rows_total,
+    return dict(B=B, train_backend=backend, step_s=dt, step_median_s=float(np.median(times)), pairs_per_s=B / dt, mean_points_per_pair=pts, rows_total=batch.rows_total,
                 loss=float(loss.detach()), peak_mem_gb=torch.cuda.max_memory_allocated() / 2 ** 30)
 
 
@@ -100,12 +103,15 @@ def bench_dem_training(B, points, steps, warmup, backend):
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
+    times = []  # per step, each ended by a synchronise: the median is what two legs of a comparison are compared by
     t0 = time.perf_counter()
     for _ in range(steps):
+        t1 = time.perf_counter()
         loss = step()
-    torch.cuda.synchronize()
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t1)
     dt = (time.perf_counter() - t0) / steps
-    return dict(B=B, points=points, train_backend=backend, step_s=dt, samples_per_s=B / dt, mean_coarse_points=sum(s[1].shape[0] for s in samples) / B,
+    return dict(B=B, points=points, train_backend=backend, step_s=dt, step_median_s=float(np.median(times)), samples_per_s=B / dt, mean_coarse_points=sum(s[1].shape[0] for s in samples) / B,
                 rows_src=batch.rows_src, rows_total=batch.rows_total, loss=float(loss.detach()),
                 peak_mem_gb=torch.cuda.max_memory_allocated() / 2 ** 30)
 
@@ -138,8 +144,9 @@ def main():
     ap.add_argument("--points", default="4000,16000", help="DSM points per sample (dem)")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--train-backend", choices=("f32", "split"), default="f32", help="net.train_backend of the training legs")
+    ap.add_argument("--train-backend", choices=("f32", "split", "bf16"), default="f32", help="net.train_backend of the training legs")
     ap.add_argument("--wgrad-only", action="store_true")
+    ap.add_argument("--no-wgrad", action="store_true", help="training legs only (the legs of a backend comparison)")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     if a.model == "dem":
@@ -148,13 +155,13 @@ def main():
             for B in (int(b) for b in (a.batches or "1,8").split(",")):
                 r = bench_dem_training(B, pts, a.steps, a.warmup, a.train_backend)
                 res["train"].append(r)
-                print("dem train %s points %5d B %2d: %.3f s/step  %.1f samples/s  (%.0f coarse points, %d rows, peak %.1f GB)"
-                      % (a.train_backend, pts, B, r["step_s"], r["samples_per_s"], r["mean_coarse_points"], r["rows_total"], r["peak_mem_gb"]))
+                print("dem train %s points %5d B %2d: %.3f s/step (median %.3f)  %.1f samples/s  (%.0f coarse points, %d rows, peak %.1f GB)"
+                      % (a.train_backend, pts, B, r["step_s"], r["step_median_s"], r["samples_per_s"], r["mean_coarse_points"], r["rows_total"], r["peak_mem_gb"]))
         if a.json:
             os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
             json.dump(res, open(a.json, "w"), indent=1)
         return
-    res = dict(wgrad=bench_wgrad())
+    res = dict(wgrad=[] if a.no_wgrad else bench_wgrad())
     for r in res["wgrad"]:
         print("wgrad %-5s rows %7d N %4d K %4d: %8.1f us  %6.1f TFLOP/s  %.2f of its roof" % (r["kernel"], r["rows"], r["N"], r["K"], r["us"], r["tflops"], r["frac_of_peak"]))
     if not a.wgrad_only:
@@ -162,7 +169,7 @@ def main():
         for B in (int(b) for b in (a.batches or "4,32").split(",")):
             r = bench_training(B, a.steps, a.warmup, a.train_backend)
             res["train"].append(r)
-            print("train %s B %2d: %.3f s/step  %.1f pairs/s  (%.0f points/pair, peak %.1f GB)" % (a.train_backend, B, r["step_s"], r["pairs_per_s"],
+            print("train %s B %2d: %.3f s/step (median %.3f)  %.1f pairs/s  (%.0f points/pair, peak %.1f GB)" % (a.train_backend, B, r["step_s"], r["step_median_s"], r["pairs_per_s"],
                                                                                                    r["mean_points_per_pair"], r["peak_mem_gb"]))
     if a.json:
         os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)

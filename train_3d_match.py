@@ -1,7 +1,7 @@
 """Drop-in for the reference's ``train_3d_match.py``: the same names (update_lr, evaluate, train), paths and hyper-parameters,
 over the loops of scream_amd/fit.py -- batches prepared on the GPU, the HIP forward / backward, FusedAdam.
 
-    python train_3d_match.py [--batch 1] [--synthetic N] [--train-backend f32|split] [--gan] [--epochs 45]
+    python train_3d_match.py [--batch 1] [--synthetic N] [--train-backend f32|split|bf16] [--gan] [--epochs 45]
 
 With the reference's on-disk splits present (``3DMatch_train/`` and ``3DMatch_val/``: src%d.npy, tgt%d.npy, T%d.npy, raw metric
 clouds) it trains on them; ``--synthetic N`` trains on N seeded synthetic pairs and validates on N / 4 others (no dataset ships
@@ -90,7 +90,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1, help="pairs per step (the reference trains at 1)")
     ap.add_argument("--synthetic", type=int, default=0)
-    ap.add_argument("--train-backend", choices=("f32", "split"), default=None)
+    ap.add_argument("--train-backend", choices=("f32", "split", "bf16"), default=None)
     ap.add_argument("--epochs", type=int, default=epochs)
     ap.add_argument("--gan", action="store_true", help="train with the adversarial loss (use_GAN)")
     a = ap.parse_args(argv)

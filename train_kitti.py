@@ -1,7 +1,7 @@
 """Drop-in for the reference's ``train_kitti.py``: the same names (update_lr, evaluate, train), path and hyper-parameters, over
 the loops of scream_amd/fit.py -- batches prepared on the GPU, the HIP forward / backward, FusedAdam under a GradScaler.
 
-    python train_kitti.py [--batch 1] [--synthetic N] [--train-backend f32|split] [--gan] [--epochs 120]
+    python train_kitti.py [--batch 1] [--synthetic N] [--train-backend f32|split|bf16] [--gan] [--epochs 120]
 
 With the reference's on-disk splits present (``KITTI_train/`` and ``KITTI_val/``: src%d.npy, tgt%d.npy, T%d.npy, raw metric
 clouds) it trains on them; ``--synthetic N`` trains on N seeded synthetic pairs and validates on N / 4 others.  Nothing runs at
@@ -75,9 +75,11 @@ def train(synthetic=0, batch=1, train_backend=None, layers=(6, 6), n_epochs=None
     net.to(device)
     optimizer_G = FusedAdam(params=net.parameters(), lr=lr_g)
     # train_kitti.py:52,186-188: scaler.scale(loss).backward(); scaler.step(optimizer_G); scaler.update().  The reference needs
-    # the scaler because its forward runs under autocast; here no autocast is needed: both training arithmetics are fp32-accurate
-    # and the split backend is scale free, so the scaled gradients are the gradients times the scale.  FusedAdam takes the scale
-    # and the scaler's found_inf on the device, so the step reads nothing back.
+    # the scaler because its forward runs under autocast.  Here the arithmetic of the matrix products is net.train_backend, not
+    # a context manager: "f32" and "split" are fp32-accurate, and --train-backend bf16 is the mirror of the reference's autocast
+    # (one 16-bit product per GEMM, fp32 accumulation; bf16 where the reference has fp16).  The split and the bf16 backend are
+    # scale free, so the scaled gradients are the gradients times the scale.  FusedAdam takes the scale and the scaler's
+    # found_inf on the device, so the step reads nothing back.
     scaler = scaler if scaler is not None else torch.amp.GradScaler("cuda")
     train_loader, val_loader = _loaders(synthetic, batch)
     return fit(net, optimizer_G, train_loader, val_loader, pair_preparer("kitti", True, device), pair_preparer("kitti", False, device),
@@ -90,7 +92,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1, help="pairs per step (the reference trains at 1)")
     ap.add_argument("--synthetic", type=int, default=0)
-    ap.add_argument("--train-backend", choices=("f32", "split"), default=None)
+    ap.add_argument("--train-backend", choices=("f32", "split", "bf16"), default=None)
     ap.add_argument("--epochs", type=int, default=epochs)
     ap.add_argument("--gan", action="store_true", help="train with the adversarial loss (use_GAN)")
     a = ap.parse_args(argv)

@@ -1,7 +1,7 @@
 """Drop-in for the reference's ``train_open_gf.py``: the same names (update_lr, evaluate, train), path and hyper-parameters, over
 the loops of scream_amd/fit.py -- DEMTransformer on packed batches, the HIP forward / backward, FusedAdam.
 
-    python train_open_gf.py [--batch 1] [--synthetic N] [--train-backend f32|split] [--gan] [--epochs 45]
+    python train_open_gf.py [--batch 1] [--synthetic N] [--train-backend f32|split|bf16] [--gan] [--epochs 45]
 
 With the reference's on-disk splits present (``OpenGF_train/`` and ``OpenGF_val/``: 1.npy, 2.npy, ... [N,6] DSM | DEM) it trains
 on them; ``--synthetic N`` trains on N seeded synthetic terrain patches and validates on N / 4 others.  Nothing runs at import.
@@ -91,7 +91,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1, help="samples per step (the reference trains at 1)")
     ap.add_argument("--synthetic", type=int, default=0)
-    ap.add_argument("--train-backend", choices=("f32", "split"), default=None)
+    ap.add_argument("--train-backend", choices=("f32", "split", "bf16"), default=None)
     ap.add_argument("--epochs", type=int, default=epochs)
     ap.add_argument("--gan", action="store_true", help="train with the adversarial loss (use_GAN)")
     a = ap.parse_args(argv)
