@@ -38,6 +38,14 @@ def _p(t: Optional[torch.Tensor], dtype=torch.float32) -> Optional[int]:
     return t.data_ptr()
 
 
+def _rows(t: torch.Tensor) -> int:
+    """Address of a 2-D fp32 device matrix whose rows may be column slices of a wider one (unit column stride; the row
+    stride goes to the library as ld*)."""
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError("matrix rows must be contiguous")
+    return _p(t) if t.is_contiguous() else _p(t[:1]) if t.shape[0] else t.data_ptr()
+
+
 def _workspace(lib_fn, name: str, *args, device, floor: int = 16) -> torch.Tensor:
     """Scratch for one call: the uint8 tensor of the size that the library's own `*_workspace_bytes(*args)` asks for (at least
     `floor` bytes, so that it always has an address); a negative size is the library refusing the arguments."""
@@ -47,29 +55,19 @@ def _workspace(lib_fn, name: str, *args, device, floor: int = 16) -> torch.Tenso
     return torch.empty(max(need, floor), device=device, dtype=torch.uint8)
 
 
-def gemm_f32(A: torch.Tensor, W: torch.Tensor, epilogue: int = EPI_NONE, n_act: int = 0,
-             bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
-             gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
+def gemm_f32(A: torch.Tensor, W: torch.Tensor, epilogue: int = EPI_NONE, n_act: int = 0, bias: Optional[torch.Tensor] = None,
+             residual: Optional[torch.Tensor] = None, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
              out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """C = epilogue(A @ W.T); A [M,K] (M % 128 == 0), W [N,K] (N % 256 == 0, K % 32 == 0)."""
+    """C = epilogue(A @ W.T); A [M,K] (M % 128 == 0), W [N,K] (N % 256 == 0, K % 32 == 0); A and out may be column slices (_rows)."""
     M, K = A.shape
     N = W.shape[0]
     assert W.shape[1] == K
     if out is None:
         out = torch.empty(M, N, device=A.device, dtype=torch.float32)
-    lib = _lib.load()
-    check(lib.scream_gemm_f32(_p(A), A.stride(0), _p(W), _p(out), out.stride(0), M, N, K, epilogue, n_act,
-                              _p(bias), _p(residual), residual.stride(0) if residual is not None else 0,
-                              _p(gamma), _p(beta), _stream()), "scream_gemm_f32")
+    check(_lib.load().scream_gemm_f32(_rows(A), A.stride(0), _p(W), _rows(out), out.stride(0), M, N, K, epilogue, n_act, _p(bias),
+                                      _p(residual), residual.stride(0) if residual is not None else 0, _p(gamma), _p(beta), _stream()),
+          "scream_gemm_f32")
     return out
-
-
-def _rows(t: torch.Tensor) -> int:
-    """Address of a 2-D fp32 device matrix whose rows may be column slices of a wider one (unit column stride; the row
-    stride goes to the library as ld*)."""
-    if t.dim() != 2 or t.stride(1) != 1:
-        raise ValueError("matrix rows must be contiguous")
-    return _p(t) if t.is_contiguous() else _p(t[:1]) if t.shape[0] else t.data_ptr()
 
 
 def gemm_bf16(A: torch.Tensor, W: torch.Tensor, epilogue: int = EPI_NONE, n_act: int = 0,
@@ -164,9 +162,8 @@ def _a_exp(A: torch.Tensor, Wp, a_exp: Optional[int]) -> int:
     return scales.exp_for(A.abs().max().item()) if a_exp is None else int(a_exp)
 
 
-def gemm_split(A: torch.Tensor, Wp: PackedW, epilogue: int = EPI_NONE, n_act: int = 0,
-               bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
-               gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
+def gemm_split(A: torch.Tensor, Wp: PackedW, epilogue: int = EPI_NONE, n_act: int = 0, bias: Optional[torch.Tensor] = None,
+               residual: Optional[torch.Tensor] = None, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
                out: Optional[torch.Tensor] = None, layout: int = 0, a_exp: Optional[int] = None) -> torch.Tensor:
     """gemm_f32's contract on the 16-bit matrix cores by operand splitting (fp32-level accuracy); Wp = pack_w(W).
     layout: LAYOUT_A_FRAG (A is fragment-major) | LAYOUT_C_FRAG (the activated query tile is written fragment-major)."""
@@ -174,10 +171,9 @@ def gemm_split(A: torch.Tensor, Wp: PackedW, epilogue: int = EPI_NONE, n_act: in
     assert K == Wp.K
     if out is None:
         out = torch.empty(M, Wp.N, device=A.device, dtype=torch.float32)
-    check(_lib.load().scream_gemm_split_f32(_p(A), A.stride(0), Wp.data_ptr(), _p(out), out.stride(0), M, Wp.N, K,
-                                            epilogue, n_act, _p(bias), _p(residual),
-                                            residual.stride(0) if residual is not None else 0, _p(gamma), _p(beta), layout,
-                                            Wp.split, _a_exp(A, Wp, a_exp), Wp.w_exp, _stream()),
+    check(_lib.load().scream_gemm_split_f32(_rows(A), A.stride(0), Wp.data_ptr(), _rows(out), out.stride(0), M, Wp.N, K, epilogue, n_act,
+                                            _p(bias), _p(residual), residual.stride(0) if residual is not None else 0, _p(gamma),
+                                            _p(beta), layout, Wp.split, _a_exp(A, Wp, a_exp), Wp.w_exp, _stream()),
           "scream_gemm_split_f32")
     return out
 

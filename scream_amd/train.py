@@ -1,20 +1,20 @@
 """Training of PointTransformer and DEMTransformer: a forward that keeps its activations, and the backward pass on the
 HIP kernels of csrc/backward.hip, wired into torch.autograd.
 
-Three arithmetics for the matrix products, chosen per model by net.train_backend (every other kernel is the same fp32 code):
-  "f32"    (default) every product on the fp32-input MFMA: scream_gemm_f32 forward and data gradients, scream_gemm_wgrad_f32.
-  "split"  fp32-accurate products on the 16-bit matrix cores with fp32 accumulation (csrc/split.h, SplitBf3: three bf16 planes,
-           six products, scale free -- gradients of any magnitude, a GradScaler's 2^16 included, need no exponent): forward and
-           data gradients on scream_gemm_split_f32 against weights packed by scream_pack_w_split, weight gradients on
-           scream_gemm_wgrad_split_f32.  Weights change every step, so their packed images (and the packed transposes the data
-           gradients read) are made per step, each once (_Gemms).  A data gradient
-           whose summed dimension the split GEMM does not take (K = 768 of the self layers' q|k|v, K = 512 of the cross
-           layers' k|v) runs as K = 256 products added in column order.
-  "bf16"   mixed precision: ONE bf16 product per GEMM with fp32 accumulation (csrc/gemm_bf16.hip; include/scream_hip.h states
-           the arithmetic), the mirror of the reference's autocast training in bf16 instead of fp16.  NOT fp32-accurate.  The
-           operands stay fp32 in memory (saved activations included) and are rounded in registers; the weights are read in
-           torch's [N,K] layout by all three products, so nothing is packed or transposed per step and every data gradient
-           is one launch: scream_gemm_bf16_f32, scream_gemm_dgrad_bf16_f32, scream_gemm_wgrad_bf16_f32.
+Three arithmetics for the matrix products, one class each (ARITHMETICS), chosen per model by net.train_backend through gemms();
+every other kernel is the same fp32 code:
+  "f32"    F32Gemms (default): every product on the fp32-input MFMA: scream_gemm_f32 forward and data gradients, scream_gemm_wgrad_f32.
+  "split"  SplitGemms: fp32-accurate products on the 16-bit matrix cores with fp32 accumulation (csrc/split.h, SplitBf3: three
+           bf16 planes, six products, scale free -- gradients of any magnitude, a GradScaler's 2^16 included, need no
+           exponent): forward and data gradients on scream_gemm_split_f32 against weights packed per step by
+           scream_pack_w_split, weight gradients on scream_gemm_wgrad_split_f32.  A data gradient whose summed dimension the
+           split GEMM does not take (split_gemm_takes_k: K = 768 of the self layers' q|k|v, K = 512 of the cross layers' k|v)
+           runs as K = 256 products added in column order.
+  "bf16"   Bf16Gemms: mixed precision, ONE bf16 product per GEMM with fp32 accumulation (csrc/gemm_bf16.hip;
+           include/scream_hip.h states the arithmetic), the mirror of the reference's autocast training in bf16 instead of
+           fp16.  NOT fp32-accurate.  The operands stay fp32 in memory (saved activations included) and are rounded in
+           registers; the weights are read in torch's [N,K] layout by all three products, so nothing is packed or transposed
+           per step and every data gradient is one launch: scream_gemm_bf16_f32, scream_gemm_dgrad_bf16_f32, scream_gemm_wgrad_bf16_f32.
 
 The forward is the unfused fp32 chain of the existing kernels (scream_pe_embed + scream_ln_fwd, scream_gemm_f32 with the
 elu + 1 / relu / bias + relu epilogues, scream_kv_reduce, scream_attn_apply, scream_ln_fwd, scream_coor_head).  The layers
@@ -41,14 +41,12 @@ import torch
 
 from . import _lib, ops
 from ._lib import SPLIT_BF3, check
-from .ops import EPI_BIAS_RELU, EPI_ELU1, EPI_NONE, EPI_RELU, D_MODEL, _p, _stream, _workspace, gemm_f32
+from .ops import EPI_BIAS_RELU, EPI_ELU1, EPI_NONE, EPI_RELU, D_MODEL, _p, _stream, _workspace
 from .packing import PackedBatch
-
-F4 = 4  # bytes per float
 
 
 def _ptr(t: torch.Tensor, col: int = 0) -> int:
-    return _p(t) + col * F4
+    return _p(t) + col * 4  # bytes per float
 
 
 def transpose(W: torch.Tensor) -> torch.Tensor:
@@ -58,83 +56,87 @@ def transpose(W: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def wgrad(dY: torch.Tensor, X: torch.Tensor, dW: torch.Tensor, colsum: torch.Tensor = None, accumulate: bool = False,
-          ldy: int = None, ldx: int = None, rows: int = None, split: int = None) -> torch.Tensor:
-    """dW[N,K] (+)= dY^T X over rows; dW any contiguous tensor of N * K floats.  split None: the fp32-input MFMA
-    (scream_gemm_wgrad_f32); SPLIT_BF3: the 16-bit matrix cores, fp32-accurate by operand splitting (scream_gemm_wgrad_split_f32);
-    "bf16": one bf16 product, fp32 accumulation (scream_gemm_wgrad_bf16_f32)."""
-    lib = _lib.load()
-    if split == "bf16":  # one bf16 product (scream_gemm_wgrad_bf16_f32): the fp32 entry point's arguments
-        name, sizer, split = "scream_gemm_wgrad_bf16_f32", "scream_wgrad_bf16_workspace_bytes", None
-    else:
-        name = "scream_gemm_wgrad_f32" if split is None else "scream_gemm_wgrad_split_f32"
-        sizer = "scream_wgrad_workspace_bytes" if split is None else "scream_wgrad_split_workspace_bytes"
-    rows = dY.shape[0] if rows is None else rows
-    N, K = dY.shape[1], X.shape[1]
-    ws = _workspace(getattr(lib, sizer), sizer, rows, N, K, device=dY.device)
-    check(getattr(lib, name)(dY.data_ptr(), dY.stride(0) if ldy is None else ldy, X.data_ptr(), X.stride(0) if ldx is None else ldx,
-                             rows, N, K, _p(dW), int(accumulate), _p(colsum), *(() if split is None else (split,)),
-                             ws.data_ptr(), ws.numel(), _stream()), name)
-    return dW
+SPLIT_K = 256  # a data gradient whose K scream_gemm_split_f32 does not take runs as products of this depth
 
 
-def wgrad_bf16(dY, X, dW, colsum=None, accumulate=False, ldy=None, ldx=None, rows=None) -> torch.Tensor:
-    return wgrad(dY, X, dW, colsum, accumulate, ldy, ldx, rows, "bf16")
+def split_gemm_takes_k(K: int) -> bool:  # scream_gemm_split_f32's summed dimension: 64 + 192 j (K_64_PLUS_192, csrc/matrix_front.h)
+    return K > 0 and K % 64 == 0 and (K // 32 - 2) % 3 == 0
 
 
-def wgrad_split(dY, X, dW, colsum=None, accumulate=False, ldy=None, ldx=None, rows=None, split: int = SPLIT_BF3) -> torch.Tensor:
-    return wgrad(dY, X, dW, colsum, accumulate, ldy, ldx, rows, split)
+class Gemms:
+    """The matrix products of ONE training step in one arithmetic, a subclass each: fwd = epilogue(A W^T) and dgrad = dY W for
+    W [N,K], and the weight gradient, whose body is this one: a subclass names its entry point, its sizer and `name`."""
+
+    def wgrad(self, dY, X, dW, colsum=None, accumulate=False, ldy=None, ldx=None, rows=None) -> torch.Tensor:
+        """dW[N,K] (+)= dY^T X over rows; dW any contiguous tensor of N * K floats."""
+        return self._wgrad(dY, X, dW, colsum, accumulate, ldy, ldx, rows)
+
+    def _wgrad(self, dY, X, dW, colsum, accumulate, ldy, ldx, rows, *extra) -> torch.Tensor:
+        lib = _lib.load()
+        rows = dY.shape[0] if rows is None else rows
+        N, K = dY.shape[1], X.shape[1]
+        ws = _workspace(getattr(lib, self.wgrad_sizer), self.wgrad_sizer, rows, N, K, device=dY.device)
+        check(getattr(lib, self.wgrad_entry)(dY.data_ptr(), dY.stride(0) if ldy is None else ldy, X.data_ptr(),
+                                             X.stride(0) if ldx is None else ldx, rows, N, K, _p(dW), int(accumulate), _p(colsum),
+                                             *extra, ws.data_ptr(), ws.numel(), _stream()), self.wgrad_entry)
+        return dW
 
 
-SPLIT_K = 256  # a data gradient whose K scream_gemm_split_f32 does not take (K != 64 + 192 j) runs as products of this depth
-
-
-class _Gemms:
-    """The matrix products of ONE training step in the arithmetic of net.train_backend: the single dispatch point of the
-    forward GEMMs, the data gradients and the weight gradients.  Every weight matrix enters one forward product and one
-    data-gradient product per step, so "split" packs each (and each transpose) exactly once per step, where it is used."""
-
-    split = bf16 = False  # the "f32" arm
-
-    def __init__(self, net):
-        backend = net._check_train_backend(net.train_backend)
-        self.split, self.bf16 = backend == "split", backend == "bf16"
+class F32Gemms(Gemms):
+    """Every product on the fp32-input MFMA; a data gradient is a GEMM against the transposed weight [K,N], which sums over N."""
+    name, wgrad_entry, wgrad_sizer = "f32", "scream_gemm_wgrad_f32", "scream_wgrad_workspace_bytes"
 
     def fwd(self, A, W, epilogue: int = EPI_NONE, n_act: int = 0, bias=None):
-        """epilogue(A W^T) for W [N,K]."""
-        if self.bf16:
-            return ops.gemm_bf16(A, W, epilogue, n_act=n_act, bias=bias)
-        if not self.split:
-            return gemm_f32(A, W, epilogue, n_act=n_act, bias=bias)
+        return ops.gemm_f32(A, W, epilogue, n_act=n_act, bias=bias)
+
+    def dgrad(self, dY, W, out=None):
+        return ops.gemm_f32(dY, transpose(W), out=out)
+
+
+class SplitGemms(Gemms):
+    """fp32-accurate products on the 16-bit matrix cores (SPLIT_BF3); each weight (and each transpose) is packed where it is used."""
+    name, wgrad_entry, wgrad_sizer = "split", "scream_gemm_wgrad_split_f32", "scream_wgrad_split_workspace_bytes"
+
+    def fwd(self, A, W, epilogue: int = EPI_NONE, n_act: int = 0, bias=None):
         return ops.gemm_split(A, ops.pack_w(W, SPLIT_BF3), epilogue, n_act=n_act, bias=bias)
 
     def dgrad(self, dY, W, out=None):
-        """dX = dY W for W [N,K]: a GEMM against the transposed weight [K,N], which sums over N ("bf16": W as it is)."""
-        if self.bf16:
-            return ops.gemm_dgrad_bf16(dY, W, out=out)
-        Wt = transpose(W)
-        if not self.split:
-            return gemm_f32(dY, Wt, out=out)
-        N = W.shape[0]
-        if N >= 64 and N % 64 == 0 and (N // 32 - 2) % 3 == 0:  # what scream_gemm_split_f32 takes: 64 + 192 j
+        Wt, N = transpose(W), W.shape[0]
+        if split_gemm_takes_k(N):
             return ops.gemm_split(dY, ops.pack_w(Wt, SPLIT_BF3), out=out)
-        assert N % SPLIT_K == 0
-        lib, M = _lib.load(), dY.shape[0]
-        if out is None:
-            out = torch.empty(M, W.shape[1], device=dY.device, dtype=torch.float32)
+        if N % SPLIT_K:
+            raise _lib.ScreamHipError("the split data gradient sums over N = %d: neither 64 + 192 j nor a multiple of %d" % (N, SPLIT_K))
+        out = torch.empty(dY.shape[0], W.shape[1], device=dY.device, dtype=torch.float32) if out is None else out
         tmp = torch.empty_like(out)
         for c in range(0, N, SPLIT_K):  # column blocks of dY in order: a fixed-order sum
-            pk = ops.pack_w(Wt[:, c:c + SPLIT_K], SPLIT_BF3)
-            dst = tmp if c else out
-            check(lib.scream_gemm_split_f32(_ptr(dY, c), dY.stride(0), pk.data_ptr(), _p(dst), dst.stride(0), M, pk.N, SPLIT_K,
-                                            EPI_NONE, 0, None, None, 0, None, None, 0, SPLIT_BF3, 0, 0, _stream()),
-                  "scream_gemm_split_f32")
+            ops.gemm_split(dY[:, c:c + SPLIT_K], ops.pack_w(Wt[:, c:c + SPLIT_K], SPLIT_BF3), out=tmp if c else out)
             if c:
                 add_(out, tmp)
         return out
 
-    def wgrad(self, dY, X, dW, colsum=None):
-        return wgrad(dY, X, dW, colsum, split="bf16" if self.bf16 else SPLIT_BF3 if self.split else None)
+    def wgrad(self, dY, X, dW, colsum=None, accumulate=False, ldy=None, ldx=None, rows=None, split: int = SPLIT_BF3) -> torch.Tensor:
+        return self._wgrad(dY, X, dW, colsum, accumulate, ldy, ldx, rows, split)
+
+
+class Bf16Gemms(Gemms):
+    """ONE bf16 product per GEMM, fp32 accumulation; W is read as it is (torch's [N,K]) by all three products."""
+    name, wgrad_entry, wgrad_sizer = "bf16", "scream_gemm_wgrad_bf16_f32", "scream_wgrad_bf16_workspace_bytes"
+
+    def fwd(self, A, W, epilogue: int = EPI_NONE, n_act: int = 0, bias=None):
+        return ops.gemm_bf16(A, W, epilogue, n_act=n_act, bias=bias)
+
+    def dgrad(self, dY, W, out=None):
+        return ops.gemm_dgrad_bf16(dY, W, out=out)
+
+
+ARITHMETICS = {c.name: c for c in (F32Gemms, SplitGemms, Bf16Gemms)}
+wgrad, wgrad_split, wgrad_bf16 = F32Gemms().wgrad, SplitGemms().wgrad, Bf16Gemms().wgrad
+
+
+def gemms(backend: str) -> Gemms:
+    """The arithmetic of net.train_backend = backend; a name the models do not know raises their ValueError."""
+    from .model import PointTransformer
+    return ARITHMETICS[PointTransformer._check_train_backend(backend)]()
 
 
 def ln_fwd(a: torch.Tensor, b, gamma, beta, out: torch.Tensor = None):
@@ -196,7 +198,11 @@ def _cat(*ws) -> torch.Tensor:
     return torch.cat([w for w in ws], dim=0).contiguous()
 
 
-def _block_fwd(P, mm: _Gemms, prefix: str, x: torch.Tensor, t, batch: PackedBatch, r0: int, cb: int, n: int,
+def _coor_w(P, k: int) -> torch.Tensor:  # coor_mlp.k's 1 x 1 convolution weight [out, in, 1] as the matrix [out, in]
+    return _w(P, "coor_mlp.%d.weight" % k)[:, :, 0].contiguous()
+
+
+def _block_fwd(P, mm: Gemms, prefix: str, x: torch.Tensor, t, batch: PackedBatch, r0: int, cb: int, n: int,
                out: torch.Tensor = None) -> (torch.Tensor, _Layer):
     """One block (models/transformer.py:74-90) on rows [r0, r0 + x.shape[0]) whose clouds are [cb, cb + n).  t: the target
     features (rows batch.rows_src ..) of a cross layer, None for a self layer.  out: where the block output goes (default:
@@ -227,7 +233,7 @@ def _block_fwd(P, mm: _Gemms, prefix: str, x: torch.Tensor, t, batch: PackedBatc
     return y, L
 
 
-def _block_bwd(P, G, mm: _Gemms, L: _Layer, dy: torch.Tensor, batch: PackedBatch, dt) -> None:
+def _block_bwd(P, G, mm: Gemms, L: _Layer, dy: torch.Tensor, batch: PackedBatch, dt) -> None:
     """dy [rows, 256] (the gradient of the block output) is REPLACED by the gradient of the block input; a cross layer adds
     the gradient of its key/value input into dt (the target features' gradient)."""
     w = lambda s: _w(P, L.prefix + s)
@@ -295,8 +301,8 @@ def _stem_passes(net, batch: PackedBatch) -> List[List[Tuple[str, int, int, int,
 def forward_saving(net, batch: PackedBatch):
     """The training forward: packed src_pred [rows_src, 3] and what the backward needs."""
     from .model import pe_dim_t
+    mm = gemms(net.train_backend)
     P = dict(net.named_parameters())
-    mm = _Gemms(net)
     dev = batch.xyz.device
     rs, rt, B = batch.rows_src, batch.rows_total, batch.n_pairs
     z0 = torch.empty(rt, D_MODEL, device=dev, dtype=torch.float32)
@@ -318,10 +324,9 @@ def forward_saving(net, batch: PackedBatch):
     for j, prefix in enumerate(_layer_prefixes(net)[2]):
         sf, L = _block_fwd(P, mm, prefix, sf, tf if j % 2 else None, batch, 0, 0, B)
         layers.append(L)
-    c = lambda k: _w(P, "coor_mlp.%d" % k + ".weight")[:, :, 0].contiguous()
-    h1 = mm.fwd(sf, c(0), EPI_BIAS_RELU, bias=_w(P, "coor_mlp.0.bias"))
-    h2 = mm.fwd(h1, c(2), EPI_BIAS_RELU, bias=_w(P, "coor_mlp.2.bias"))
-    out = ops.coor_head(h2, c(4), _w(P, "coor_mlp.4.bias"))
+    h1 = mm.fwd(sf, _coor_w(P, 0), EPI_BIAS_RELU, bias=_w(P, "coor_mlp.0.bias"))
+    h2 = mm.fwd(h1, _coor_w(P, 2), EPI_BIAS_RELU, bias=_w(P, "coor_mlp.2.bias"))
+    out = ops.coor_head(h2, _coor_w(P, 4), _w(P, "coor_mlp.4.bias"))
     return out, dict(z0=z0, s0=s0, layers=layers, n_stem=n_stem, sf=sf, h1=h1, h2=h2, mm=mm)
 
 
@@ -329,22 +334,21 @@ def backward(net, batch: PackedBatch, saved, dout: torch.Tensor) -> List[torch.T
     """Gradients of every parameter (named_parameters order) for the packed output gradient dout [rows_src, 3]."""
     P = dict(net.named_parameters())
     G = {n: torch.empty_like(p, dtype=torch.float32) for n, p in P.items()}
-    mm = saved["mm"]  # the arithmetic, and the packed weights, of the forward this backward belongs to
+    mm = saved["mm"]  # the arithmetic of the forward this backward belongs to (it holds no weights: each is packed where used)
     dev = dout.device
     rs, rt = batch.rows_src, batch.rows_total
     dout = dout.to(torch.float32).contiguous()
-    c = lambda k: _w(P, "coor_mlp.%d" % k + ".weight")[:, :, 0].contiguous()
     # coor_mlp (models/pointnet.py:27-33,60)
     h1, h2 = saved["h1"], saved["h2"]
     grad3(h2, dout, G["coor_mlp.4.weight"], False, col_s=G["coor_mlp.4.bias"])
     dh2 = torch.empty(rs, D_MODEL, device=dev, dtype=torch.float32)
-    check(_lib.load().scream_coor_head_bwd(_p(dout), _p(c(4)), _p(h2), _p(dh2), rs, _stream()), "scream_coor_head_bwd")
+    check(_lib.load().scream_coor_head_bwd(_p(dout), _p(_coor_w(P, 4)), _p(h2), _p(dh2), rs, _stream()), "scream_coor_head_bwd")
     mm.wgrad(dh2, h1, G["coor_mlp.2.weight"], G["coor_mlp.2.bias"])
-    dh1 = mm.dgrad(dh2, c(2))
+    dh1 = mm.dgrad(dh2, _coor_w(P, 2))
     relu_bwd(dh1, h1)
     mm.wgrad(dh1, saved["sf"], G["coor_mlp.0.weight"], G["coor_mlp.0.bias"])
     dF = torch.zeros(rt, D_MODEL, device=dev, dtype=torch.float32)  # gradient of the features of all rows
-    mm.dgrad(dh1, c(0), out=dF[:rs])
+    mm.dgrad(dh1, _coor_w(P, 0), out=dF[:rs])
     del dh1, dh2
     layers, n_stem = saved["layers"], saved["n_stem"]
     for L in reversed(layers[n_stem:]):  # cross stage: source rows; the target features collect every cross layer's gradient

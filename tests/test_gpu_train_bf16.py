@@ -283,14 +283,14 @@ def test_a_restatement_without_one_rounding_is_over_the_bar(drop):
 
 def test_one_gemm_on_the_f32_path_is_over_the_bar(monkeypatch):
     sd, pairs, net, loss, g, masks, _, _ = point_case(1, 1, ((300, 280),))
-    plain = train._Gemms.fwd
+    plain = train.Bf16Gemms.fwd
 
     def fwd(self, A, W, epilogue=EPI_NONE, n_act=0, bias=None):
         if W.shape[0] == 1024:  # the FFN's first product of every block
             return ops.gemm_f32(A, W, epilogue, n_act=n_act, bias=bias)
         return plain(self, A, W, epilogue, n_act=n_act, bias=bias)
 
-    monkeypatch.setattr(train._Gemms, "fwd", fwd)
+    monkeypatch.setattr(train.Bf16Gemms, "fwd", fwd)
     _, g1, masks1 = T.point_gpu(point_net(sd, 1, 1), pairs, DEV)
     g64r, g32r = restated(T.oracle_grads, sd, pairs, masks1)
     bad = T.rule("bf16 (1,1) with mlp.0 on the fp32 path", g1, g64r, g32r)

@@ -1,6 +1,6 @@
 """The backward entry points of include/scream_hip.h ("Training") one by one against float64, at the shapes, options and edges
 the training step drives them with (scream_amd/train.py): optional pointers NULL and set, accumulate on and off, one row, a
-partial block, 300 000 rows, leading dimensions wider than the matrix, padded rows; then the data gradients of train._Gemms
+partial block, 300 000 rows, leading dimensions wider than the matrix, padded rows; then the data gradients of train.gemms()
 on both arithmetics and one block (train._block_fwd + train._block_bwd) end to end.
 
 Bars: an elementwise kernel equals the fp32 expression bit for bit; a reduction is held to <= max(2 x the error of the same
@@ -401,14 +401,12 @@ def test_wgrad_at_the_qkv_shapes_and_wide_leading_dimensions(split):
 
 # ------------------------------------------------------------------------------------- data gradients
 def gemms(split):
-    mm = train._Gemms.__new__(train._Gemms)  # the dispatch point without a model around it
-    mm.split = split
-    return mm
+    return train.gemms("split" if split else "f32")
 
 
 @pytest.mark.parametrize("split", [False, True])
 def test_data_gradients_at_the_five_weight_shapes_against_float64(split):
-    """train._Gemms.dgrad, dX = dY W, for the weights of a block.  Under "split", 768 and 512 summed columns run as K = 256
+    """The arithmetic's dgrad, dX = dY W, for the weights of a block.  Under "split", 768 and 512 summed columns run as K = 256
     products added in column order (scream_add_f32): twice, bitwise equal."""
     rng = np.random.default_rng(170 + split)
     mm = gemms(split)
@@ -421,6 +419,32 @@ def test_data_gradients_at_the_five_weight_shapes_against_float64(split):
         held("dgrad %s %d x %d" % ("split" if split else "f32", N, K), got, want, cpu32)
         out = torch.full_like(got, 7.0)
         assert mm.dgrad(dY.to(DEV), W.to(DEV), out=out) is out and torch.equal(out, got)  # out=, and a second call
+
+
+def test_gemm_f32_and_gemm_split_take_row_strided_views():
+    """A = columns 256..511 of a [256, 768] matrix (two row tiles: a wrong row stride shows between them), out = the same
+    columns of another; every other column of both holds 7.0.  The result equals the call on contiguous copies bit for bit,
+    the columns outside the slice stay 7.0, and a view with column stride 2 raises before any launch."""
+    rng = np.random.default_rng(175)
+    wideA = torch.full((256, 768), 7.0)
+    wideA[:, 256:512] = randn(rng, 256, 256)
+    wideA, W = wideA.to(DEV), (randn(rng, 256, 256) / 16).to(DEV)
+    Wp = ops.pack_w(W, _lib.SPLIT_BF3)
+    A = wideA[:, 256:512]
+    assert A.stride() == (768, 1) and not A.is_contiguous()
+    for what, gemm in (("gemm_f32", lambda a, out: ops.gemm_f32(a, W, out=out)), ("gemm_split", lambda a, out: ops.gemm_split(a, Wp, out=out))):
+        wide_out = torch.full((256, 768), 7.0, device=DEV)
+        out = wide_out[:, 256:512]
+        assert gemm(A, out) is out
+        want = gemm(A.contiguous(), torch.empty(256, 256, device=DEV))
+        assert torch.equal(out, want), what
+        assert (wide_out[:, :256] == 7.0).all() and (wide_out[:, 512:] == 7.0).all(), what
+        before = wide_out.clone()
+        with pytest.raises(ValueError):
+            gemm(wideA[:, 0:512:2], torch.empty(256, 256, device=DEV))
+        with pytest.raises(ValueError):
+            gemm(A, wide_out[:, 0:512:2])
+        assert torch.equal(wide_out, before), what
 
 
 # ------------------------------------------------------------------------------------- one block end to end

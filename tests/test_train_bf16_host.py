@@ -131,14 +131,29 @@ def test_the_drivers_take_the_backend(driver, monkeypatch):
         mod.main(["--train-backend", "fp16"])
 
 
-def test_train_wrappers_dispatch_the_bf16_arm_without_a_gpu():
-    """_Gemms is the one dispatch point; a weight gradient whose N the library refuses raises from the bf16 sizer."""
+def test_train_wrappers_dispatch_the_bf16_arm_without_a_gpu(monkeypatch):
+    """train.gemms(backend) is the one dispatch point, and what forward_saving takes for a model with that train_backend; a
+    weight gradient whose N the library refuses raises from the bf16 sizer."""
     from scream_amd import train
     net = PointTransformer(256, 1, 1)
-    for backend, flags in (("f32", (False, False)), ("split", (True, False)), ("bf16", (False, True))):
+    taken, plain = [], train.gemms
+
+    class Taken(Exception):
+        pass
+
+    def recording(backend):  # forward_saving chooses its arithmetic first: stop it there, before it needs a batch
+        taken.append(plain(backend))
+        raise Taken
+
+    for backend in ("f32", "split", "bf16"):
         net.train_backend = backend
-        mm = train._Gemms(net)
-        assert (mm.split, mm.bf16) == flags
+        monkeypatch.setattr(train, "gemms", recording)
+        with pytest.raises(Taken):
+            train.forward_saving(net, None)
+        monkeypatch.setattr(train, "gemms", plain)
+        for mm in (train.gemms(backend), taken.pop()):
+            assert type(mm) is train.ARITHMETICS[backend] and mm.name == backend
+    assert not taken
     with pytest.raises(_lib.ScreamHipError, match=r"scream_wgrad_bf16_workspace_bytes\(300, 200, 256\)"):
         train.wgrad_bf16(torch.zeros(300, 200), torch.zeros(300, 256), None)
 

@@ -5,7 +5,7 @@ beside the HBM roof.
     python tools/gemm_bf16_bench.py [--rows 65536,330240] [--reps 20] [--json OUT]
 
 Per row count and (N, K) of the training step -- (256,256) merge / q, (768,256) q|k|v, (1024,256) mlp.0, (256,1024) mlp.2 -- the
-forward C = A W^T, the data gradient dX = dY W and the weight gradient dW = dY^T X are timed through train._Gemms, i.e. with
+forward C = A W^T, the data gradient dX = dY W and the weight gradient dW = dY^T X are timed through train.gemms(backend), i.e. with
 everything a training step launches for them: "split" packs W (and transposes it for the data gradient, which runs in K = 256
 chunks plus adds where the summed dimension is 768 or 1024), "bf16" is one launch (two for the weight gradient).  Legs
 alternate split / bf16 / split / bf16; each figure is the median over --reps calls of device-event times after a warm-up
@@ -50,11 +50,7 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("gemm_bf16_bench.py measures on the MI355X; no GPU found")
-    net = PointTransformer(256, 1, 1)
-    mms = {}
-    for backend in ("split", "bf16"):
-        net.train_backend = backend
-        mms[backend] = train._Gemms(net)
+    mms = {backend: train.gemms(backend) for backend in PointTransformer.TRAIN_BACKENDS}
     out = []
     g = torch.Generator(device=DEV).manual_seed(0)
     rnd = lambda *s: torch.randn(*s, device=DEV, generator=g)

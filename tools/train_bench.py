@@ -144,7 +144,7 @@ def main():
     ap.add_argument("--points", default="4000,16000", help="DSM points per sample (dem)")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--train-backend", choices=("f32", "split", "bf16"), default="f32", help="net.train_backend of the training legs")
+    ap.add_argument("--train-backend", choices=PointTransformer.TRAIN_BACKENDS, default="f32", help="net.train_backend of the training legs")
     ap.add_argument("--wgrad-only", action="store_true")
     ap.add_argument("--no-wgrad", action="store_true", help="training legs only (the legs of a backend comparison)")
     ap.add_argument("--json", default=None)

@@ -19,6 +19,7 @@ from torch.utils import data
 from scream_amd import FusedAdam
 from scream_amd.data import RawPairFiles, SyntheticRawPairs
 from scream_amd.fit import fit, gan_training, pair_preparer, pair_real_rows, val_loss
+from scream_amd.model import PointTransformer
 
 use_GAN = False
 generator_save_path = "params/point-generator.pth"
@@ -90,7 +91,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1, help="pairs per step (the reference trains at 1)")
     ap.add_argument("--synthetic", type=int, default=0)
-    ap.add_argument("--train-backend", choices=("f32", "split", "bf16"), default=None)
+    ap.add_argument("--train-backend", choices=PointTransformer.TRAIN_BACKENDS, default=None)
     ap.add_argument("--epochs", type=int, default=epochs)
     ap.add_argument("--gan", action="store_true", help="train with the adversarial loss (use_GAN)")
     a = ap.parse_args(argv)
