@@ -19,6 +19,7 @@ Deliberate differences from evaluate_3d_match.py, all documented in DESIGN.md:
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import math
 import os
 from typing import Callable, Iterable, List, Optional, Sequence
@@ -68,16 +69,23 @@ def gt_pose_metric(rot: torch.Tensor, trans: torch.Tensor, s: float, c: torch.Te
     return torch.cat([torch.cat([rot, t], dim=1), torch.tensor([[0.0, 0.0, 0.0, 1.0]])], dim=0)
 
 
+def _strip_pair(src, tgt, rot, trans, s, c):
+    """The six fields every registration item has (a KITTI item is exactly these), raw or from a DataLoader(batch_size=1)."""
+    if torch.is_tensor(src) and src.dim() == 3:
+        src, tgt, rot, trans, c = src[0], tgt[0], rot[0], trans[0], c[0]
+        s = s[0] if torch.is_tensor(s) or isinstance(s, (list, tuple)) else s
+    return src.float(), tgt.float(), rot.float(), trans.float(), (float(s.item()) if torch.is_tensor(s) else float(s)), c.float()
+
+
 def _strip(item):
     """Accept both raw dataset items and DataLoader(batch_size=1) collations of them."""
     src, tgt, rot, trans, s, idx, cov, c, scene = item
     if torch.is_tensor(src) and src.dim() == 3:
-        src, tgt, rot, trans, idx, cov, c = src[0], tgt[0], rot[0], trans[0], idx[0], cov[0], c[0]
-        s = s[0] if torch.is_tensor(s) or isinstance(s, (list, tuple)) else s
+        idx, cov = idx[0], cov[0]
         scene = scene[0] if torch.is_tensor(scene) or isinstance(scene, (list, tuple)) else scene
-    s = float(s.item()) if torch.is_tensor(s) else float(s)
+    src, tgt, rot, trans, s, c = _strip_pair(src, tgt, rot, trans, s, c)
     scene = int(scene.item()) if torch.is_tensor(scene) else int(scene)
-    return src.float(), tgt.float(), rot.float(), trans.float(), s, [int(v) for v in idx], np.asarray(cov, dtype=np.float32), c.float(), scene
+    return src, tgt, rot, trans, s, [int(v) for v in idx], np.asarray(cov, dtype=np.float32), c, scene
 
 
 def aggregate_rows(rows: np.ndarray, re_static_method: str = "median"):
@@ -109,6 +117,21 @@ _staging = {}  # (device, lane stream) -> StagingBuffers
 IN_FLIGHT = int(os.environ.get("SCREAM_IN_FLIGHT", "4"))
 
 
+@dataclasses.dataclass
+class LaneResult:
+    """One lane's results (_register_lane), on the device but for ``T_gt``.  ``run``, ``accept`` (which holds the Kabsch pose) and
+    ``stream`` are set only while a long ICP schedule is out in pieces: continue_long_icp() enqueues the rest where the lane ran."""
+    T: torch.Tensor
+    re: torch.Tensor
+    te: torch.Tensor
+    loss: torch.Tensor
+    T_gt: torch.Tensor
+    T_gt_d: torch.Tensor
+    run: Optional[ops.IcpRun]
+    accept: Optional[Callable]
+    stream: Optional[torch.cuda.Stream]
+
+
 def _register_lane(net, its, centers, pair_ids, corr, dis_thresh, icp, icp_dist, icp_iters, device, pred_hook, backend=None):
     """Device part of register_items for one lane (runs on the current stream): pack, A1-A6, A7-A9, A10 (+ GPU ICP).
     Nothing here blocks the host: the batch and every per-pair scalar go up in two asynchronous copies from pinned
@@ -132,7 +155,7 @@ def _register_lane(net, its, centers, pair_ids, corr, dis_thresh, icp, icp_dist,
         src_pred = pred_hook(batch, src_pred, pair_ids)
     T, n_corr, idx, dmin, valid = register_batch(batch, src_pred, s, c, dis_thresh, corr)
     re, te = ops.transformation_error_batched(T, T_gt_d)
-    out = {"T_gt": T_gt, "T_gt_d": T_gt_d, "run": None}
+    pieces = (None, None, None)  # (run, accept, stream) of a long ICP schedule that is out in pieces
     if isinstance(icp, str):
         if icp != "gpu":
             raise ValueError("icp must be None, 'gpu' or a callable")
@@ -157,13 +180,81 @@ def _register_lane(net, its, centers, pair_ids, corr, dis_thresh, icp, icp_dist,
             # waits while it enqueues (until round 3 the C call itself synchronised every 32 iterations).
             run = ops.IcpRun(*icp_args)
             run.advance(ops.ICP_ASYNC_ITERS)
-            run.accept, run.stream = accept, torch.cuda.current_stream(device)
-            out["run"] = run
+            pieces = (run, accept, torch.cuda.current_stream(device))
             T, re, te = accept(run.T)
     # PointTransformer.loss per pair (models/pointnet.py:93-99, evaluate_3d_match.py:86) for the whole batch in one launch
     loss = ops.point_loss(src_pred.contiguous(), batch.xyz[: batch.rows_src], batch.src_row0, batch.src_len_dev, rot_d, trans_d)
-    out.update(T=T, re=re, te=te, loss=loss)
-    return out
+    return LaneResult(T, re, te, loss, T_gt, T_gt_d, *pieces)
+
+
+class RegisteredBatch:
+    """One batch with A1-A10 (+ optional GPU ICP) enqueued by the constructor; ``finish()`` waits for the device and gives the
+    host arrays of register_items.  Arguments as register_items_async's."""
+
+    def __init__(self, net, its, centers, pair_ids, corr, dis_thresh, icp, icp_dist, icp_iters, device, pred_hook, lanes, stream,
+                 backend):
+        self.its, self.icp, self.device = its, icp, device
+        self.on_stream = (lambda: torch.cuda.stream(stream)) if stream is not None else contextlib.nullcontext
+        if stream is not None:
+            lanes = 1
+            stream.wait_stream(torch.cuda.current_stream(device))  # (normally idle: orders the batch behind whatever the caller queued)
+        if lanes is None:
+            lanes = _lanes.DEFAULT_LANES if len(its) >= 8 else 1
+        parts = _lanes.split_weighted([it[0].shape[0] + it[1].shape[0] for it in its], lanes)
+        with self.on_stream():
+            # (lane-stream allocations stay referenced from here until finish() has consumed the copy)
+            self.lanes = _lanes.run(device, parts, lambda rg: _register_lane(
+                net, [its[i] for i in rg], [centers[i] for i in rg], [pair_ids[i] for i in rg], corr, dis_thresh, icp, icp_dist,
+                icp_iters, device, pred_hook, backend))
+            self.publish()
+            self.T_gt = torch.cat([o.T_gt for o in self.lanes])
+            self.T_gt_d = torch.cat([o.T_gt_d for o in self.lanes])
+
+    def publish(self):  # one small device buffer -> one asynchronous D2H copy into pinned memory
+        T = torch.cat([o.T for o in self.lanes])
+        re, te = torch.cat([o.re for o in self.lanes]), torch.cat([o.te for o in self.lanes])
+        loss = torch.cat([o.loss for o in self.lanes]).reshape(-1)
+        self.flat = torch.cat([T.reshape(-1), re, te, loss]).float()
+        self.host = torch.empty(self.flat.shape, dtype=torch.float32, pin_memory=True)
+        self.host.copy_(self.flat, non_blocking=True)
+        self.done = torch.cuda.current_stream(self.device).record_event()
+
+    def continue_long_icp(self):
+        """Only for schedules longer than ops.ICP_ASYNC_ITERS whose first piece left a pair moving: more pieces, then the ICP's
+        tail and the result copy again (scream_amd/ops.py: IcpRun).  Runs when the batch is COLLECTED, i.e. behind the enqueueing
+        of the following batches -- the device has their work while the host waits here."""
+        events = []
+        for o in self.lanes:
+            if o.run is None or o.run.all_stopped():
+                continue
+            with torch.cuda.stream(o.stream):
+                piece = 2 * ops.ICP_ASYNC_ITERS
+                while not o.run.all_stopped():
+                    o.run.advance(piece)
+                    piece *= 2
+                o.T, o.re, o.te = o.accept(o.run.T)
+                events.append(o.stream.record_event())
+        if events:
+            with self.on_stream():
+                for ev in events:
+                    torch.cuda.current_stream(self.device).wait_event(ev)
+                self.publish()
+
+    def finish(self):
+        self.continue_long_icp()
+        self.done.synchronize()
+        B = len(self.its)
+        h = self.host.numpy().astype(np.float64)
+        T_h = h[:16 * B].reshape(B, 4, 4).astype(np.float32)
+        re_h, te_h, loss_h = h[16 * B:17 * B].copy(), h[17 * B:18 * B].copy(), h[18 * B:19 * B].copy()
+        if callable(self.icp):  # e.g. a wrapper around o3d.registration_icp: (item, T_init) -> T
+            for i, it in enumerate(self.its):
+                refined = np.asarray(self.icp(it, T_h[i]), dtype=np.float32)
+                r1, t1 = ops.transformation_error_batched(torch.from_numpy(refined[None]).to(self.device), self.T_gt_d[i:i + 1].contiguous())
+                if r1.item() <= re_h[i] and t1.item() <= te_h[i]:
+                    T_h[i], re_h[i], te_h[i] = refined, r1.item(), t1.item()
+        self.lanes = self.flat = self.host = self.done = self.T_gt_d = None  # consumed: the slot's next batch must not find them held
+        return T_h, self.T_gt.numpy(), re_h, te_h, loss_h
 
 
 @torch.no_grad()
@@ -176,78 +267,11 @@ def register_items_async(net, its: Sequence[tuple], centers: Sequence[torch.Tens
     the host arrays of register_items.  Everything between the call and ``finish()`` overlaps the GPU work, which is
     how evaluate_loader hides the host side of batch i-1 and the packing of batch i+1 behind batch i.
     ``stream``: run the WHOLE batch -- one packed forward, search, solve, ICP, result copy -- on that stream and leave the
-    current stream alone (evaluate_loader alternates two such streams between consecutive batches, below).
+    current stream alone (evaluate_loader gives consecutive batches different streams, scream_amd/lanes.py: in_flight).
     ``backend``: the forward's arithmetic for THIS batch (PointTransformer.forward_packed(backend=); None = the model's own)."""
     device = device or next(net.parameters()).device
-    if stream is not None:
-        lanes = 1
-        stream.wait_stream(torch.cuda.current_stream(device))  # (normally idle: orders the batch behind whatever the caller queued)
-    if lanes is None:
-        lanes = _lanes.DEFAULT_LANES if len(its) >= 8 else 1
-    parts = _lanes.split_weighted([it[0].shape[0] + it[1].shape[0] for it in its], lanes)
-    with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
-        outs = _lanes.run(device, parts, lambda rg: _register_lane(
-            net, [its[i] for i in rg], [centers[i] for i in rg], [pair_ids[i] for i in rg], corr, dis_thresh, icp, icp_dist,
-            icp_iters, device, pred_hook, backend))
-        pub = {}
-
-        def publish():  # one small device buffer -> one asynchronous D2H copy into pinned memory
-            T = torch.cat([o["T"] for o in outs])
-            re, te = torch.cat([o["re"] for o in outs]), torch.cat([o["te"] for o in outs])
-            loss = torch.cat([o["loss"] for o in outs]).reshape(-1)
-            flat = torch.cat([T.reshape(-1), re, te, loss]).float()
-            host = torch.empty(flat.shape, dtype=torch.float32, pin_memory=True)
-            host.copy_(flat, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(torch.cuda.current_stream(device))
-            pub.update(flat=flat, host=host, done=done)
-
-        publish()
-        T_gt = torch.cat([o["T_gt"] for o in outs])
-        T_gt_d = torch.cat([o["T_gt_d"] for o in outs])
-    keep = [outs, pub]  # lane-stream allocations stay referenced until the copy has been consumed
-
-    def continue_long_icp():
-        """Only for schedules longer than ops.ICP_ASYNC_ITERS whose first piece left a pair moving: more pieces, then the ICP's
-        tail and the result copy again (scream_amd/ops.py: IcpRun).  Runs when the batch is COLLECTED, i.e. behind the enqueueing
-        of the following batches -- the device has their work while the host waits here."""
-        redo = False
-        for o in outs:
-            run = o["run"]
-            if run is None or run.all_stopped():
-                continue
-            redo = True
-            with torch.cuda.stream(run.stream):
-                piece = 2 * ops.ICP_ASYNC_ITERS
-                while not run.all_stopped():
-                    run.advance(piece)
-                    piece *= 2
-                o["T"], o["re"], o["te"] = run.accept(run.T)
-                ev = torch.cuda.Event()
-                ev.record(run.stream)
-            with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
-                torch.cuda.current_stream(device).wait_event(ev)
-        if redo:
-            with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
-                publish()
-
-    def finish():
-        continue_long_icp()
-        pub["done"].synchronize()
-        B = len(its)
-        h = pub["host"].numpy().astype(np.float64)
-        T_h = h[:16 * B].reshape(B, 4, 4).astype(np.float32)
-        re_h, te_h, loss_h = h[16 * B:17 * B].copy(), h[17 * B:18 * B].copy(), h[18 * B:19 * B].copy()
-        if callable(icp):  # e.g. a wrapper around o3d.registration_icp: (item, T_init) -> T
-            for i, it in enumerate(its):
-                refined = np.asarray(icp(it, T_h[i]), dtype=np.float32)
-                r1, t1 = ops.transformation_error_batched(torch.from_numpy(refined[None]).to(device), T_gt_d[i:i + 1].contiguous())
-                if r1.item() <= re_h[i] and t1.item() <= te_h[i]:
-                    T_h[i], re_h[i], te_h[i] = refined, r1.item(), t1.item()
-        keep.clear()
-        return T_h, T_gt.numpy(), re_h, te_h, loss_h
-
-    return finish
+    return RegisteredBatch(net, its, centers, pair_ids, corr, dis_thresh, icp, icp_dist, icp_iters, device, pred_hook, lanes,
+                           stream, backend).finish
 
 
 def register_items(net, its: Sequence[tuple], centers: Sequence[torch.Tensor], pair_ids: Sequence[int],
@@ -304,7 +328,6 @@ def evaluate_loader(net, loader: Iterable, corr: str = "tgt", dis_thresh: float 
     rank, world = sdist.rank_world()
     mine = sdist.shard_indices(n, rank, world)
     rows: List[np.ndarray] = []
-    done = 0
     # var-len batches are lists of items; worker processes overlap file I/O + normalisation (or synthetic generation) with
     # the GPU work of the previous batch.  NOT pin_memory=True: the batch is repacked on the host into this module's own
     # pinned staging buffers anyway (PackedBatch.from_host), and reading a batch back out of the loader's pinned copy --
@@ -320,36 +343,26 @@ def evaluate_loader(net, loader: Iterable, corr: str = "tgt", dis_thresh: float 
     batches = torch.utils.data.DataLoader(torch.utils.data.Subset(dataset, mine), batch_size=batch_pairs, shuffle=False,
                                           collate_fn=collate_pairs, num_workers=num_workers, pin_memory=False,
                                           multiprocessing_context=ctx)
-    def collect(finish, n_done):
+    ids = [mine[b0:b0 + batch_pairs] for b0 in range(0, len(mine), batch_pairs)]  # the loader's batches, in its order
+
+    def enqueue(job, stream):  # (worker processes send a batch as three flat tensors, scream_amd/data.py)
+        return evaluate_items_async(net, unpack_batch(job[0]), job[1], corr, dis_thresh, icp, pred_hook=pred_hook, stream=stream)
+
+    def collect(job, finish):
         r = finish()
         rows.append(r)
         if verbose and rank == 0:
             print("\r%s  re: %.5f  te: %.5f  rmse: %.5f  rr: %.5f" % (
-                processbar(n_done, len(mine)), r[-1, sdist.COL_RE], r[-1, sdist.COL_TE], r[-1, sdist.COL_RMSE],
+                processbar(sum(len(b) for b in rows), len(mine)), r[-1, sdist.COL_RE], r[-1, sdist.COL_TE], r[-1, sdist.COL_RMSE],
                 float(np.concatenate(rows)[:, sdist.COL_SUCCESS].mean())), end="")
 
     # Batch i is enqueued before the host side of batch i-1 runs: the GPU never waits for the host.  Consecutive batches go to
-    # alternating HIP streams, each batch whole (one packed forward of all its pairs): several batches are then in flight
-    # out of phase, and the launch-bound end of one -- the ICP loop is ~60 tiny dependent launches -- runs beside the
-    # others' forwards instead of beside nothing (two lanes INSIDE a batch finish together and both sit in their ICP loops
-    # at the same time: 1 373 vs 1 570 pairs/s with / without ICP; results are the same either way, pairs never interact).
+    # alternating HIP streams (scream_amd/lanes.py: in_flight), each batch whole (one packed forward of all its pairs): several
+    # batches are then in flight out of phase, and the launch-bound end of one -- the ICP loop is ~60 tiny dependent launches --
+    # runs beside the others' forwards instead of beside nothing (two lanes INSIDE a batch finish together and both sit in their
+    # ICP loops at the same time: 1 373 vs 1 570 pairs/s with / without ICP; results are the same either way, pairs never interact).
     dev = next(net.parameters()).device if hasattr(net, "parameters") else None
-    # in_flight batches are enqueued before the oldest is collected, each on its own stream (a stream, its staging buffers and
-    # its workspace are reused only after the batch that last used them has been collected).
-    in_flight = max(2, int(in_flight))
-    streams = _lanes.lane_streams(dev, in_flight) if dev is not None and dev.type == "cuda" else [None] * in_flight
-    pending, k = [], 0
-    for items in batches:
-        items = unpack_batch(items)  # (worker processes send a batch as three flat tensors, scream_amd/data.py)
-        ids = mine[done:done + len(items)]
-        fin = evaluate_items_async(net, items, ids, corr, dis_thresh, icp, pred_hook=pred_hook, stream=streams[k % in_flight])
-        k += 1
-        done += len(ids)
-        pending.append((fin, done))
-        if len(pending) >= in_flight:
-            collect(*pending.pop(0))
-    for pd in pending:
-        collect(*pd)
+    _lanes.in_flight(dev, max(2, int(in_flight)), zip(batches, ids), enqueue, collect)
     local = np.concatenate(rows) if rows else np.zeros((0, sdist.ROW_WIDTH))
     allrows = sdist.all_gather_rows(local)
     out = aggregate_rows(allrows, re_static_method)

@@ -22,7 +22,7 @@ from . import dist as sdist
 from . import synthetic
 from .data import normalize_pair
 from . import lanes as _lanes
-from .evaluate import IN_FLIGHT, register_items_async
+from .evaluate import IN_FLIGHT, _strip_pair, register_items_async
 from .geometry import processbar
 
 SKIP_ITEMS = (124, 142)  # evaluate_kitti.py:32-34
@@ -57,14 +57,6 @@ class SyntheticKittiPairs(Dataset):
         return normalize_pair(*synthetic.make_kitti_pair(self.seed0 + i), "bbox")
 
 
-def _strip6(item):
-    src, tgt, rot, trans, s, c = item
-    if torch.is_tensor(src) and src.dim() == 3:
-        src, tgt, rot, trans, c = src[0], tgt[0], rot[0], trans[0], c[0]
-        s = s[0] if torch.is_tensor(s) or isinstance(s, (list, tuple)) else s
-    return src.float(), tgt.float(), rot.float(), trans.float(), (float(s.item()) if torch.is_tensor(s) else float(s)), c.float()
-
-
 @torch.no_grad()
 def evaluate(net, loader, dis_thresh: float = KITTI_DIS_THRESH, icp_thresh: float = KITTI_ICP_DIST, icp="gpu",
              icp_iters: int = KITTI_ICP_ITERS, batch_pairs: int = 8, skip: Sequence[int] = SKIP_ITEMS,
@@ -82,7 +74,13 @@ def evaluate(net, loader, dis_thresh: float = KITTI_DIS_THRESH, icp_thresh: floa
     mine = ids[rank::world]
     rows = []
 
-    def collect(fin, bid, n_done):
+    def enqueue(bid, stream):
+        its = [_strip_pair(*dataset[i]) for i in bid]
+        centers = [-(it[2].t() @ it[3]).reshape(3) for it in its]  # evaluate_kitti.py:39
+        return register_items_async(net, its, centers, bid, "tgt", dis_thresh, icp, icp_thresh, icp_iters, pred_hook=pred_hook,
+                                    stream=stream, backend=backend)
+
+    def collect(bid, fin):
         T, T_gt, re, te, loss = fin()
         for k, i in enumerate(bid):
             r = np.zeros(sdist.ROW_WIDTH)
@@ -90,24 +88,11 @@ def evaluate(net, loader, dis_thresh: float = KITTI_DIS_THRESH, icp_thresh: floa
             r[sdist.COL_RE], r[sdist.COL_TE], r[sdist.COL_LOSS] = re[k], te[k], loss[k]
             rows.append(r)
         if verbose and rank == 0:
-            print("\r%s  re: %.5f  te: %.5f" % (processbar(n_done, len(mine)), re[-1], te[-1]), end="")
+            print("\r%s  re: %.5f  te: %.5f" % (processbar(len(rows), len(mine)), re[-1], te[-1]), end="")
 
-    # like evaluate_loader (scream_amd/evaluate.py): in_flight batches enqueued, each whole on its own stream, collected in order
-    dev = next(net.parameters()).device
-    in_flight = max(1, int(in_flight))
-    streams = _lanes.lane_streams(dev, in_flight) if dev.type == "cuda" else [None] * in_flight
-    pending = []
-    for k, b0 in enumerate(range(0, len(mine), batch_pairs)):
-        bid = mine[b0:b0 + batch_pairs]
-        its = [_strip6(dataset[i]) for i in bid]
-        centers = [-(it[2].t() @ it[3]).reshape(3) for it in its]  # evaluate_kitti.py:39
-        fin = register_items_async(net, its, centers, bid, "tgt", dis_thresh, icp, icp_thresh, icp_iters, pred_hook=pred_hook,
-                                   stream=streams[k % in_flight], backend=backend)
-        pending.append((fin, bid, min(b0 + batch_pairs, len(mine))))
-        if len(pending) >= in_flight:
-            collect(*pending.pop(0))
-    for pd in pending:
-        collect(*pd)
+    # in_flight batches enqueued, each whole on its own stream, collected in order (scream_amd/lanes.py: in_flight)
+    _lanes.in_flight(next(net.parameters()).device, max(1, int(in_flight)),
+                     [mine[b0:b0 + batch_pairs] for b0 in range(0, len(mine), batch_pairs)], enqueue, collect)
     allrows = sdist.all_gather_rows(np.array(rows).reshape(-1, sdist.ROW_WIDTH))
     n = max(allrows.shape[0], 1)
     ok = allrows[:, sdist.COL_SUCCESS] > 0

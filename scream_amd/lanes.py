@@ -4,11 +4,12 @@ Pairs never interact, so nothing orders lane 0's kernels 
 are persistent grids of one block per CU; with 650 or 1302 output tiles a launch ends in a partial round during
 which most CUs idle, and every launch ends with a store-bound epilogue.  A second lane's kernels fill exactly those
 holes (measured: 37.7 -> 35.7 ms per 32-pair forward with two lanes, 35.4 with four).  Same kernels, same inputs per
-pair, same results bit for bit -- only the interleaving on the chip changes.
+pair, same results bit for bit -- only the interleaving on the chip changes.  ``in_flight`` uses the same streams the other
+way round: whole batches, each on its own stream, several enqueued at a time.
 """
 from __future__ import annotations
 
-from typing import Callable, List, Sequence, TypeVar
+from typing import Callable, Iterable, List, Optional, Sequence, TypeVar
 
 import torch
 
@@ -22,6 +23,22 @@ def lane_streams(device: torch.device, n: int) -> List[torch.cuda.Stream]:
     while len(pool) < n:
         pool.append(torch.cuda.Stream(device=device))
     return pool[:n]
+
+
+def in_flight(device: Optional[torch.device], n: int, jobs: Iterable, enqueue: Callable, collect: Callable) -> None:
+    """Keep n jobs enqueued: ``handle = enqueue(job, stream)`` for every job, job k on stream k % n of lane_streams(device, n)
+    (None when device is None or no HIP device), and ``collect(job, handle)`` oldest first as soon as n are pending; the rest
+    are collected at the end.  Slot k % n -- the stream and whatever the caller keys on it: its staging buffers, its forward
+    workspace -- is reused by job k only after job k - n, the job that last used it, was collected: collect() must have consumed
+    everything its job left queued on the stream or held of the slot's memory before it returns."""
+    streams = lane_streams(device, n) if device is not None and device.type == "cuda" else [None] * n
+    pending = []
+    for k, job in enumerate(jobs):
+        pending.append((job, enqueue(job, streams[k % n])))
+        if len(pending) >= n:
+            collect(*pending.pop(0))
+    for p in pending:
+        collect(*p)
 
 
 def split(n_items: int, lanes: int) -> List[range]:

@@ -441,6 +441,56 @@ def test_concurrent_lanes_do_not_change_results():
                 np.testing.assert_array_equal(a, b)
 
 
+def test_long_icp_schedule_continues_on_lane_streams(monkeypatch):
+    """A schedule longer than ops.ICP_ASYNC_ITERS whose batch ran as several lanes (stream=None, lanes >= 2): each lane's first
+    piece goes out on its own lane stream, and the rest is enqueued there when the batch is collected.  Same five arrays, bit for
+    bit, as the whole 30-iteration schedule in one call.  The continuation cannot be skipped: a pair stops at an evaluation
+    e >= 1 at the earliest, evaluation 1 happens in launch 2 (csrc/icp_p2p.hip, icp_pose_step: e = it - 1), and a first piece of
+    ICP_ASYNC_ITERS = 2 holds launches 0 and 1 -- the advance counter below keeps the test from passing vacuously all the same."""
+    from scream_amd.evaluate import _strip, register_items
+    from scream_amd.model import PointTransformer
+    net = PointTransformer(256, 2, 1)
+    net.load_state_dict(make_state_dict(4, 256, 2, 1))
+    net = net.to(DEV).eval()
+    ds = SyntheticPairs("3dmatch", 9, seed0=70)
+    items = [ds[i] for i in range(len(ds))]
+    its = [_strip(it) for it in items]
+    core = [(it[0], it[1], it[2], it[3], it[4], it[7]) for it in its]
+    centers = [it[3] for it in its]
+
+    def hook(batch, src_pred, ids):  # realistic correspondences, so that the ICP has work to do
+        out = src_pred.clone()
+        for k, i in enumerate(ids):
+            r0 = int(batch.cloud_row0_host[k])
+            out[r0:r0 + items[i][0].shape[0]] = _noisy_registered(items[i], i).to(DEV)
+        return out
+
+    def run(lanes):
+        return register_items(net, core, centers, list(range(9)), "tgt", 0.1, "gpu", icp_iters=30, pred_hook=hook, lanes=lanes)
+
+    assert ops.ICP_ASYNC_ITERS >= 30
+    ref = run(1)  # the whole schedule in one asynchronous call (ops.icp_p2p)
+    advances = {}  # id(run) -> (the run, kept alive so that ids stay distinct; its advance() calls)
+    advance = ops.IcpRun.advance
+
+    def counted(self, k):
+        advances.setdefault(id(self), [self, 0])[1] += 1
+        return advance(self, k)
+    monkeypatch.setattr(ops.IcpRun, "advance", counted)
+    old = ops.ICP_ASYNC_ITERS
+    ops.ICP_ASYNC_ITERS = 2
+    try:
+        for lanes in (1, 2, 3):
+            for rep in range(2):  # twice: the second pass reuses the lanes' streams and workspaces
+                advances.clear()
+                out = run(lanes)
+                assert len(advances) == lanes and all(n > 1 for _, n in advances.values()), (lanes, advances)
+                for a, b in zip(ref, out):
+                    np.testing.assert_array_equal(a, b)
+    finally:
+        ops.ICP_ASYNC_ITERS = old
+
+
 def test_open_gf_dem_evaluation_vs_oracle():
     """evaluate_open_gf.py:46-73 for DEMTransformer: batched forward + fused-search Chamfer + height errors against the
     oracle's per-sample restatement (dense N x M Chamfer, one sample per forward)."""

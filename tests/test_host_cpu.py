@@ -791,6 +791,39 @@ def test_evaluate_loader_keeps_in_flight_batches_enqueued_and_collects_in_order(
                 assert log.index(("enq", k)) < log.index(("fin", k - (n - 1)))
 
 
+@pytest.mark.parametrize("n", [1, 2, 3, 4])
+def test_in_flight_keeps_n_jobs_enqueued_and_reuses_a_slot_only_after_its_job_was_collected(n, monkeypatch):
+    """lanes.in_flight: every job collected exactly once, in job order; job k enqueued only after job k - n was collected, and
+    before job k - (n - 1) is, so n jobs really are pending; job k runs on stream k % n (None without a HIP device)."""
+    import types
+    from scream_amd import lanes
+    for count in (0, 1, n - 1, n, n + 1, 2 * n + 1):
+        log, streams = [], []
+
+        def enqueue(job, stream):
+            log.append(("enq", job))
+            streams.append(stream)
+            return "handle%d" % job
+
+        def collect(job, handle):
+            assert handle == "handle%d" % job
+            log.append(("fin", job))
+        lanes.in_flight(None, n, iter(range(count)), enqueue, collect)  # (an iterator: jobs may be produced lazily)
+        assert streams == [None] * count
+        assert [k for t, k in log if t == "fin"] == list(range(count))  # each exactly once, oldest first
+        for k in range(count):
+            if k >= n:
+                assert log.index(("fin", k - n)) < log.index(("enq", k))
+            if n - 1 <= k < count - 1:
+                assert log.index(("enq", k)) < log.index(("fin", k - (n - 1)))
+    sentinels = [object() for _ in range(n)]
+    dev = types.SimpleNamespace(type="cuda", index=0)
+    monkeypatch.setattr(lanes, "lane_streams", lambda device, m: sentinels[:m] if device is dev and m == n else None)
+    got = []
+    lanes.in_flight(dev, n, range(2 * n + 1), lambda job, stream: got.append(stream), lambda job, handle: None)
+    assert len(got) == 2 * n + 1 and all(got[k] is sentinels[k % n] for k in range(2 * n + 1))
+
+
 def test_bench_launches_its_own_ranks(tmp_path):
     """`python bench.py --gpus N` with no launcher around it spawns the N ranks itself (CPU-only parent), forwards rank
     0's single JSON line and propagates a failing rank's exit code (round-1 verdict: the driver's command form)."""
