@@ -73,6 +73,11 @@ class _Pack:
 
 
 class PointTransformer(nn.Module):
+    # What DEMTransformer overrides: the names of the self-layer lists, registered in this order (the first runs on the source
+    # cloud; a second one, when there is one, on the target cloud), and the renderer's views.
+    _stems = ("stem",)
+    _view = "muti"
+
     def __init__(self, d_model: int = 256, self_layer_num: int = 6, cross_layer_num: int = 6):
         super().__init__()
         if d_model != D_MODEL:
@@ -82,27 +87,29 @@ class PointTransformer(nn.Module):
         self.pre_norm = nn.LayerNorm(d_model)
         self.self_layer_num = self_layer_num
         self.cross_layer_num = cross_layer_num
-        self.stem = nn.ModuleList([_MHAParams(d_model) for _ in range(self_layer_num)])
+        for name in self._stems:
+            setattr(self, name, nn.ModuleList([_MHAParams(d_model) for _ in range(self_layer_num)]))
         self.cross = nn.ModuleList()
         for _ in range(cross_layer_num):
             self.cross.append(_MHAParams(d_model))
             self.cross.append(_CrossParams(d_model))
         self.coor_mlp = nn.Sequential(nn.Conv1d(d_model, d_model, 1), nn.ReLU(), nn.Conv1d(d_model, d_model, 1),
                                       nn.ReLU(), nn.Conv1d(d_model, 3, 1))
-        # models/pointnet.py:36: the depth renderer of get_imgs=True (training-time GAN loss); no parameters, no buffers
-        self.generator = RegistrationRender(rho=24, w=64)
+        # models/pointnet.py:36,133: the depth renderer of get_imgs=True (training-time GAN loss); no parameters, no buffers
+        self.generator = RegistrationRender(rho=24, w=64, view=self._view)
         self._packs = {}  # gemm backend -> _Pack: the weights in that backend's kernel layout (built on first use)
         self._ws = None
 
     # ------------------------------------------------------------------ weights -> kernel layout
     def _layer_modules(self) -> List[_MHAParams]:
-        mods = list(self.stem)
+        mods = list(getattr(self, self._stems[0]))
         for i, m in enumerate(self.cross):
             mods.append(m if i % 2 == 0 else m.layer)
         return mods
 
     def _stem_tgt_modules(self) -> Optional[List[_MHAParams]]:
-        return None  # PointTransformer: one stem for both clouds
+        """None: one stem serves both clouds (PointTransformer)."""
+        return list(getattr(self, self._stems[1])) if len(self._stems) > 1 else None
 
     # GEMM path of the forward.  "h2" (default since round 3): fp16 matrix cores, operands split in two fp16 planes with
     # power-of-two scales derived from the weights (scream_amd/scales.py), three products -- fp32-level accuracy at half the
@@ -367,40 +374,27 @@ class PointTransformer(nn.Module):
     def forward(self, src, tgt, src_center=None, s=1, get_imgs=False, get_transform=False, filter=None):
         """models/pointnet.py:38-91.  Inference (under no_grad, as the reference evaluates) unless train() was called and
         grad mode is on: then src_ carries a grad_fn (train_3d_match.py's loop)."""
-        if self._trains():
-            return self._forward_train(src, tgt, src_center, s, get_imgs, get_transform, filter)
-        with torch.no_grad():
-            return self._forward_infer(src, tgt, src_center, s, get_imgs, get_transform, filter)
+        with torch.set_grad_enabled(self._trains()):  # inference: everything below under no_grad
+            src_ = self._forward_pair(src, tgt, None if src_center is None else src_center.reshape(3))
+            # pointnet.py:62-65: the predicted source (normalised frame) and the raw target; differentiable in src_ only
+            imgs = self.generator(src_[0], tgt[0].detach()) if get_imgs else None
+            transform = None
+            if get_transform:  # pointnet.py:66-74: NN against `filter` at 0.075, Kabsch in the normalised frame; never in the graph
+                from .geometry import register_from_prediction
+                with torch.no_grad():
+                    ref = tgt[0] if filter is None else filter[0]
+                    transform = register_from_prediction(src[0], src_[0].detach(), ref, float(s), 0.075)
+        return src_, imgs, transform
 
-    def _forward_train(self, src, tgt, src_center, s, get_imgs, get_transform, filter):
+    def _forward_pair(self, src, tgt, center):
+        """src [1,N,3], tgt [1,M,3] -> the prediction [1,N,3] of the one-pair batch.  The inputs are data (detached).  In training
+        the prediction is a view of forward_packed_train's and carries its grad_fn; in inference it is a clone of the N rows."""
         assert src.shape[0] == 1, "batch size must 1"
         assert tgt.shape[0] == 1, "batch size must 1"
-        center = None if src_center is None else src_center.reshape(3)
         batch = PackedBatch.from_pairs([src[0].detach()], [tgt[0].detach()], [None if center is None else center.detach()])
-        src_ = self.forward_packed_train(batch)[: src.shape[1]].unsqueeze(0)
-        # pointnet.py:62-65: the predicted source (normalised frame) and the raw target; differentiable in src_
-        imgs = self.generator(src_[0], tgt[0].detach()) if get_imgs else None
-        transform = None
-        if get_transform:
-            from .geometry import register_from_prediction
-            with torch.no_grad():
-                ref = tgt[0] if filter is None else filter[0]
-                transform = register_from_prediction(src[0], src_[0].detach(), ref, float(s), 0.075)
-        return src_, imgs, transform
-
-    def _forward_infer(self, src, tgt, src_center=None, s=1, get_imgs=False, get_transform=False, filter=None):
-        assert src.shape[0] == 1, "batch size must 1"
-        assert tgt.shape[0] == 1, "batch size must 1"
-        center = None if src_center is None else src_center.reshape(3)
-        batch = PackedBatch.from_pairs([src[0]], [tgt[0]], [center])
-        src_ = self.forward_packed(batch)[: src.shape[1]].unsqueeze(0).clone()
-        imgs = self.generator(src_[0], tgt[0]) if get_imgs else None  # pointnet.py:62-65
-        transform = None
-        if get_transform:  # pointnet.py:66-74: NN against `filter` at 0.075, Kabsch in the normalised frame
-            from .geometry import register_from_prediction
-            ref = tgt[0] if filter is None else filter[0]
-            transform = register_from_prediction(src[0], src_[0], ref, float(s), 0.075)
-        return src_, imgs, transform
+        if self._trains():
+            return self.forward_packed_train(batch)[: src.shape[1]].unsqueeze(0)
+        return self.forward_packed(batch)[: src.shape[1]].unsqueeze(0).clone()
 
     def loss(self, src_pred, src_pcd, rot_gt, trans_gt):
         """models/pointnet.py:93-99 (L1 point loss; metric bookkeeping, not a hot-path kernel)."""
@@ -419,61 +413,18 @@ class DEMTransformer(PointTransformer):
     DSM cloud (``stem_dsm``) and the coarse DEM cloud (``stem_dem``), raw coordinates into the embedding for both
     clouds, no correspondence/Kabsch stage.  forward(dsm, dem_coarse, get_imgs=False) -> (dem_, imgs)."""
 
-    def __init__(self, d_model: int = 256, self_layer_num: int = 6, cross_layer_num: int = 6):
-        nn.Module.__init__(self)
-        if d_model != D_MODEL:
-            raise NotImplementedError("the gfx950 kernels are built for d_model=256")
-        self.embedding = nn.Conv1d(3, d_model, kernel_size=1, stride=1)
-        self.pre_norm = nn.LayerNorm(d_model)
-        self.self_layer_num = self_layer_num
-        self.cross_layer_num = cross_layer_num
-        self.stem_dsm = nn.ModuleList([_MHAParams(d_model) for _ in range(self_layer_num)])
-        self.stem_dem = nn.ModuleList([_MHAParams(d_model) for _ in range(self_layer_num)])
-        self.cross = nn.ModuleList()
-        for _ in range(cross_layer_num):
-            self.cross.append(_MHAParams(d_model))
-            self.cross.append(_CrossParams(d_model))
-        self.coor_mlp = nn.Sequential(nn.Conv1d(d_model, d_model, 1), nn.ReLU(), nn.Conv1d(d_model, d_model, 1),
-                                      nn.ReLU(), nn.Conv1d(d_model, 3, 1))
-        self.generator = RegistrationRender(rho=24, w=64, view="single")  # models/pointnet.py:133
-        self._packs = {}
-        self._ws = None
-
-    def _layer_modules(self) -> List[_MHAParams]:
-        mods = list(self.stem_dsm)
-        for i, m in enumerate(self.cross):
-            mods.append(m if i % 2 == 0 else m.layer)
-        return mods
-
-    def _stem_tgt_modules(self) -> Optional[List[_MHAParams]]:
-        return list(self.stem_dem)
+    _stems = ("stem_dsm", "stem_dem")
+    _view = "single"  # models/pointnet.py:133
 
     def forward(self, dsm, dem_coarse, get_imgs=False):
         """models/pointnet.py:134-160.  Inference unless train() was called and grad mode is on: then dem_ (and imgs) carry
         a grad_fn (train_open_gf.py's loop).  Batched training: forward_packed_train(PackedBatch.from_pairs(dsms, dem_coarses,
         [zeros(3)] * B))."""
-        if self._trains():
-            return self._forward_train(dsm, dem_coarse, get_imgs)
-        with torch.no_grad():
-            return self._forward_infer(dsm, dem_coarse, get_imgs)
-
-    def _forward_train(self, dsm, dem_coarse, get_imgs=False):
-        assert dsm.shape[0] == 1, "batch size must 1"
-        assert dem_coarse.shape[0] == 1, "batch size must 1"
-        zero = torch.zeros(3, device=dsm.device)  # both clouds embed their raw coordinates (pointnet.py:138-139)
-        batch = PackedBatch.from_pairs([dsm[0].detach()], [dem_coarse[0].detach()], [zero])
-        dem_ = self.forward_packed_train(batch)[: dsm.shape[1]].unsqueeze(0)
-        # pointnet.py:156-159: differentiable in dem_; the coarse DEM is data
-        imgs = self.generator(dem_[0], dem_coarse[0].detach()) if get_imgs else None
-        return dem_, imgs
-
-    def _forward_infer(self, dsm, dem_coarse, get_imgs=False):
-        assert dsm.shape[0] == 1, "batch size must 1"
-        assert dem_coarse.shape[0] == 1, "batch size must 1"
-        zero = torch.zeros(3, device=dsm.device)  # both clouds embed their raw coordinates (pointnet.py:138-139)
-        batch = PackedBatch.from_pairs([dsm[0]], [dem_coarse[0]], [zero])
-        dem_ = self.forward_packed(batch)[: dsm.shape[1]].unsqueeze(0).clone()
-        imgs = self.generator(dem_[0], dem_coarse[0]) if get_imgs else None  # pointnet.py:156-159
+        with torch.set_grad_enabled(self._trains()):  # inference: everything below under no_grad
+            zero = torch.zeros(3, device=dsm.device)  # both clouds embed their raw coordinates (pointnet.py:138-139)
+            dem_ = self._forward_pair(dsm, dem_coarse, zero)
+            # pointnet.py:156-159: differentiable in dem_; the coarse DEM is data
+            imgs = self.generator(dem_[0], dem_coarse[0].detach()) if get_imgs else None
         return dem_, imgs
 
     def forward_batch(self, dsms, dems, centers=None):

@@ -57,27 +57,28 @@ def view_eulers(view: str = "muti"):
     return [np.array([0, 0, 0])]
 
 
-class _RenderFn(torch.autograd.Function):
-    """imgs [V,2,w,w] of one pair; the backward routes each source-image pixel's gradient to its argmax point."""
+class _RenderPackedFn(torch.autograd.Function):
+    """imgs [B*V,2,w,w] of B packed pairs; the backward is the packed scream_render_depth_bwd, which routes each source-image
+    pixel's gradient to its argmax point."""
 
     @staticmethod
-    def forward(ctx, src_pred, tgt, rot, meta, w, rho):
-        src = src_pred.detach().to(torch.float32).contiguous()
+    def forward(ctx, src, s_row0, s_len, tgt, t_row0, t_len, max_s_len, max_t_len, rot, w, rho):
+        src = src.detach().to(torch.float32).contiguous()
         tgt = tgt.detach().to(torch.float32).contiguous()
-        n, m = src.shape[0], tgt.shape[0]
-        ws = ops.render_workspace(1, rot.shape[0], w, n, src.device)
-        imgs, argmax = ops.render_depth(src, meta[0:1], meta[1:2], tgt, meta[2:3], meta[3:4], n, m, rot, w, rho, ws)
-        ctx.save_for_backward(src, rot, meta, argmax, ws)
-        ctx.w, ctx.rho = w, rho
-        ctx.mark_non_differentiable(argmax)
-        return imgs[0]
+        B, V = s_row0.shape[0], rot.shape[0]
+        ws = ops.render_workspace(B, V, w, src.shape[0], src.device)
+        imgs, argmax = ops.render_depth(src, s_row0, s_len, tgt, t_row0, t_len, max_s_len, max_t_len, rot, w, rho, ws)
+        ctx.save_for_backward(src, s_row0, s_len, rot, argmax, ws)
+        ctx.geo = (B, V, int(max_s_len), int(w), float(rho))
+        return imgs.view(B * V, 2, w, w)
 
     @staticmethod
     def backward(ctx, dimgs):
-        src, rot, meta, argmax, ws = ctx.saved_tensors
-        dsrc = ops.render_depth_bwd(dimgs.to(torch.float32).contiguous().unsqueeze(0), argmax, src, meta[0:1], meta[1:2],
-                                    src.shape[0], rot, ctx.w, ctx.rho, ws)
-        return dsrc, None, None, None, None, None
+        src, s_row0, s_len, rot, argmax, ws = ctx.saved_tensors
+        B, V, max_s_len, w, rho = ctx.geo
+        dsrc = ops.render_depth_bwd(dimgs.to(torch.float32).contiguous().view(B, V, 2, w, w), argmax, src, s_row0, s_len, max_s_len, rot,
+                                    w, rho, ws)
+        return (dsrc,) + (None,) * 10
 
 
 class RegistrationRender(nn.Module):
@@ -127,9 +128,10 @@ class RegistrationRender(nn.Module):
                                       % (src_pred.device, tgt_pcd.device))
         if torch.is_grad_enabled() and tgt_pcd.requires_grad:
             raise ValueError("RegistrationRender differentiates src_pred only: pass tgt_pcd detached (no caller needs its gradient)")
-        dev = src_pred.device
-        return _RenderFn.apply(src_pred, tgt_pcd, self.view_matrices(dev), self._meta(src_pred.shape[0], tgt_pcd.shape[0], dev),
-                               self.w, float(self.rho))
+        n, m, dev = src_pred.shape[0], tgt_pcd.shape[0], src_pred.device
+        meta = self._meta(n, m, dev)  # the one pair as a packed batch of one: B * V = V images
+        return _RenderPackedFn.apply(src_pred, meta[0:1], meta[1:2], tgt_pcd, meta[2:3], meta[3:4], n, m, self.view_matrices(dev),
+                                     self.w, float(self.rho))
 
 
 def render_packed(src: torch.Tensor, s_row0, s_len, tgt: torch.Tensor, t_row0, t_len, max_s_len: int, max_t_len: int,
@@ -137,29 +139,6 @@ def render_packed(src: torch.Tensor, s_row0, s_len, tgt: torch.Tensor, t_row0, t
     """B pairs in one launch set (no autograd): packed rows as ops.render_depth takes them -> imgs [B, V, 2, w, w]."""
     rot = torch.stack([rotation_matrix(e) for e in eulers]).to(src.device)
     return ops.render_depth(src, s_row0, s_len, tgt, t_row0, t_len, max_s_len, max_t_len, rot, w, rho)[0]
-
-
-class _RenderPackedFn(torch.autograd.Function):
-    """imgs [B*V,2,w,w] of B packed pairs; the backward is the packed scream_render_depth_bwd."""
-
-    @staticmethod
-    def forward(ctx, src, s_row0, s_len, tgt, t_row0, t_len, max_s_len, max_t_len, rot, w, rho):
-        src = src.detach().to(torch.float32).contiguous()
-        tgt = tgt.detach().to(torch.float32).contiguous()
-        B, V = s_row0.shape[0], rot.shape[0]
-        ws = ops.render_workspace(B, V, w, src.shape[0], src.device)
-        imgs, argmax = ops.render_depth(src, s_row0, s_len, tgt, t_row0, t_len, max_s_len, max_t_len, rot, w, rho, ws)
-        ctx.save_for_backward(src, s_row0, s_len, rot, argmax, ws)
-        ctx.geo = (B, V, int(max_s_len), int(w), float(rho))
-        return imgs.view(B * V, 2, w, w)
-
-    @staticmethod
-    def backward(ctx, dimgs):
-        src, s_row0, s_len, rot, argmax, ws = ctx.saved_tensors
-        B, V, max_s_len, w, rho = ctx.geo
-        dsrc = ops.render_depth_bwd(dimgs.to(torch.float32).contiguous().view(B, V, 2, w, w), argmax, src, s_row0, s_len, max_s_len, rot,
-                                    w, rho, ws)
-        return (dsrc,) + (None,) * 10
 
 
 def render_packed_train(src: torch.Tensor, s_row0, s_len, tgt: torch.Tensor, t_row0, t_len, max_s_len: int, max_t_len: int,

@@ -2,6 +2,7 @@
 import functools
 import importlib
 import os
+import re
 
 import numpy as np
 import pytest
@@ -72,3 +73,19 @@ def test_drivers_keep_the_reference_surface_and_run_nothing_at_import(name, path
         drv.lr_g = lr
     with pytest.raises(SystemExit):
         drv.main(["--train-backend", "fp8"])
+
+
+def test_the_training_entry_points_are_written_once():
+    """The loaders, the command line, the optimiser and update_lr's loop stand in scream_amd/fit.py, not in the three drivers;
+    render.py has one autograd Function for its one kernel pair; model.py has one constructor body and no forward body per
+    mode."""
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = lambda *parts: open(os.path.join(repo, *parts)).read()
+    for drv in ("train_3d_match.py", "train_kitti.py", "train_open_gf.py"):
+        for needle in ("DataLoader(", "ArgumentParser(", "FusedAdam(", "param_groups"):
+            assert needle not in text(drv), (drv, needle)
+    render = text("scream_amd", "render.py")
+    assert len(re.findall(r"^class \w+\(torch\.autograd\.Function\):", render, re.M)) == 1 and render.count("autograd.Function") == 1
+    model = text("scream_amd", "model.py")
+    assert model.count("nn.Conv1d(3, d_model") == 1
+    assert not re.search(r"_forward_train|_forward_infer", model)

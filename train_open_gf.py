@@ -10,16 +10,11 @@ evaluate_open_gf.py's.  ``--gan`` turns on use_GAN: the adversarial loss of
 scream_amd/gan.py (a 2-channel HIP discriminator, FusedAdam at lr_d with betas (0.5, 0.999)) through fit(gan=...); the
 discriminator is saved to discriminator_save_path whenever the generator is.
 """
-import argparse
 import os
+import sys
 
-import torch
-from torch.utils import data
-
-from scream_amd import FusedAdam
 from scream_amd.evaluate_open_gf import OpenGFFiles, SyntheticDEM
-from scream_amd.fit import dem_preparer, dem_real_rows, fit, gan_training, val_loss
-from scream_amd.model import PointTransformer
+from scream_amd.fit import Driver, dem_preparer, dem_real_rows
 
 use_GAN = False
 generator_save_path = "params/dem-generator.pth"
@@ -33,15 +28,6 @@ lr_update_epoch = 15
 epochs = 45
 
 
-def update_lr(optimizer, gamma=0.5):
-    """train_open_gf.py:44-49."""
-    global lr_g
-    lr_g = max(lr_g * gamma, min_learning_rate)
-    for param_group in optimizer.param_groups:
-        param_group['lr'] = lr_g
-    print("lr update finished  cur lr: %.5f" % lr_g)
-
-
 def _count(root):
     n = 0
     while os.path.exists(os.path.join(root, "%d.npy" % (n + 1))):
@@ -49,56 +35,30 @@ def _count(root):
     return n
 
 
-def _loaders(synthetic, batch):
+def _datasets(synthetic):
     if synthetic:
-        train_set, val_set = SyntheticDEM(synthetic, 0), SyntheticDEM(max(synthetic // 4, 1), 10 ** 6)
-    else:
-        for d in ("OpenGF_train", "OpenGF_val"):
-            if _count(d) == 0:
-                raise FileNotFoundError("%s/ is not populated (process_open_gf.py writes it); pass --synthetic N to train on seeded "
-                                        "synthetic terrain" % d)
-        train_set, val_set = OpenGFFiles("OpenGF_train", _count("OpenGF_train")), OpenGFFiles("OpenGF_val", _count("OpenGF_val"))
-    return (data.DataLoader(train_set, batch_size=batch, shuffle=True, collate_fn=list),
-            data.DataLoader(val_set, batch_size=batch, shuffle=False, collate_fn=list))
+        return SyntheticDEM(synthetic, 0), SyntheticDEM(max(synthetic // 4, 1), 10 ** 6)
+    for d in ("OpenGF_train", "OpenGF_val"):
+        if _count(d) == 0:
+            raise FileNotFoundError("%s/ is not populated (process_open_gf.py writes it); pass --synthetic N to train on seeded "
+                                    "synthetic terrain" % d)
+    return OpenGFFiles("OpenGF_train", _count("OpenGF_train")), OpenGFFiles("OpenGF_val", _count("OpenGF_val"))
 
 
-def evaluate(net, val_loader, prepare_val):
-    """The validation loss (train_open_gf.py:52-76)."""
-    return val_loss(net, val_loader, prepare_val)[0]
+def _preparers(device):
+    return (dem_preparer(device),) * 2
 
 
-def _gan(device):
-    """What use_GAN adds: this driver's lr_d, ground-truth rows and discriminator_save_path."""
-    return gan_training(device, dem_real_rows, lr_d=lr_d, save_path=discriminator_save_path)
+_driver = Driver(sys.modules[__name__], dem_real_rows, "samples per step (the reference trains at 1)")
+update_lr, _gan, main = _driver.update_lr, _driver.gan, _driver.main
+evaluate = _driver.evaluate  # the validation loss (train_open_gf.py:52-76)
 
 
 def train(synthetic=0, batch=1, train_backend=None, layers=(6, 6), n_epochs=None, save_path=None, device=None, log=print, gan=None):
     """train_open_gf.py:79-146.  Returns fit()'s history."""
     from models.pointnet import DEMTransformer
-    device = torch.device(device if device is not None else "cuda:0")
-    net = DEMTransformer(d_model=256, self_layer_num=layers[0], cross_layer_num=layers[1])
-    if train_backend is not None:
-        net.train_backend = train_backend
-    net.to(device)
-    optimizer_G = FusedAdam(params=net.parameters(), lr=lr_g)
-    train_loader, val_loader = _loaders(synthetic, batch)
-    prepare = dem_preparer(device)
-    return fit(net, optimizer_G, train_loader, val_loader, prepare, prepare, epochs if n_epochs is None else n_epochs,
-               save_path or generator_save_path, gamma=learning_rate_decay_gamma, every=lr_update_epoch, floor=min_learning_rate, log=log,
-               gan=_gan(device) if (use_GAN if gan is None else gan) else None)
-
-
-def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batch", type=int, default=1, help="samples per step (the reference trains at 1)")
-    ap.add_argument("--synthetic", type=int, default=0)
-    ap.add_argument("--train-backend", choices=PointTransformer.TRAIN_BACKENDS, default=None)
-    ap.add_argument("--epochs", type=int, default=epochs)
-    ap.add_argument("--gan", action="store_true", help="train with the adversarial loss (use_GAN)")
-    a = ap.parse_args(argv)
-    global use_GAN
-    use_GAN = use_GAN or a.gan
-    train(a.synthetic, a.batch, a.train_backend, n_epochs=a.epochs)
+    return _driver.train(DEMTransformer, _datasets, _preparers, synthetic, batch, train_backend, layers, n_epochs, save_path, device,
+                         log, gan=gan)
 
 
 if __name__ == "__main__":
