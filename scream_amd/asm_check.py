@@ -9,9 +9,11 @@ program order with the in-order model of the vector-memory queue (loads, LDS-DMA
 outstanding.  Second check (check_scalar_base_hazard): the wait states hipcc does not insert in front of an asm memory
 instruction whose scalar base was just written by a VALU instruction.  Third and fourth: the data registers of a wide asm
 store, and asm vector instructions that read a matrix-instruction result (check_store_data_hazard, check_mfma_asm_read_hazard).
+gate() is what scream_amd/build.py refuses a library with: these four on every kernel, and no scratch for the kernels it names.
 
-    python tools/asm_inflight_check.py file.s [kernel-name-substring]
+    python -m scream_amd.asm_check file.s [kernel-name-substring]
 """
+import os
 import re
 import sys
 
@@ -225,66 +227,86 @@ def kernels(path):
         yield nm, lines[i:end]
 
 
+
+
+def private_segments(path):
+    """kernel name -> .amdhsa_private_segment_fixed_size (bytes of scratch per lane) from the kernel descriptors of the file"""
+    out, name = {}, None
+    for l in open(path):
+        w = l.split()
+        if w[:1] == [".amdhsa_kernel"]:
+            name = w[1]
+        elif w[:1] == [".amdhsa_private_segment_fixed_size"]:
+            out[name] = int(w[1])
+    return out
+
+
+def findings(name, body):
+    """The check list: every violation of the four detectors in one kernel, one worded line each (gate() refuses with the first,
+    main() prints them)."""
+    out = ["touches a register whose asm load is still in flight: %s   <- pending %s" % (line, regs) for n, line, regs in check_kernel(name, body)]
+    out += ["reads a matrix-instruction result with an asm vector instruction %d wait states behind it, fewer than 20 (%s ; %s)"
+            % (ws, mf, t) for i, t, mf, ws in check_mfma_asm_read_hazard(name, body)]
+    out += ["uses a scalar base %d wait states after a VALU write of it, fewer than 5 (%s -> %s)" % (ws, tt, t)
+            for i, t, tt, ws in check_scalar_base_hazard(name, body)]
+    out += ["overwrites the data of a wide store %d wait states behind it, fewer than 2 (%s ; %s)" % (ws, t, tt)
+            for i, t, tt, ws in check_store_data_hazard(name, body)]
+    return out
+
+
+def gate(asm, asm_loads, no_scratch=(), want=""):
+    """What a build must pass before it may run, on the assembly of the very object that will run (build.assembly).  asm_loads: the file
+    requests operands with inline asm and waits for them with hand-counted s_waitcnt vmcnt(N) -- whether hipcc's register allocation
+    respects that is a property of the generated code, so the four detectors run on every kernel whose mangled name contains `want`.
+    no_scratch: name fragments; every kernel of the file whose name contains one must have a private segment of 0 bytes, and a fragment
+    that matches no kernel is refused (a renamed kernel must not pass unseen).  Raises RuntimeError naming file, kernel and instruction;
+    returns the number of kernels the detectors saw."""
+    n = 0
+    for name, body in kernels(asm) if asm_loads else ():
+        if want not in name:
+            continue
+        n += 1
+        bad = findings(name, body)
+        if bad:
+            raise RuntimeError("%s: %s %s (%d findings in this kernel; this hipcc allocates registers differently from the one the "
+                               "kernels were written with)" % (asm, name, bad[0], len(bad)))
+    sizes = private_segments(asm)
+    for frag in no_scratch:
+        named = [k for k in sizes if frag in k]
+        if not named:
+            raise RuntimeError("%s: no kernel named *%s* in the generated assembly" % (asm, frag))
+        for k in named:
+            if sizes[k]:
+                raise RuntimeError("%s: %s uses %d bytes of scratch per lane (this hipcc allocates registers differently from the one "
+                                   "the kernel was written with)" % (asm, k, sizes[k]))
+    return n
+
+
 def verify_source(src, flags, out_s, want=""):
-    """Compile `src` to assembly with `flags` (the flags of the object that will run) and apply all three checks to every kernel
-    whose mangled name contains `want`; raises RuntimeError naming the first violation.  For any build other than the one
-    scream_amd/build.py verifies itself: whatever removes or adds memory operations changes what a hand-counted vmcnt(N) leaves
+    """Compile `src` to assembly with `flags` (the per-file flags of the object that will run) and put it through gate() with the
+    build's table entry for that file; returns the number of kernels whose mangled name contains `want`.  For any build other than the
+    one scream_amd/build.py verifies itself: whatever removes or adds memory operations changes what a hand-counted vmcnt(N) leaves
     in flight (round 2: a "no weight DMA" tuning variant of the layer tail -- since removed -- was launched with its ring waits
     still counting twelve pieces that no longer existed; the row operands were consumed while pending, their registers recycled
     as per-lane 64-bit addresses, the loads landed in them, and the next access left the aperture --
     HSA_STATUS_ERROR_MEMORY_APERTURE_VIOLATION)."""
-    import subprocess
-    r = subprocess.run(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only", *flags, src, "-o", out_s],
-                       capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("hipcc -S failed for %s:\n%s" % (src, r.stderr))
-    n = 0
-    for nm, body in kernels(out_s):
-        if want not in nm:
-            continue
-        n += 1
-        bad, hz, sd = check_kernel(nm, body), check_scalar_base_hazard(nm, body), check_store_data_hazard(nm, body)
-        mh = check_mfma_asm_read_hazard(nm, body)
-        if mh:
-            raise RuntimeError("%s %s: %s reads a matrix-instruction result with an asm vector instruction %d wait states behind it (%s ; %s)" % (src, flags, nm, mh[0][3], mh[0][2], mh[0][1]))
-        if bad:
-            raise RuntimeError("%s %s: %s touches a register whose asm load is still in flight (%d places, first: %s)" % (src, flags, nm, len(bad), bad[0][1]))
-        if hz:
-            raise RuntimeError("%s %s: %s uses a scalar base %d wait states after a VALU write of it (%s -> %s)" % (src, flags, nm, hz[0][3], hz[0][2], hz[0][1]))
-        if sd:
-            raise RuntimeError("%s %s: %s overwrites the data of a wide store %d wait states behind it (%s ; %s)" % (src, flags, nm, sd[0][3], sd[0][1], sd[0][2]))
-    return n
+    from . import build
+    asm_loads, no_scratch = build.GATE.get(os.path.basename(src), (True, ()))
+    return gate(build.assembly(src, flags, out_s), asm_loads, no_scratch, want)
 
 
 def main():
-    path = sys.argv[1]
     want = sys.argv[2] if len(sys.argv) > 2 else ""
     total = 0
-    for nm, body in kernels(path):
+    for nm, body in kernels(sys.argv[1]):
         if want not in nm:
             continue
-        bad = check_kernel(nm, body)
+        bad = findings(nm, body)
         n_asm = sum(1 for l in body if re.match(r"\s*global_load_dwordx4 [va]", l))
         print("%s: %d register loads, %d violations" % (nm[:70], n_asm, len(bad)))
-        for n, line, regs in bad[:12]:
-            print("   +%d  %s   <- pending v%s" % (n, line, regs))
+        for text in bad[:12]:
+            print("   " + text)
         total += len(bad)
-        mh = check_mfma_asm_read_hazard(nm, body)
-        if mh:
-            print("   %d asm reads of a matrix-instruction result fewer than 20 wait states behind it, first: %s ; %s (%d)" % (len(mh), mh[0][2], mh[0][1], mh[0][3]))
-            total += len(mh)
-        hz = check_scalar_base_hazard(nm, body)
-        if hz:
-            print("   %d scalar-base hazards (VALU writes an SGPR < 5 wait states before a memory instruction uses it):" % len(hz))
-            for i, t, tt, ws in hz[:6]:
-                print("      %s  ->  %s   (%d wait states)" % (tt, t, ws))
-        total += len(hz)
-        sd = check_store_data_hazard(nm, body)
-        if sd:
-            print("   %d store-data hazards (VALU overwrites a wide store's data register < 2 wait states behind it):" % len(sd))
-            for i, t, tt, ws in sd[:6]:
-                print("      %s  ;  %s   (%d wait states)" % (t, tt, ws))
-        total += len(sd)
     return 1 if total else 0
 
 

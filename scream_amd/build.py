@@ -8,9 +8,12 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
+from . import asm_check
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libscream_hip.so")
+OBJDIR = os.path.join(HERE, "build")
 ARCH = "gfx950"
 
 # parity-critical files keep every fp32 operation individually rounded (see the file headers)
@@ -45,15 +48,24 @@ SOURCES = {
     # the discriminator's BatchNorm and loss steps are individually rounded operations restated by tests/gan_ref.py
     "gan.hip": ["-ffp-contract=off"],
 }
-ASM_LOADS = ("gemm_split.hip", "tail_split.hip", "proj_ring.hip")  # verified after code generation, see verify_one
-# kernels that must not touch scratch at all: a spill inside a ring stage costs a round trip per stage, and hipcc orders a scratch
-# reload against the LDS-DMA in flight with vmcnt(0) -- the ring would drain once per stage (the layer tail's history)
-NO_SCRATCH = {"proj_ring.hip": ("proj_ring_kernel",), "tail_split.hip": ("tail_kernelINS_7SplitH2", "tail_kernelINS_7SplitH1")}
-# kernels outside ASM_LOADS that must not touch scratch either: the raw-scan ICP search keeps its eight stepped binary searches
-# and its best candidate in registers (a spill would sit inside the dependent-load chain that bounds it)
-NO_SCRATCH_PLAIN = {"icp_raw.hip": ("raw_search_kernel", "raw_nn_kernel"),
-                    # the bf16 training GEMMs hold a 32 x 256 accumulator tile and both operands' next k-tile in registers
-                    "gemm_bf16.hip": ("gemm_bf16_kernel", "wgrad_split_partial_kernel")}
+# The gate: what asm_check.gate() must pass on a file's generated code before the library is linked, as (asm loads, no scratch).
+# asm loads: the file requests operands with inline asm and waits for them with hand-counted s_waitcnt vmcnt(N); whether hipcc's
+# register allocation respects that is a property of the generated code, not of the source, so the build proves it on the very code
+# it ships (same flags, assembly instead of an object) and FAILS if any instruction touches a register whose load is outstanding.
+# no scratch: kernels (name fragments) that must not touch scratch at all.
+GATE = {
+    "gemm_split.hip": (True, ()),
+    # a spill inside a ring stage costs a round trip per stage, and hipcc orders a scratch reload against the LDS-DMA in flight with
+    # vmcnt(0) -- the ring would drain once per stage (the layer tail's history)
+    "tail_split.hip": (True, ("tail_kernelINS_7SplitH2", "tail_kernelINS_7SplitH1")),
+    "proj_ring.hip": (True, ("proj_ring_kernel",)),
+    # the raw-scan ICP search keeps its eight stepped binary searches and its best candidate in registers (a spill would sit inside
+    # the dependent-load chain that bounds it)
+    "icp_raw.hip": (False, ("raw_search_kernel", "raw_nn_kernel")),
+    # the bf16 training GEMMs hold a 32 x 256 accumulator tile and both operands' next k-tile in registers
+    "gemm_bf16.hip": (False, ("gemm_bf16_kernel", "wgrad_split_partial_kernel")),
+}
+COMMON = ["-O3", "-std=c++17", "--offload-arch=" + ARCH, "-fPIC", "-Wall", "-Wno-unused-function"]
 
 
 def _hipcc() -> str:
@@ -63,109 +75,59 @@ def _hipcc() -> str:
     return exe
 
 
-def _stale() -> bool:
-    if not os.path.exists(LIB):
+def _stale(target: str) -> bool:
+    if not os.path.exists(target):
         return True
-    t = os.path.getmtime(LIB)
+    t = os.path.getmtime(target)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "scream_hip.h"), __file__]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force: bool = False, verbose: bool = False, out: str = None) -> str:
-    """out: write the library there instead of scream_amd/libscream_hip.so (experiment builds loaded with SCREAM_LIB=)."""
-    global LIB
-    if out:
-        LIB, force = out, True
-    if not force and not _stale():
-        return LIB
-    hipcc = _hipcc()
-    objdir = os.path.join(HERE, "build")
-    os.makedirs(objdir, exist_ok=True)
-    common = [hipcc, "-O3", "-std=c++17", "--offload-arch=" + ARCH, "-fPIC", "-Wall", "-Wno-unused-function"]
-
-    def compile_one(item):
-        src, extra = item
-        obj = os.path.join(objdir, src.replace(".hip", ".o"))
-        cmd = common + extra + ["-c", os.path.join(CSRC, src), "-o", obj]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("hipcc failed for %s:\n%s\n%s" % (src, " ".join(cmd), r.stderr))
-        if verbose and r.stderr.strip():
-            print(r.stderr, file=sys.stderr)
-        return obj
-
-    def verify_one(src):
-        """The files in ASM_LOADS request operands with inline asm and wait for them with hand-counted s_waitcnt vmcnt(N);
-        whether hipcc's register allocation respects that is a property of the generated code, not of the source.  So the
-        build proves it on the very code it ships (same flags, assembly instead of an object): tools/asm_inflight_check.py
-        walks every kernel and the build FAILS if any instruction touches a register whose load is still outstanding."""
-        sys.path.insert(0, os.path.join(HERE, "..", "tools"))
-        import asm_inflight_check as chk
-        asm = os.path.join(objdir, src.replace(".hip", ".s"))
-        cmd = common + SOURCES[src] + ["-S", "--cuda-device-only", os.path.join(CSRC, src), "-o", asm]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("hipcc -S failed for %s:\n%s" % (src, r.stderr))
-        for name, body in chk.kernels(asm):
-            if any(k in name for k in NO_SCRATCH.get(src, ())) and any(("scratch_" in l or "buffer_store" in l) for l in body):
-                raise RuntimeError("%s: %s spills registers to scratch (this hipcc allocates registers differently from the one the "
-                                   "kernel was written with)" % (src, name))
-            bad = chk.check_kernel(name, body)
-            if bad:
-                raise RuntimeError("%s: %s touches a register whose asm load is still in flight (%d places, first: %s); "
-                                   "this hipcc allocates registers differently from the one the kernels were written with"
-                                   % (src, name, len(bad), bad[0][1]))
-            sd = chk.check_store_data_hazard(name, body)
-            if sd:
-                raise RuntimeError("%s: %s overwrites the data of a wide store %d wait states behind it (%s ; %s)"
-                                   % (src, name, sd[0][3], sd[0][1], sd[0][2]))
-            mh = chk.check_mfma_asm_read_hazard(name, body)
-            if mh:
-                raise RuntimeError("%s: %s reads a matrix-instruction result with an asm vector instruction %d wait states behind it "
-                                   "(%s ; %s)" % (src, name, mh[0][3], mh[0][2], mh[0][1]))
-            hz = chk.check_scalar_base_hazard(name, body)
-            if hz:
-                raise RuntimeError("%s: %s uses a scalar base %d wait states after a VALU write of it (%s -> %s)"
-                                   % (src, name, hz[0][3], hz[0][2], hz[0][1]))
-        return src
-
-    def verify_no_scratch(src):
-        """The kernels of NO_SCRATCH_PLAIN in the code the build ships (same flags, assembly instead of an object)."""
-        asm = os.path.join(objdir, src.replace(".hip", ".s"))
-        cmd = common + SOURCES[src] + ["-S", "--cuda-device-only", os.path.join(CSRC, src), "-o", asm]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("hipcc -S failed for %s:\n%s" % (src, r.stderr))
-        text = open(asm).read()
-        for kernel in NO_SCRATCH_PLAIN[src]:
-            at = text.find(".amdhsa_kernel")
-            found = False
-            while at >= 0:
-                end = text.find(".end_amdhsa_kernel", at)
-                block = text[at:end]
-                if kernel in block.split("\n", 1)[0]:
-                    found = True
-                    size = [l.split()[-1] for l in block.splitlines() if ".amdhsa_private_segment_fixed_size" in l]
-                    if size != ["0"]:
-                        raise RuntimeError("%s: %s uses %s bytes of scratch per lane" % (src, kernel, size))
-                at = text.find(".amdhsa_kernel", end)
-            if not found:
-                raise RuntimeError("%s: kernel %s not found in the generated assembly" % (src, kernel))
-        return src
-
-    with ThreadPoolExecutor(max_workers=4) as ex:
-        verify = os.environ.get("SCREAM_BUILD_VERIFY", "1") != "0"
-        checks = [ex.submit(verify_one, src) for src in ASM_LOADS] if verify else []
-        checks += [ex.submit(verify_no_scratch, src) for src in NO_SCRATCH_PLAIN] if verify else []
-        objs = list(ex.map(compile_one, SOURCES.items()))
-        for c in checks:
-            c.result()
-    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", LIB + ".tmp"] + objs
+def _compile(src: str, out: str, flags=None, asm: bool = False, verbose: bool = False) -> str:
+    """The one hipcc command line of a source (a file of csrc/ by name, or an absolute path): the object the library is linked from, or with
+    asm=True the assembly of the same device code.  flags: instead of the file's own in SOURCES."""
+    flags = SOURCES[os.path.basename(src)] if flags is None else list(flags)
+    cmd = [_hipcc()] + COMMON + flags + (["-S", "--cuda-device-only"] if asm else ["-c"]) + [os.path.join(CSRC, src), "-o", out]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
+        raise RuntimeError("hipcc failed for %s:\n%s\n%s" % (src, " ".join(cmd), r.stderr))
+    if verbose and r.stderr.strip():
+        print(r.stderr, file=sys.stderr)
+    return out
+
+
+def assembly(src: str, flags=None, out: str = None, force: bool = False) -> str:
+    """Path of the gfx950 assembly of a source: by default with the shipped flags, as scream_amd/build/<name>.s -- the file the gate
+    reads and the CPU tests assert on, generated once and again only when a source, the header or this file is newer.  With flags
+    or out (experiment builds, test fixtures) it is generated on every call."""
+    shipped = flags is None and out is None
+    out = out or os.path.join(OBJDIR, os.path.basename(src).replace(".hip", ".s"))
+    if force or not shipped or _stale(out):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        os.replace(_compile(src, out + ".tmp", flags, asm=True), out)
+    return out
+
+
+def build(force: bool = False, verbose: bool = False, out: str = None) -> str:
+    """out: write the library there instead of scream_amd/libscream_hip.so (experiment builds loaded with SCREAM_LIB=)."""
+    lib, force = out or LIB, force or bool(out)
+    if not force and not _stale(lib):
+        return lib
+    os.makedirs(OBJDIR, exist_ok=True)
+
+    def gate(src):
+        return asm_check.gate(assembly(src, force=force), *GATE[src])
+
+    with ThreadPoolExecutor(max_workers=4) as ex:
+        checks = [ex.submit(gate, src) for src in GATE] if os.environ.get("SCREAM_BUILD_VERIFY", "1") != "0" else []
+        objs = list(ex.map(lambda src: _compile(src, os.path.join(OBJDIR, src.replace(".hip", ".o")), verbose=verbose), SOURCES))
+        for c in checks:
+            c.result()
+    r = subprocess.run([_hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib + ".tmp"] + objs, capture_output=True, text=True)
+    if r.returncode != 0:
         raise RuntimeError("link failed:\n%s" % r.stderr)
-    os.replace(LIB + ".tmp", LIB)
-    return LIB
+    os.replace(lib + ".tmp", lib)
+    return lib
 
 
 if __name__ == "__main__":

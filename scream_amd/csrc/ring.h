@@ -80,7 +80,7 @@ __device__ __forceinline__ void mfma_group(f32x16& acc, const typename SP::vec (
 // is how hipcc restores a spilled scalar) and a vector-memory instruction that reads it as its address.  hipcc inserts them
 // in front of its own memory instructions but does not look inside an asm statement: a scalar base restored right in front
 // of one of these loads or stores was read stale, and the access went to a wild address (round 2, the ring-design projection
-// kernel's query-only variant: memory fault).  tools/asm_inflight_check.py verifies the wait states on the generated code of
+// kernel's query-only variant: memory fault).  scream_amd/asm_check.py verifies the wait states on the generated code of
 // every kernel that uses these helpers, at every build (scream_amd/build.py refuses to link otherwise; the CPU suite asserts).
 // four loads STEP bytes apart: the pieces a = 0 .. 3 of a fragment-major segment (1 KiB) or of a lane's 128-byte segment (32 B)
 // NT: the non-temporal hint (rows that stream through once: the L2 then keeps the weight image instead of them)

@@ -172,7 +172,7 @@ __global__ __launch_bounds__(TT, 1) void tail_kernel(const float* __restrict__ Q
     for (int u = 0; u < PIECES; ++u) dma_piece(1, u);
 
     // ---- row operand requests (inline asm; every consumer sits behind a counted wait + pin) -------------------------
-    // RULE (tools/asm_inflight_check.py enforces it on the generated code): a requested register is consumed at the top
+    // RULE (scream_amd/asm_check.py enforces it on the generated code): a requested register is consumed at the top
     // of the NEXT stage, never kept pending across a LayerNorm block -- hipcc, which believes the value present, otherwise
     // spills it to scratch right behind the asm statement when registers are short there.
     // grp: first float of the wave's 32-row group (8192 floats in either layout); segment seg, piece a, this lane:

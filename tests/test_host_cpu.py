@@ -521,18 +521,15 @@ def test_fp16_exponents_raise_outside_their_range_instead_of_clamping():
         scales.tail_exps(torch.full((256, 256), 2.0 ** 38), torch.ones(1024, 256), torch.ones(256, 1024), g, b, 2.0 ** 38, 1.0)
 
 
-def test_split_kernel_k_loop_has_no_register_spills(tmp_path):
+def test_split_kernel_k_loop_has_no_register_spills():
     """gemm_split.hip loads its A operands with inline asm, so the compiler does not know those registers are in flight:
     a spill (scratch store) of one of them inside the k-loop would save stale bytes.  Compile to assembly and require
     the k-loop of every instantiation to be free of scratch traffic (spills outside it only touch loop invariants)."""
-    import re, shutil, subprocess
+    import re, shutil
     if shutil.which("hipcc") is None:
         pytest.skip("hipcc not available")
-    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scream_amd", "csrc", "gemm_split.hip")
-    out = tmp_path / "x3.s"
-    subprocess.run(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only", "-o", str(out), src],
-                   check=True, capture_output=True, timeout=600)
-    lines = out.read_text().splitlines()
+    from scream_amd import build
+    lines = open(build.assembly("gemm_split.hip")).read().splitlines()
     starts = [i for i, l in enumerate(lines) if re.match(r"^_ZN.*gemm_split_kernelINS_\d+Split\w+ELi\d+ELb[01]E.*:", l)]
     assert len(starts) == 36  # three operand splits x six epilogues x two layouts of the A operand
     checked = 0
@@ -560,24 +557,20 @@ def test_split_kernel_k_loop_has_no_register_spills(tmp_path):
     assert checked == 36
 
 
-def test_no_instruction_touches_a_register_whose_asm_load_is_pending(tmp_path):
+def test_no_instruction_touches_a_register_whose_asm_load_is_pending():
     """gemm_split.hip and tail_split.hip load operands with inline asm and wait for them with hand-counted s_waitcnt vmcnt(N):
     hipcc believes such a register holds its value from the asm statement on and may copy, spill or reuse it before the
     wait (the round-1 advisor's finding; round 2 saw it happen -- a scratch_store of the destination right behind the
     load -- until the tail kernel stopped keeping requests pending across its LayerNorm blocks).
-    tools/asm_inflight_check.py walks the control-flow graph of the generated code with the in-order model of the
+    scream_amd/asm_check.py walks the control-flow graph of the generated code with the in-order model of the
     vector-memory queue and reports every instruction that touches a VGPR whose load is still outstanding: none allowed."""
-    import shutil, subprocess
+    import shutil
     if shutil.which("hipcc") is None:
         pytest.skip("hipcc not available")
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    import asm_inflight_check as chk
-    for src, extra, want in (("gemm_split.hip", [], "gemm_split_kernel"), ("tail_split.hip", ["-ffp-contract=off"], "11tail_kernel")):  # (the mangled name: not pack_tail_kernel)
-        out = tmp_path / (src + ".s")
-        subprocess.run(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only", *extra, "-o", str(out),
-                        os.path.join(REPO, "scream_amd", "csrc", src)], check=True, capture_output=True, timeout=900)
+    from scream_amd import asm_check as chk, build
+    for src, want in (("gemm_split.hip", "gemm_split_kernel"), ("tail_split.hip", "11tail_kernel")):  # (the mangled name: not pack_tail_kernel)
         n_kernels = 0
-        for name, body in chk.kernels(str(out)):
+        for name, body in chk.kernels(build.assembly(src)):
             if want not in name:
                 continue
             n_kernels += 1
@@ -605,10 +598,9 @@ def test_no_instruction_touches_a_register_whose_asm_load_is_pending(tmp_path):
 
 
 def test_the_static_checker_detects_what_it_is_there_for():
-    """tools/asm_inflight_check.py guards the build; these are its three detectors on hand-written snippets (the patterns that
+    """scream_amd/asm_check.py guards the build; these are its three detectors on hand-written snippets (the patterns that
     were really seen in round 2), each with its fixed counterpart."""
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    import asm_inflight_check as chk
+    from scream_amd import asm_check as chk
     lines = lambda text: [l for l in text.strip().splitlines()]
     # (1) a pending asm-load destination copied before the counted wait
     bad = lines("""
@@ -680,16 +672,15 @@ def test_the_static_checker_detects_what_it_is_there_for():
 
 
 def test_verify_source_refuses_asm_loads_touched_in_flight(tmp_path):
-    """asm_inflight_check.verify_source compiles a source with the flags of the object that will run and checks the generated
-    code: it refuses to hand back a library whose inline-asm loads are touched while still in flight (round 2 launched an
-    unverified build of the layer tail with exactly that defect and faulted the GPU), and the shipped fp16 layer tail passes it."""
+    """asm_check.verify_source compiles a source with the flags of the object that will run and puts the generated code through
+    asm_check.gate, the build's own gate: it refuses to hand back a library whose inline-asm loads are touched while still in
+    flight (round 2 launched an unverified build of the layer tail with exactly that defect and faulted the GPU), and the shipped
+    fp16 layer tail passes it."""
     import shutil
     if shutil.which("hipcc") is None:
         pytest.skip("hipcc not available")
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    import asm_inflight_check as chk
-    src = os.path.join(REPO, "scream_amd", "csrc", "tail_split.hip")
-    assert chk.verify_source(src, ["-ffp-contract=off"], str(tmp_path / "t1.s"), "11tail_kernelINS_7SplitH2ELb0EE") == 1  # (the shipped flags, scream_amd/build.py)
+    from scream_amd import asm_check as chk, build
+    assert chk.gate(build.assembly("tail_split.hip"), *build.GATE["tail_split.hip"], want="11tail_kernelINS_7SplitH2ELb0EE") == 1  # (the shipped flags, scream_amd/build.py)
     bad = tmp_path / "bad.hip"  # a register load consumed behind a wait that does not cover it
     bad.write_text("""#include <hip/hip_runtime.h>
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -702,23 +693,68 @@ __global__ void k(const float* p, float* o) {
 """)
     with pytest.raises(RuntimeError, match="still in flight"):
         chk.verify_source(str(bad), [], str(tmp_path / "bad.s"))
+    with pytest.raises(RuntimeError, match=r"bad\.s: _Z1kPKfPf touches .*: \S+ v"):  # file, kernel and instruction
+        chk.gate(str(tmp_path / "bad.s"), True)
 
 
-def test_f32_kernel_k_loop_has_no_register_spills(tmp_path):
+def _private_memory_fixture(tmp_path):
+    """Two kernels of the same shape: `with_array` indexes a per-thread array of 1 KiB by a value known only at run time, which hipcc
+    keeps in private memory (it is too large for registers and cannot be promoted); `plain` has no array."""
+    from scream_amd import build
+    src = tmp_path / "private.hip"
+    src.write_text("""#include <hip/hip_runtime.h>
+__global__ void with_array(const int* idx, float* o) {
+    float a[256];
+    for (int i = 0; i < 256; ++i) a[i] = o[i] * float(i);
+    o[threadIdx.x] = a[idx[threadIdx.x] & 255] + a[idx[threadIdx.x + 64] & 255];
+}
+__global__ void plain(const int* idx, float* o) { o[threadIdx.x] = float(idx[threadIdx.x]); }
+""")
+    return build.assembly(str(src), [], str(tmp_path / "private.s"))
+
+
+def test_the_gate_refuses_a_kernel_that_uses_scratch(tmp_path):
+    """The no-scratch rule of asm_check.gate reads the private segment size of the kernel descriptor: a named kernel with a
+    per-thread array in private memory is refused, the same kernel without the array passes."""
+    import shutil
+    if shutil.which("hipcc") is None:
+        pytest.skip("hipcc not available")
+    from scream_amd import asm_check as chk
+    asm = _private_memory_fixture(tmp_path)
+    sizes = chk.private_segments(asm)
+    assert sizes["_Z10with_arrayPKiPf"] >= 1024 and sizes["_Z5plainPKiPf"] == 0  # the fixture is what it claims to be
+    with pytest.raises(RuntimeError, match=r"private\.s: _Z10with_arrayPKiPf uses \d+ bytes of scratch"):
+        chk.gate(asm, False, ("with_array",))
+    with pytest.raises(RuntimeError, match="bytes of scratch"):
+        chk.gate(asm, True, ("plain", "with_array"))  # ... beside the detectors and behind a name that passes
+    assert chk.gate(asm, False, ("plain",)) == 0 and chk.gate(asm, True, ("plain",)) == 2  # (the detectors saw both kernels)
+
+
+def test_the_gate_refuses_a_no_scratch_name_that_matches_no_kernel(tmp_path):
+    """A kernel that was renamed must not pass the no-scratch rule unseen: a name fragment without a kernel is refused, for a file
+    with the asm-load protocol and for one without."""
+    import shutil
+    if shutil.which("hipcc") is None:
+        pytest.skip("hipcc not available")
+    from scream_amd import asm_check as chk
+    asm = _private_memory_fixture(tmp_path)
+    for asm_loads in (False, True):
+        with pytest.raises(RuntimeError, match=r"private\.s: no kernel named \*plain_kernel\*"):
+            chk.gate(asm, asm_loads, ("plain", "plain_kernel"))
+
+
+def test_f32_kernel_k_loop_has_no_register_spills():
     """gemm_f32.hip (the non-default SCREAM_GEMM=f32 path) is built at 2 blocks per CU = 128 VGPRs + 128 accumulators, and
     hipcc parks a handful of LOOP INVARIANTS (tile bookkeeping, epilogue pointers) in scratch: 6-18 dwords per
     instantiation, stored in the kernel prologue / at the top of the persistent tile loop and reloaded in the epilogue.
     That is harmless -- its A loads are ordinary compiler-tracked loads, so a spill can never capture an in-flight
     register (unlike gemm_split.hip's inline-asm loads) -- as long as none of it sits inside the k-loop, where it would cost
     a scratch round trip per 32-deep k-tile.  Pin exactly that."""
-    import re, shutil, subprocess
+    import re, shutil
     if shutil.which("hipcc") is None:
         pytest.skip("hipcc not available")
-    src = os.path.join(REPO, "scream_amd", "csrc", "gemm_f32.hip")
-    out = tmp_path / "f32.s"
-    subprocess.run(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only", "-o", str(out), src],
-                   check=True, capture_output=True, timeout=600)
-    lines = out.read_text().splitlines()
+    from scream_amd import build
+    lines = open(build.assembly("gemm_f32.hip")).read().splitlines()
     starts = [i for i, l in enumerate(lines) if re.match(r"^_ZN.*gemm_f32_kernelILi\d+ELi32EE.*:", l)]
     assert len(starts) == 6
     for a, b in zip(starts, starts[1:] + [len(lines)]):
@@ -843,24 +879,21 @@ def test_bench_launches_its_own_ranks(tmp_path):
     assert r.returncode == 3 and not r.stdout.strip()
 
 
-def test_ring_projection_kernel_keeps_its_registers(tmp_path):
+def test_ring_projection_kernel_keeps_its_registers():
     """csrc/proj_ring.hip holds the operand planes of a wave's 64 rows in the WHOLE accumulation register file (256 AGPRs, pinned
     with "+a" constraints) and its accumulators in VGPRs (-mllvm -amdgpu-mfma-vgpr-form=1, scream_amd/build.py): the generated code
     must have no scratch, and the only moves between the two register files are the 256 writes per tile that park the freshly split
     planes -- left to itself hipcc keeps the planes VGPR-class and moves each one back in front of every matrix instruction
     (1 141 moves, a quarter of the kernel's vector instructions, when the kernel was first built)."""
-    import re, shutil, subprocess
+    import re, shutil
     if shutil.which("hipcc") is None:
         pytest.skip("hipcc not available")
-    from scream_amd import build as B
-    src = os.path.join(REPO, "scream_amd", "csrc", "proj_ring.hip")
-    out = tmp_path / "ring.s"
-    subprocess.run(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", *B.SOURCES["proj_ring.hip"], "-S", "--cuda-device-only", "-o", str(out), src],
-                   check=True, capture_output=True, timeout=600)
-    text = out.read_text()
-    m = re.search(r"^(\S*proj_ring_kernelINS_7SplitH2\S*):[^\n]*\n(.*?)\.Lfunc_end", text, re.S | re.M)
-    assert m, "proj_ring_kernel<SplitH2> not found"
-    body = m.group(2)
+    from scream_amd import asm_check, build
+    asm = build.assembly("proj_ring.hip")
+    text = open(asm).read()
+    found = ["\n".join(body) for name, body in asm_check.kernels(asm) if "proj_ring_kernelINS_7SplitH2" in name]
+    assert found, "proj_ring_kernel<SplitH2> not found"
+    body = found[0]
     assert "scratch_" not in body
     assert len(re.findall(r"v_accvgpr_write", body)) == 256 and len(re.findall(r"v_accvgpr_read", body)) == 0
     assert len(re.findall(r"v_mfma_f32_32x32x16_f16 v\[", body)) == len(re.findall(r"v_mfma_f32_32x32x16_f16", body))  # accumulators in VGPRs

@@ -8,21 +8,18 @@ hipcc makes, not of the source (left alone hipcc gathered a whole query chunk's 
     cannot hide even in principle).
 
 A stage is what stands between two s_barrier of proj_ring_kernel<SplitH2> with at least 96 matrix instructions."""
-import os
 import re
 import shutil
-import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TRANS = ("v_exp", "v_log", "v_rcp", "v_rsq", "v_sqrt", "v_sin", "v_cos")
 
 
 def _stages(body):
     """per stage: the list of (vector instructions, transcendentals) of its gaps, in program order"""
     stages, gaps, v, t, seen = [], [], 0, 0, False
-    for line in body.splitlines():
+    for line in body:
         s = line.strip()
         if not s or s.startswith(";") or s.endswith(":") or re.match(r"^\.L\S+:", s):
             continue
@@ -41,17 +38,13 @@ def _stages(body):
     return [g for g in stages if len(g) + 1 >= 96]
 
 
-def test_every_gap_of_a_ridden_stage_can_hide_what_it_holds(tmp_path):
+def test_every_gap_of_a_ridden_stage_can_hide_what_it_holds():
     if shutil.which("hipcc") is None:
         pytest.skip("hipcc not available")
-    from scream_amd import build as B
-    src = os.path.join(REPO, "scream_amd", "csrc", "proj_ring.hip")
-    out = tmp_path / "ring.s"
-    subprocess.run(["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", *B.SOURCES["proj_ring.hip"], "-S", "--cuda-device-only", "-o", str(out), src],
-                   check=True, capture_output=True, timeout=600)
-    m = re.search(r"^(\S*proj_ring_kernelINS_7SplitH2\S*):[^\n]*\n(.*?)\.Lfunc_end", out.read_text(), re.S | re.M)
-    assert m, "proj_ring_kernel<SplitH2> not found"
-    stages = _stages(m.group(2))
+    from scream_amd import asm_check, build
+    found = [body for name, body in asm_check.kernels(build.assembly("proj_ring.hip")) if "proj_ring_kernelINS_7SplitH2" in name]
+    assert found, "proj_ring_kernel<SplitH2> not found"
+    stages = _stages(found[0])
     ridden = [g for g in stages if sum(v for v, _ in g) >= 64]  # a ride: query 256, key ~350, value ~80 vector instructions in the gaps
     assert len(ridden) >= 6, "the ridden stages of the kernel were not found: %s" % [sum(v for v, _ in g) for g in stages]
     for g in ridden:

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """Instruction mix per basic block of one kernel in an assembly file: asm_mix.py file.s kernel-substring [min_mfma]"""
-import re, sys, collections
-s = open(sys.argv[1]).read()
+import collections, os, re, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from scream_amd.asm_check import kernels
 key = sys.argv[2]
 lim = int(sys.argv[3]) if len(sys.argv) > 3 else 20
-m = re.search(r'^(\S*' + re.escape(key) + r'\S*):[^\n]*\n(.*?)\.Lfunc_end', s, re.S | re.M)
-body = m.group(2).splitlines()
+body = next(b for n, b in kernels(sys.argv[1]) if key in n)[1:]
 blocks = []; cur = ['entry', collections.Counter()]
 for l in body:
     t = l.strip()

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """How well the vector instructions of a kernel are interleaved with its matrix instructions: histogram of the lengths of the runs of
 VALU-class instructions between two consecutive MFMAs (and of the MFMA runs with nothing between them): asm_runs.py file.s kernel-substring"""
-import re, sys, collections
-s = open(sys.argv[1]).read()
+import collections, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from scream_amd.asm_check import kernels
 key = sys.argv[2]
-m = re.search(r'^(\S*' + re.escape(key) + r'\S*):[^\n]*\n(.*?)\.Lfunc_end', s, re.S | re.M)
+body = next(b for n, b in kernels(sys.argv[1]) if key in n)[1:]
 vr = collections.Counter(); mr = collections.Counter(); v = 0; mm = 0; seen = False; cyc = 0
-for l in m.group(2).splitlines():
+for l in body:
     t = l.strip()
     if not t or t.startswith(';') or t.endswith(':'): continue
     op = t.split()[0]

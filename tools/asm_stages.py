@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Instruction mix between consecutive s_barrier instructions of one kernel (in program order): asm_stages.py file.s kernel-substring"""
-import re, sys, collections
-s = open(sys.argv[1]).read()
+import collections, os, re, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from scream_amd.asm_check import kernels
 key = sys.argv[2]
-m = re.search(r'^(\S*' + re.escape(key) + r'\S*):[^\n]*\n(.*?)\.Lfunc_end', s, re.S | re.M)
+body = next(b for n, b in kernels(sys.argv[1]) if key in n)[1:]
 segs = []; c = collections.Counter(); lab = 'entry'
-for l in m.group(2).splitlines():
+for l in body:
     t = l.strip()
     if not t or t.startswith(';'): continue
     if re.match(r'^\.LBB\d+_\d+:', t):
