@@ -1,4 +1,10 @@
-"""ctypes binding of libscream_hip.so (include/scream_hip.h).
+"""ctypes binding of libscream_hip.so, derived from include/scream_hip.h.
+
+The header is the one statement of the C ABI: it is parsed once, when this module is imported, into PROTOTYPES (per function:
+return type, argument types, parameter names, what every pointer points to, whether it ends in `void* stream`) and SIGNATURES
+(name -> (restype, argtypes), what load() gives ctypes).  A prototype the parser cannot read, or a struct pointer without a
+class below, raises at import: nothing is skipped.  Only the five ctypes.Structure classes are still written by hand beside
+their typedefs.  ops.call marshals every argument by these declarations.
 
 The product path has no CPU fallback: if the library cannot be built/loaded the first use
 raises, loudly.  ``SCREAM_NO_BUILD=1`` forbids the lazy hipcc build (the GPU box normally
@@ -8,18 +14,14 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
+import re
+from typing import Dict, NamedTuple, Optional, Tuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SCREAM_LIB=<path>: load that build instead (A/B runs of two builds on the same GPU box; never built automatically)
 LIB_PATH = os.environ.get("SCREAM_LIB") or os.path.join(_HERE, "libscream_hip.so")
+HEADER_PATH = os.path.join(_HERE, "..", "include", "scream_hip.h")
 ABI_VERSION = 21
-
-c_f32p = C.POINTER(C.c_float)
-c_i32p = C.POINTER(C.c_int32)
-c_u8p = C.POINTER(C.c_uint8)
-c_u64p = C.POINTER(C.c_uint64)
-
 
 SPLIT_H1, SPLIT_H2, SPLIT_BF3 = 1, 2, 3
 
@@ -60,105 +62,60 @@ class GanGradsT(C.Structure):
     _fields_ = [("w", C.c_void_p * 5), ("b0", C.c_void_p), ("b4", C.c_void_p), ("gamma", C.c_void_p * 3), ("beta", C.c_void_p * 3)]
 
 
-# name -> (restype, argtypes); every symbol include/scream_hip.h declares
-V, I32, I64, F32, F64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
-SIGNATURES = {
-    "scream_version": (C.c_char_p, []),
-    "scream_abi_version": (C.c_int, []),
-    "scream_gemm_f32": (C.c_int, [V, I64, V, V, I64, I64, I32, I32, I32, I32, V, V, I64, V, V, V]),
-    "scream_gemm_qkv_f32": (C.c_int, [V, I64, V, V, I64, I64, I32, I32, I32, V, V, V, I64, V, V]),
-    "scream_kv_finalize": (C.c_int, [V, V, V, I64, I32, I32, V, V]),
-    "scream_pack_w_split": (C.c_int, [V, I32, I32, I32, I32, V, V]),
-    "scream_gemm_split_f32": (C.c_int, [V, I64, V, V, I64, I64, I32, I32, I32, I32, V, V, I64, V, V, I32, I32, I32, I32, V]),
-    "scream_gemm_qkv_split_f32": (C.c_int, [V, I64, V, V, I64, I64, I32, I32, I32, V, V, V, I64, V, I32, I32, I32, I32, I32, I32, V]),
-    "scream_proj_image_bytes": (C.c_int64, [I32, I32]),
-    "scream_pack_proj": (C.c_int, [V, I32, I32, I32, I32, V, V]),
-    "scream_proj_qkv_f32": (C.c_int, [V, V, V, I64, I32, I32, V, V, V, I64, V, I32, I32, I32, I32, I32, V]),
-    "scream_tail_image_bytes": (C.c_int64, [I32, I32]),
-    "scream_kv_image_bytes": (C.c_int64, []),
-    "scream_pack_tail": (C.c_int, [V, V, V, V, I32, C.POINTER(TailExpsT), V, V]),
-    "scream_kv_finalize_image": (C.c_int, [V, V, V, I64, I32, I32, V, I32, I64, I64, I32, V]),
-    "scream_layer_tail_f32": (C.c_int, [V, V, V, I32, V, V, V, V, V, V, V, V, V, I64, I32, C.POINTER(TailExpsT), V]),
-    "scream_act_layout": (C.c_int, [V, V, I64, I32, V]),
-    "scream_pe_embed_ln": (C.c_int, [V, V, V, V, V, V, V, V, V, I64, V]),
-    "scream_pe_embed_ln_frag": (C.c_int, [V, V, V, V, V, V, V, V, V, I64, V]),
-    "scream_kv_reduce": (C.c_int, [V, V, I64, I64, V, V, I32, I32, I32, V, V, V]),
-    "scream_attn_apply": (C.c_int, [V, I64, V, V, I32, V, V, I64, I64, V]),
-    "scream_coor_head": (C.c_int, [V, V, V, V, I64, V]),
-    "scream_forward_workspace_bytes": (C.c_int64, [I64, I64, I32, I32, I32, I32]),
-    "scream_forward": (C.c_int, [C.POINTER(ModelT), C.POINTER(BatchT), V, I64, V, V, V, V]),
-    "scream_trace_create": (C.c_void_p, [I32]),
-    "scream_trace_destroy": (None, [V]),
-    "scream_trace_reset": (C.c_int, [V]),
-    "scream_trace_read": (C.c_int, [V, I32, V, V, V, V, V]),
-    "scream_trace_read_starts": (C.c_int, [V, I32, V]),
-    "scream_nn_search": (C.c_int, [V, V, V, V, V, V, V, I32, I32, I32, I64, I64, F32, V, V, V, V, V, V]),
-    "scream_square_distance": (C.c_int, [V, V, V, I32, I32, I32, V]),
-    "scream_kabsch_corr": (C.c_int, [V, V, V, V, V, V, V, V, V, I32, V, V, V]),
-    "scream_rigid_transform_3d": (C.c_int, [V, V, V, F32, I32, I32, V, V]),
-    "scream_transformation_error": (C.c_int, [V, V, I32, V, V, V]),
-    "scream_point_loss": (C.c_int, [V, V, V, V, V, V, I32, V, V]),
-    "scream_icp_workspace_bytes": (C.c_int64, [I64, I64, I32]),
-    "scream_icp_p2p": (C.c_int, [V, V, V, V, V, V, V, V, I32, I32, I32, I64, I64, F32, I32, F32, F32, V, V, V, V, I64, V]),
-    "scream_wgrad_workspace_bytes": (C.c_int64, [I64, I32, I32]),
-    "scream_gemm_wgrad_f32": (C.c_int, [V, I64, V, I64, I64, I32, I32, V, I32, V, V, I64, V]),
-    "scream_wgrad_split_workspace_bytes": (C.c_int64, [I64, I32, I32]),
-    "scream_gemm_wgrad_split_f32": (C.c_int, [V, I64, V, I64, I64, I32, I32, V, I32, V, I32, V, I64, V]),
-    "scream_gemm_bf16_f32": (C.c_int, [V, I64, V, V, I64, I64, I32, I32, I32, I32, V, V]),
-    "scream_gemm_dgrad_bf16_f32": (C.c_int, [V, I64, V, V, I64, I64, I32, I32, V]),
-    "scream_wgrad_bf16_workspace_bytes": (C.c_int64, [I64, I32, I32]),
-    "scream_gemm_wgrad_bf16_f32": (C.c_int, [V, I64, V, I64, I64, I32, I32, V, I32, V, V, I64, V]),
-    "scream_ln_fwd": (C.c_int, [V, V, V, V, V, V, V, I64, V]),
-    "scream_ln_bwd_workspace_bytes": (C.c_int64, [I64]),
-    "scream_ln_bwd": (C.c_int, [V, V, V, V, V, V, V, V, V, V, I32, I64, V, I64, V]),
-    "scream_attn_bwd_workspace_bytes": (C.c_int64, [I32, I32]),
-    "scream_attn_bwd": (C.c_int, [V, I64, I64, I64, V, V, V, V, I64, I64, I64, V, V, V, V, I32, I32, I32, I32, V, I64, V, V, I64,
-                                  V, I64, V]),
-    "scream_relu_bwd": (C.c_int, [V, V, I64, V]),
-    "scream_add_f32": (C.c_int, [V, V, I64, V]),
-    "scream_transpose_f32": (C.c_int, [V, I32, I32, V, V]),
-    "scream_coor_head_bwd": (C.c_int, [V, V, V, V, I64, V]),
-    "scream_grad3_workspace_bytes": (C.c_int64, [I64]),
-    "scream_grad3": (C.c_int, [V, V, V, V, I64, V, I32, V, V, I32, V, I64, V]),
-    "scream_pe_embed": (C.c_int, [V, V, V, V, V, V, V, I64, V]),
-    "scream_icp_p2p_range": (C.c_int, [V, V, V, V, V, V, V, V, I32, I32, I32, I64, I64, F32, I32, F32, F32, V, V, V, I32, I32, V, V, I64, V]),
-    "scream_icp_p2p_brute_range": (C.c_int, [V, V, V, V, V, V, V, V, I32, I32, I32, I64, I64, F32, I32, F32, F32, V, V, V, I32, I32, V, V, I64, V]),
-    "scream_render_workspace_bytes": (C.c_int64, [I32, I32, I32, I64]),
-    "scream_render_depth": (C.c_int, [V, V, V, V, V, V, I32, I32, I32, I64, V, I32, I32, F32, V, V, V, I64, V]),
-    "scream_render_depth_bwd": (C.c_int, [V, V, V, I32, I32, I64, V, I32, I32, F32, V, V, V, I64, V, V]),
-    "scream_voxel_workspace_bytes": (C.c_int64, [I64, I32]),
-    "scream_voxel_down_sample": (C.c_int, [V, V, V, I32, I32, V, V, V, V, V, I64, V]),
-    "scream_dsm_workspace_bytes": (C.c_int64, [I64, I32, I32]),
-    "scream_dsm_extract": (C.c_int, [V, V, V, I32, I64, V, V, V, I32, I64, I32, F32, V, V, V, I64, V]),
-    "scream_dsm_dem_assemble": (C.c_int, [V, V, V, V, I32, I32, I64, V, V, V]),
-    "scream_radius_workspace_bytes": (C.c_int64, [I64, I32, I32]),
-    "scream_radius_count": (C.c_int, [V, V, V, I32, I64, V, V, V, I32, I64, V, I32, F64, V, V, I64, V]),
-    "scream_radius_pairs": (C.c_int, [V, V, V, I32, I64, V, V, V, I32, I64, V, I32, F64, V, I64, I32, V, V, V]),
-    "scream_prep_pairs_workspace_bytes": (C.c_int64, [I64, I32, I32]),
-    "scream_prep_pairs": (C.c_int, [V, I32, I64, V, V, I32, V, V, V, F64, C.c_uint64, V, I32, I32, V, I32, I64, V, V, V, V, V, V, V,
-                                    V, I64, V]),
-    "scream_l1_pairs_workspace_bytes": (C.c_int64, [I32, I32]),
-    "scream_l1_pairs_fwd": (C.c_int, [V, V, V, V, V, V, V, I32, I32, I64, V, V, V, I64, V]),
-    "scream_l1_pairs_bwd": (C.c_int, [V, V, V, V, V, V, V, V, I32, I32, I64, V, V]),
-    "scream_icp_raw_workspace_bytes": (C.c_int64, [I64, I64, I32]),
-    "scream_icp_raw_range": (C.c_int, [V, V, V, V, V, V, I32, I32, I32, I64, I64, F64, I32, F64, F64, V, V, V, I32, I32, V, V, I64, V]),
-    "scream_icp_raw_nn": (C.c_int, [V, V, V, V, V, V, I32, I32, I32, I64, I64, F64, V, V, V, V, V, I64, V]),
-    "scream_adam_step": (C.c_int, [V, I32, V, I64, V, V, V, F64, F64, F64, F64, V]),
-    "scream_gan_conv_workspace_bytes": (C.c_int64, [I32, I32, I32, I32, I32, I32, I32]),
-    "scream_gan_conv_fwd": (C.c_int, [V, V, V, I32, I32, I32, I32, I32, I32, I32, V, V, I64, V]),
-    "scream_gan_conv_dgrad": (C.c_int, [V, V, V, I32, I32, I32, I32, I32, I32, V, V, I64, V]),
-    "scream_gan_conv_wgrad": (C.c_int, [V, V, I32, I32, I32, I32, I32, I32, V, V, V, I64, V]),
-    "scream_gan_bn_fwd": (C.c_int, [V, V, V, V, V, V, I32, I32, I32, I32, V, V, V, V]),
-    "scream_gan_bn_bwd": (C.c_int, [V, V, V, V, V, V, I32, I32, I32, V, V, V, V, V]),
-    "scream_gan_loss_g": (C.c_int, [V, I64, V, V]),
-    "scream_gan_loss_g_bwd": (C.c_int, [V, I64, V, V]),
-    "scream_gan_loss_d": (C.c_int, [V, I64, V, I64, V, V]),
-    "scream_gan_loss_d_bwd": (C.c_int, [V, V, I64, V, I64, V, V, V]),
-    "scream_pairs_transform": (C.c_int, [V, V, V, V, I32, I64, V, V]),
-    "scream_gan_workspace_bytes": (C.c_int64, [I32, I32, I32, I32, I32]),
-    "scream_gan_forward": (C.c_int, [V, C.POINTER(GanParamsT), I32, I32, I32, I32, I32, I32, V, V, I64, V]),
-    "scream_gan_backward": (C.c_int, [V, V, C.POINTER(GanParamsT), I32, I32, I32, I32, I32, V, I64, V, C.POINTER(GanGradsT), V]),
-}
+# the structs an entry point takes by pointer (scream_layer_t is reached only through scream_model_t)
+STRUCTS = {"scream_tail_exps_t": TailExpsT, "scream_model_t": ModelT, "scream_batch_t": BatchT,
+           "scream_gan_params_t": GanParamsT, "scream_gan_grads_t": GanGradsT}
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float, "double": C.c_double}
+_POINTEES = ("float", "int32_t", "int64_t", "uint64_t", "uint8_t", "double", "void")
+_RETURNS = dict(_SCALARS, **{"void": None, "void*": C.c_void_p, "const char*": C.c_char_p})
+
+
+class Prototype(NamedTuple):
+    restype: object
+    argtypes: Tuple
+    params: Tuple[str, ...]  # the parameter names
+    pointees: Tuple          # per parameter: None (a scalar), the pointee's C type name, or the Structure class of a struct pointer
+    stream: bool             # the last parameter is `void* stream`
+
+
+def parse_header(text: str) -> Dict[str, Prototype]:
+    """Every function prototype of a C header in the style of include/scream_hip.h.  What is left of the text without comments,
+    preprocessor lines, the extern "C" guard, struct typedefs and enums must be prototypes over the types above, every one;
+    anything else raises ValueError."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r"typedef\s+struct\s*\{[^}]*\}\s*\w+\s*;|enum\s*\{[^}]*\}\s*;", " ", text)
+    out = {}
+    for stmt in (" ".join(s.split()) for s in text.split(";")):
+        if not stmt:
+            continue
+        m = re.fullmatch(r"(.+?) ?\b(\w+) ?\((.*)\)", stmt)
+        if m is None or m.group(1) not in _RETURNS or m.group(2) in out:
+            raise ValueError("cannot read the prototype %r" % stmt)
+        name, argtypes, params, pointees = m.group(2), [], [], []
+        for decl in ([] if m.group(3).strip() == "void" else m.group(3).split(",")):
+            p = re.fullmatch(r"(const )?(\w+) ?(\*?) ?(\w+)", decl.strip())
+            if p is None:
+                raise ValueError("%s: cannot read the parameter %r" % (name, decl.strip()))
+            const, base, star, pname = p.groups()
+            if not star and not const and base in _SCALARS:
+                ctype, pointee = _SCALARS[base], None
+            elif star and base in _POINTEES:
+                ctype, pointee = C.c_void_p, base  # data pointers travel as integers (tensor.data_ptr())
+            elif star and const and base in STRUCTS:
+                ctype, pointee = C.POINTER(STRUCTS[base]), STRUCTS[base]
+            else:
+                raise ValueError("%s: no ctypes class for the parameter %r" % (name, decl.strip()))
+            argtypes.append(ctype), params.append(pname), pointees.append(pointee)
+        out[name] = Prototype(_RETURNS[m.group(1)], tuple(argtypes), tuple(params), tuple(pointees),
+                              bool(params) and params[-1] == "stream" and pointees[-1] == "void")
+    return out
+
+
+with open(HEADER_PATH) as _f:
+    PROTOTYPES = parse_header(_f.read())
+SIGNATURES = {name: (p.restype, list(p.argtypes)) for name, p in PROTOTYPES.items()}  # every symbol the header declares
 
 _lib: Optional[C.CDLL] = None
 

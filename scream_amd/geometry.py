@@ -7,7 +7,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import ops
 from .packing import PackedBatch
 
 __all__ = ["square_distance", "nn_search_pair", "chamfer_distance", "rigid_transform_3d", "integrate_trans", "transformation_error",
@@ -36,8 +36,7 @@ def square_distance(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     B, N, _ = src.shape
     _, M, _ = dst.shape
     out = torch.empty(B, N, M, device=src.device, dtype=torch.float32)
-    _lib.check(_lib.load().scream_square_distance(ops._p(src.contiguous().float()), ops._p(dst.contiguous().float()),
-                                                  ops._p(out), B, N, M, ops._stream()), "scream_square_distance")
+    ops.call("scream_square_distance", src.contiguous().float(), dst.contiguous().float(), out, B, N, M)
     return out
 
 

@@ -314,13 +314,12 @@ class PointTransformer(nn.Module):
         backend: the arithmetic of THIS call (default: self.gemm_backend); images are cached per backend (_pack_weights)."""
         pk = self._pack_weights(backend)
         mt = pk.mt
-        lib = _lib.load()
         dev = batch.xyz.device
         if ops._stream() not in pk.streams:  # first forward of this stream since the weights were packed
             torch.cuda.current_stream(dev).wait_event(pk.event)
             pk.streams.add(ops._stream())
-        need = lib.scream_forward_workspace_bytes(batch.rows_src, batch.rows_total, batch.n_pairs, batch.max_chunks, mt.gemm_split,
-                                                  mt.n_cross)
+        need = ops.call("scream_forward_workspace_bytes", batch.rows_src, batch.rows_total, batch.n_pairs, batch.max_chunks, mt.gemm_split,
+                        mt.n_cross)
         # one scratch buffer per stream: concurrent lanes (scream_amd/lanes.py) run forwards of the same model side by side
         if self._ws is None:
             self._ws = {}
@@ -336,9 +335,7 @@ class PointTransformer(nn.Module):
         bt.cloud_len = ops._p(batch.cloud_len, torch.int32)
         src_pred = torch.empty(batch.rows_src, 3, device=dev, dtype=torch.float32)
         feats = torch.empty(batch.rows_src, D_MODEL, device=dev, dtype=torch.float32) if return_feats else None
-        _lib.check(lib.scream_forward(C.byref(mt), C.byref(bt), ws.data_ptr(), ws.numel(),
-                                      src_pred.data_ptr(), feats.data_ptr() if return_feats else None,
-                                      trace, ops._stream()), "scream_forward")
+        ops.call("scream_forward", mt, bt, ws, ws.numel(), src_pred, feats, trace)
         return (src_pred, feats) if return_feats else src_pred
 
     def forward_batch(self, srcs: Sequence[torch.Tensor], tgts: Sequence[torch.Tensor],

@@ -2,6 +2,10 @@
 
 torch is plumbing here (device memory + the current HIP stream); all arithmetic happens in
 libscream_hip.so.  There is no CPU fallback: a tensor that is not on a HIP device is an error.
+
+Every call goes through call(name, *args), which marshals the arguments by the header's own declaration of the function
+(_lib.PROTOTYPES): tensors are passed as they are and checked against the parameter's pointee type.  _p(t, dtype) remains for
+the addresses call cannot check: a buffer whose dtype the header does not fix, a column offset, a struct field.
 """
 from __future__ import annotations
 
@@ -23,7 +27,8 @@ D_MODEL = 256
 
 
 def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
+    """The current stream's handle (torch.cuda.current_stream().cuda_stream without building a Stream object for every call)."""
+    return torch._C._cuda_getCurrentRawStream(torch.cuda.current_device())
 
 
 def _p(t: Optional[torch.Tensor], dtype=torch.float32) -> Optional[int]:
@@ -46,13 +51,68 @@ def _rows(t: torch.Tensor) -> int:
     return _p(t) if t.is_contiguous() else _p(t[:1]) if t.shape[0] else t.data_ptr()
 
 
-def _workspace(lib_fn, name: str, *args, device, floor: int = 16) -> torch.Tensor:
+# what a tensor must hold to be passed for a pointer the header declares with this pointee (void*: images and workspaces)
+_DTYPES = {"float": torch.float32, "int32_t": torch.int32, "int64_t": torch.int64, "uint64_t": torch.int64, "uint8_t": torch.uint8,
+           "double": torch.float64, "void": torch.uint8}
+# name -> (per parameter: int / float for a scalar, the dtype behind a data pointer, the class behind a struct pointer;
+#          ends in `void* stream`; returns a size) for every entry point that returns a status or a size
+_PLANS = {name: (tuple((float if t in (C.c_float, C.c_double) else int) if pointee is None else _DTYPES.get(pointee, pointee)
+                       for t, pointee in zip(p.argtypes, p.pointees)), p.stream, p.restype is C.c_int64)
+          for name, p in _lib.PROTOTYPES.items() if p.stream or p.restype is C.c_int64}
+
+
+def call(name: str, *args):
+    """The one path into the library: scream_<name>(*args), every argument marshalled by the header's declaration of its
+    parameter.  A scalar becomes int() or float().  For a pointer: a tensor must be on the GPU, contiguous and of the pointee's
+    dtype (_DTYPES) and becomes its address; None is NULL; a Python int is an address the caller computed (a column offset,
+    _rows, a buffer whose dtype the header cannot know: _p(t, dtype) checks those); a ctypes structure goes by reference.  The
+    current stream is appended when the function ends in `void* stream` and the caller left it out.  A status other than 0 and
+    a negative size raise ScreamHipError naming the function; the value is returned."""
+    try:
+        kinds, has_stream, sizer = _PLANS[name]
+    except KeyError:
+        raise TypeError("%s is not an entry point that returns a status or a size" % name) from None
+    if has_stream and len(args) == len(kinds) - 1:
+        args += (_stream(),)
+    elif len(args) != len(kinds):
+        raise TypeError("%s takes %d arguments (%s), got %d" % (name, len(kinds), ", ".join(_lib.PROTOTYPES[name].params), len(args)))
+    conv = []
+    for kind, a in zip(kinds, args):
+        if kind is int or kind is float:
+            a = kind(a)
+        elif isinstance(a, torch.Tensor):
+            if a.dtype != kind or not a.is_cuda or not a.is_contiguous():
+                _refuse(name, len(conv), a, kind)
+            a = a.data_ptr()
+        elif type(a) is kind:
+            a = C.byref(a)
+        elif a is not None and not isinstance(a, int):
+            _refuse(name, len(conv), a, kind)
+        conv.append(a)
+    rc = getattr(_lib.load(), name)(*conv)
+    if not sizer:
+        if rc:
+            check(rc, name)
+    elif rc < 0:
+        raise _lib.ScreamHipError("%s(%s): invalid argument" % (name, ", ".join(str(a) for a in args)))
+    return rc
+
+
+def _refuse(name: str, index: int, a, kind):
+    """Raise for argument `index` of call(name, ...): _p's exception for a tensor, with the function and the parameter."""
+    where = "%s(%s): " % (name, _lib.PROTOTYPES[name].params[index])
+    if not isinstance(a, torch.Tensor):
+        raise TypeError(where + "expected %s, got %r" % (kind, a))
+    try:
+        _p(a, kind)
+    except (_lib.ScreamHipError, TypeError, ValueError) as e:
+        raise type(e)(where + str(e)) from None
+
+
+def _workspace(name: str, *args, device, floor: int = 16) -> torch.Tensor:
     """Scratch for one call: the uint8 tensor of the size that the library's own `*_workspace_bytes(*args)` asks for (at least
     `floor` bytes, so that it always has an address); a negative size is the library refusing the arguments."""
-    need = lib_fn(*args)
-    if need < 0:
-        raise _lib.ScreamHipError("%s(%s): invalid argument" % (name, ", ".join(str(a) for a in args)))
-    return torch.empty(max(need, floor), device=device, dtype=torch.uint8)
+    return torch.empty(max(call(name, *args), floor), device=device, dtype=torch.uint8)
 
 
 def gemm_f32(A: torch.Tensor, W: torch.Tensor, epilogue: int = EPI_NONE, n_act: int = 0, bias: Optional[torch.Tensor] = None,
@@ -64,9 +124,8 @@ def gemm_f32(A: torch.Tensor, W: torch.Tensor, epilogue: int = EPI_NONE, n_act: 
     assert W.shape[1] == K
     if out is None:
         out = torch.empty(M, N, device=A.device, dtype=torch.float32)
-    check(_lib.load().scream_gemm_f32(_rows(A), A.stride(0), _p(W), _rows(out), out.stride(0), M, N, K, epilogue, n_act, _p(bias),
-                                      _p(residual), residual.stride(0) if residual is not None else 0, _p(gamma), _p(beta), _stream()),
-          "scream_gemm_f32")
+    call("scream_gemm_f32", _rows(A), A.stride(0), W, _rows(out), out.stride(0), M, N, K, epilogue, n_act, bias,
+         residual, residual.stride(0) if residual is not None else 0, gamma, beta)
     return out
 
 
@@ -78,8 +137,7 @@ def gemm_bf16(A: torch.Tensor, W: torch.Tensor, epilogue: int = EPI_NONE, n_act:
     assert W.shape[1] == K and W.is_contiguous()
     if out is None:
         out = torch.empty(M, N, device=A.device, dtype=torch.float32)
-    check(_lib.load().scream_gemm_bf16_f32(_rows(A), A.stride(0), _p(W), _rows(out), out.stride(0), M, N, K, epilogue, n_act,
-                                           _p(bias), _stream()), "scream_gemm_bf16_f32")
+    call("scream_gemm_bf16_f32", _rows(A), A.stride(0), W, _rows(out), out.stride(0), M, N, K, epilogue, n_act, bias)
     return out
 
 
@@ -90,8 +148,7 @@ def gemm_dgrad_bf16(dY: torch.Tensor, W: torch.Tensor, out: Optional[torch.Tenso
     assert W.shape[0] == N and W.is_contiguous()
     if out is None:
         out = torch.empty(M, K, device=dY.device, dtype=torch.float32)
-    check(_lib.load().scream_gemm_dgrad_bf16_f32(_rows(dY), dY.stride(0), _p(W), _rows(out), out.stride(0), M, N, K, _stream()),
-          "scream_gemm_dgrad_bf16_f32")
+    call("scream_gemm_dgrad_bf16_f32", _rows(dY), dY.stride(0), W, _rows(out), out.stride(0), M, N, K)
     return out
 
 
@@ -138,7 +195,7 @@ def pack_w(W: torch.Tensor, split: Optional[int] = None, w_exp: Optional[int] = 
     w_exp = int(w_exp or 0)
     dt = torch.float16 if split in (SPLIT_H2, SPLIT_H1) else torch.bfloat16
     out = torch.empty(split, K // 32, N, 32, device=W.device, dtype=dt)
-    check(_lib.load().scream_pack_w_split(_p(W), N, K, split, w_exp, _p(out, dt), _stream()), "scream_pack_w_split")
+    call("scream_pack_w_split", W, N, K, split, w_exp, _p(out, dt))
     return PackedW(out, split, w_exp, N, K, W.abs().sum(dim=1).cpu() if split != SPLIT_BF3 else None)
 
 
@@ -150,7 +207,7 @@ def act_layout(X: torch.Tensor, to_fragment: bool) -> torch.Tensor:
     M = X.shape[0]
     assert X.shape[1] == D_MODEL
     out = torch.empty_like(X)
-    check(_lib.load().scream_act_layout(_p(X), _p(out), M, int(to_fragment), _stream()), "scream_act_layout")
+    call("scream_act_layout", X, out, M, to_fragment)
     return out
 
 
@@ -171,10 +228,9 @@ def gemm_split(A: torch.Tensor, Wp: PackedW, epilogue: int = EPI_NONE, n_act: in
     assert K == Wp.K
     if out is None:
         out = torch.empty(M, Wp.N, device=A.device, dtype=torch.float32)
-    check(_lib.load().scream_gemm_split_f32(_rows(A), A.stride(0), Wp.data_ptr(), _rows(out), out.stride(0), M, Wp.N, K, epilogue, n_act,
-                                            _p(bias), _p(residual), residual.stride(0) if residual is not None else 0, _p(gamma),
-                                            _p(beta), layout, Wp.split, _a_exp(A, Wp, a_exp), Wp.w_exp, _stream()),
-          "scream_gemm_split_f32")
+    call("scream_gemm_split_f32", _rows(A), A.stride(0), Wp.data_ptr(), _rows(out), out.stride(0), M, Wp.N, K, epilogue, n_act,
+         bias, residual, residual.stride(0) if residual is not None else 0, gamma, beta, layout, Wp.split, _a_exp(A, Wp, a_exp),
+         Wp.w_exp)
     return out
 
 
@@ -197,15 +253,12 @@ def pack_tail(Wm: torch.Tensor, W1: torch.Tensor, W2: torch.Tensor, split: Optio
     if split != SPLIT_BF3 and exps is None:
         raise ValueError("pack_tail on an fp16 split needs the operand exponents (scream_amd/scales.py)")
     exps = exps if exps is not None else tail_exps()
-    lib = _lib.load()
     if Wq_next is not None:
         Wq_next = Wq_next.detach().to(torch.float32).contiguous()
         assert Wq_next.shape == (D_MODEL, D_MODEL)
-    nbytes = lib.scream_tail_image_bytes(split, int(Wq_next is not None))
-    if nbytes < 0:
-        raise _lib.ScreamHipError("scream_tail_image_bytes returned %d (a next-layer query projection needs an fp16 split)" % nbytes)
-    out = torch.empty(nbytes, device=Wm.device, dtype=torch.uint8)
-    check(lib.scream_pack_tail(_p(Wm), _p(W1), _p(W2), _p(Wq_next), split, C.byref(exps), _p(out, torch.uint8), _stream()), "scream_pack_tail")
+    # (a negative size: a next-layer query projection needs an fp16 split)
+    out = torch.empty(call("scream_tail_image_bytes", split, Wq_next is not None), device=Wm.device, dtype=torch.uint8)
+    call("scream_pack_tail", Wm, W1, W2, Wq_next, split, exps, out)
     return PackedTail(out, split, exps, Wq_next is not None)
 
 
@@ -215,14 +268,12 @@ def kv_finalize_image(partial: torch.Tensor, cloud_row0, cloud_len, row_base: in
     the same `split` (default: default_split()): three bf16 planes, or two fp16 planes with a per-head exponent chosen on the device.
     partial [L, M/128, 8, 1056] (a batched key/value projection of L layers): returns [L, n_clouds, kv_image_bytes]."""
     split = default_split() if split is None else split
-    lib = _lib.load()
     L = partial.shape[0] if partial.dim() == 4 else 1
-    img = lib.scream_kv_image_bytes()
+    img = call("scream_kv_image_bytes")
     if out is None:
         out = torch.zeros((L, n_clouds, img) if partial.dim() == 4 else (n_clouds, img), device=partial.device, dtype=torch.uint8)
-    check(lib.scream_kv_finalize_image(_p(partial), _p(cloud_row0, torch.int32), _p(cloud_len, torch.int32), row_base,
-                                    cloud_begin, n_kv, _p(out, torch.uint8), L, partial[0].numel() if L > 1 else 0,
-                                    n_clouds * img if L > 1 else 0, split, _stream()), "scream_kv_finalize_image")
+    call("scream_kv_finalize_image", partial, cloud_row0, cloud_len, row_base, cloud_begin, n_kv, out, L,
+         partial[0].numel() if L > 1 else 0, n_clouds * img if L > 1 else 0, split)
     return out
 
 
@@ -237,10 +288,8 @@ def layer_tail(Q: torch.Tensor, kv_image: torch.Tensor, tile_cloud, kv_cloud_off
     assert (q_next is not None) == tail.next_q, "q_next goes with an image that carries the next layer's query stages"
     if out is None:
         out = torch.empty(M, D_MODEL, device=x.device, dtype=torch.float32)
-    check(_lib.load().scream_layer_tail_f32(_p(Q), _p(kv_image, torch.uint8), _p(tile_cloud, torch.int32),
-                                            kv_cloud_offset, _p(cloud_len, torch.int32), _p(x),
-                                            tail.data_ptr(), _p(g1), _p(b1), _p(g2), _p(b2), _p(out), _p(q_next),
-                                            M, tail.split, C.byref(tail.exps), _stream()), "scream_layer_tail_f32")
+    call("scream_layer_tail_f32", Q, kv_image, tile_cloud, kv_cloud_offset, cloud_len, x, tail.data_ptr(), g1, b1, g2, b2, out,
+         q_next, M, tail.split, tail.exps)
     return out
 
 
@@ -272,16 +321,14 @@ def gemm_qkv(A: torch.Tensor, W, n_q: int, tile_cloud, cloud_row0, cloud_len, ro
     sp = isinstance(W, PackedW)  # packed operand planes -> the split kernel
     N = W.N if sp else W.shape[0]
     Q, part = _qkv_outputs(A, N, n_q)
-    args = (_p(A), A.stride(0), W.data_ptr() if sp else _p(W), _p(Q), n_q, M, N, K, n_q,
-            _p(tile_cloud, torch.int32), _p(cloud_row0, torch.int32), _p(cloud_len, torch.int32), row_base, _p(part))
+    args = (A, A.stride(0), W.data_ptr() if sp else W, Q, n_q, M, N, K, n_q, tile_cloud, cloud_row0, cloud_len, row_base, part)
     if sp:
         # (bf16 x 3 is scale free: no exponent is read)
         a_exp, k_exp, v_exp = (0, 0, 0) if W.split == SPLIT_BF3 else _qkv_exps(A, W.row_l1, n_q, a_exp, k_exp, v_exp)
-        check(_lib.load().scream_gemm_qkv_split_f32(*args, layout, W.split, a_exp, W.w_exp, k_exp, v_exp, _stream()),
-              "scream_gemm_qkv_split_f32")
+        call("scream_gemm_qkv_split_f32", *args, layout, W.split, a_exp, W.w_exp, k_exp, v_exp)
     else:
         assert layout == 0
-        check(_lib.load().scream_gemm_qkv_f32(*args, _stream()), "scream_gemm_qkv")
+        call("scream_gemm_qkv_f32", *args)
     return Q, part
 
 
@@ -307,11 +354,8 @@ def pack_proj(W: torch.Tensor, n_q: int, split: Optional[int] = None, w_exp: Opt
     N, K = W.shape
     assert K == D_MODEL
     w_exp = scales.w_exp(W) if w_exp is None else int(w_exp)
-    nbytes = _lib.load().scream_proj_image_bytes(N, split)
-    if nbytes <= 0:
-        raise _lib.ScreamHipError("scream_proj_image_bytes(%d, %d) = %d" % (N, split, nbytes))
-    out = torch.empty(nbytes, device=W.device, dtype=torch.uint8)
-    check(_lib.load().scream_pack_proj(_p(W), N, n_q, split, w_exp, _p(out, torch.uint8), _stream()), "scream_pack_proj")
+    out = torch.empty(call("scream_proj_image_bytes", N, split), device=W.device, dtype=torch.uint8)
+    call("scream_pack_proj", W, N, n_q, split, w_exp, out)
     return PackedProj(out, split, w_exp, N, n_q, W.abs().sum(dim=1).cpu())
 
 
@@ -322,16 +366,14 @@ def proj_qkv(x_frag: torch.Tensor, P: PackedProj, tile_cloud, cloud_row0, cloud_
     M = x_frag.shape[0]
     Q, part = _qkv_outputs(x_frag, P.N, P.n_q)  # (n_q is 0 or the model width)
     a_exp, k_exp, v_exp = _qkv_exps(x_frag, P.row_l1, P.n_q, a_exp, k_exp, v_exp)
-    check(_lib.load().scream_proj_qkv_f32(_p(x_frag), P.data_ptr(), _p(Q), M, P.N, P.n_q, _p(tile_cloud, torch.int32),
-                                          _p(cloud_row0, torch.int32), _p(cloud_len, torch.int32), row_base, _p(part), P.split,
-                                          a_exp, P.w_exp, k_exp, v_exp, _stream()), "scream_proj_qkv_f32")
+    call("scream_proj_qkv_f32", x_frag, P.data_ptr(), Q, M, P.N, P.n_q, tile_cloud, cloud_row0, cloud_len, row_base, part, P.split,
+         a_exp, P.w_exp, k_exp, v_exp)
     return Q, part
 
 
 def kv_finalize(part, cloud_row0, cloud_len, row_base: int, cloud_begin: int, n_kv: int, n_clouds: int) -> torch.Tensor:
     kv = torch.zeros(n_clouds, 8, KV_ELEMS, device=part.device, dtype=torch.float32)
-    check(_lib.load().scream_kv_finalize(_p(part), _p(cloud_row0, torch.int32), _p(cloud_len, torch.int32), row_base,
-                                         cloud_begin, n_kv, _p(kv), _stream()), "scream_kv_finalize")
+    call("scream_kv_finalize", part, cloud_row0, cloud_len, row_base, cloud_begin, n_kv, kv)
     return kv
 
 
@@ -339,10 +381,8 @@ def pe_embed_ln(xyz, tile_cloud, center, dim_t, emb_w, emb_b, gamma, beta, frag:
     """A1.  frag=True: the same values in the fragment-major layout (include/scream_hip.h SCREAM_ACT_FRAG; act_layout undoes it)."""
     rows = xyz.shape[0]
     feats = torch.empty(rows, D_MODEL, device=xyz.device, dtype=torch.float32)
-    lib = _lib.load()
-    fn, name = (lib.scream_pe_embed_ln_frag, "scream_pe_embed_ln_frag") if frag else (lib.scream_pe_embed_ln, "scream_pe_embed_ln")
-    check(fn(_p(xyz), _p(tile_cloud, torch.int32), _p(center), _p(dim_t), _p(emb_w),
-             _p(emb_b), _p(gamma), _p(beta), _p(feats), rows, _stream()), name)
+    call("scream_pe_embed_ln_frag" if frag else "scream_pe_embed_ln", xyz, tile_cloud, center, dim_t, emb_w, emb_b, gamma, beta, feats,
+         rows)
     return feats
 
 
@@ -355,24 +395,20 @@ def kv_reduce(Kf: torch.Tensor, Vf: torch.Tensor, ld: int, row_base: int, cloud_
     for t in (Kf, Vf):
         if not t.is_cuda or t.dtype != torch.float32:
             raise TypeError("kv_reduce needs fp32 device tensors")
-    check(_lib.load().scream_kv_reduce(Kf.data_ptr(), Vf.data_ptr(), ld, row_base, _p(cloud_row0, torch.int32),
-                                       _p(cloud_len, torch.int32), cloud_begin, n_kv, max_chunks, _p(partial),
-                                       _p(kv), _stream()), "scream_kv_reduce")
+    call("scream_kv_reduce", Kf.data_ptr(), Vf.data_ptr(), ld, row_base, cloud_row0, cloud_len, cloud_begin, n_kv, max_chunks, partial, kv)
     return kv
 
 
 def attn_apply(Qf: torch.Tensor, ldq: int, kv, tile_cloud, kv_cloud_offset: int, cloud_len, rows: int) -> torch.Tensor:
     out = torch.empty(rows, D_MODEL, device=kv.device, dtype=torch.float32)
-    check(_lib.load().scream_attn_apply(Qf.data_ptr(), ldq, _p(kv), _p(tile_cloud, torch.int32), kv_cloud_offset,
-                                        _p(cloud_len, torch.int32), _p(out), D_MODEL, rows, _stream()),
-          "scream_attn_apply")
+    call("scream_attn_apply", Qf.data_ptr(), ldq, kv, tile_cloud, kv_cloud_offset, cloud_len, out, D_MODEL, rows)
     return out
 
 
 def coor_head(X: torch.Tensor, W: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     rows = X.shape[0]
     out = torch.empty(rows, 3, device=X.device, dtype=torch.float32)
-    check(_lib.load().scream_coor_head(_p(X), _p(W), _p(b), _p(out), rows, _stream()), "scream_coor_head")
+    call("scream_coor_head", X, W, b, out, rows)
     return out
 
 
@@ -387,18 +423,14 @@ def nn_search(query: torch.Tensor, ref: torch.Tensor, q_row0, q_len, r_row0, r_l
     idx = torch.empty(qn, device=dev, dtype=torch.int32)
     dmin = torch.empty(qn, device=dev, dtype=torch.float32)
     valid = torch.empty(qn, device=dev, dtype=torch.uint8)
-    check(_lib.load().scream_nn_search(_p(query), _p(ref), _p(q_row0, torch.int32), _p(q_len, torch.int32),
-                                       _p(r_row0, torch.int32), _p(r_len, torch.int32), _p(s), n_pairs, max_q_len,
-                                       max_r_len, qn, rn, float(thresh), _p(ref_prep), _p(keys, torch.int64),
-                                       _p(idx, torch.int32), _p(dmin), _p(valid, torch.uint8), _stream()),
-          "scream_nn_search")
+    call("scream_nn_search", query, ref, q_row0, q_len, r_row0, r_len, s, n_pairs, max_q_len, max_r_len, qn, rn, thresh, ref_prep,
+         keys, idx, dmin, valid)
     return idx, dmin, valid
 
 
 def render_workspace(n_pairs: int, n_views: int, w: int, src_rows_total: int, device) -> torch.Tensor:
     """Scratch of render_depth; render_depth_bwd needs the forward's, untouched (it begins with the depth ranges)."""
-    return _workspace(_lib.load().scream_render_workspace_bytes, "scream_render_workspace_bytes", n_pairs, n_views, w, src_rows_total,
-                      device=device)
+    return _workspace("scream_render_workspace_bytes", n_pairs, n_views, w, src_rows_total, device=device)
 
 
 def render_depth(src: torch.Tensor, s_row0, s_len, tgt: torch.Tensor, t_row0, t_len, max_s_len: int, max_t_len: int,
@@ -411,10 +443,8 @@ def render_depth(src: torch.Tensor, s_row0, s_len, tgt: torch.Tensor, t_row0, t_
         workspace = render_workspace(n_pairs, V, w, src.shape[0], dev)
     imgs = torch.empty(n_pairs, V, 2, w, w, device=dev, dtype=torch.float32)
     argmax = torch.empty(n_pairs, V, 2, w, w, device=dev, dtype=torch.int32)
-    check(_lib.load().scream_render_depth(_p(src), _p(s_row0, torch.int32), _p(s_len, torch.int32), _p(tgt), _p(t_row0, torch.int32),
-                                          _p(t_len, torch.int32), n_pairs, int(max_s_len), int(max_t_len), src.shape[0],
-                                          _p(rot.reshape(V, 9)), V, int(w), float(rho), _p(imgs), _p(argmax, torch.int32),
-                                          _p(workspace, torch.uint8), workspace.numel(), _stream()), "scream_render_depth")
+    call("scream_render_depth", src, s_row0, s_len, tgt, t_row0, t_len, n_pairs, max_s_len, max_t_len, src.shape[0], rot.reshape(V, 9),
+         V, w, rho, imgs, argmax, workspace, workspace.numel())
     return imgs, argmax
 
 
@@ -424,10 +454,8 @@ def render_depth_bwd(dimgs: torch.Tensor, argmax: torch.Tensor, src: torch.Tenso
     those of the render_depth call.  Returns dsrc [rows,3] (zero on rows outside every source cloud)."""
     n_pairs, V = s_row0.shape[0], rot.shape[0]
     dsrc = torch.zeros(src.shape[0], 3, device=src.device, dtype=torch.float32)
-    check(_lib.load().scream_render_depth_bwd(_p(src), _p(s_row0, torch.int32), _p(s_len, torch.int32), n_pairs, int(max_s_len),
-                                              src.shape[0], _p(rot.reshape(V, 9)), V, int(w), float(rho), _p(dimgs),
-                                              _p(argmax, torch.int32), _p(workspace, torch.uint8), workspace.numel(), _p(dsrc),
-                                              _stream()), "scream_render_depth_bwd")
+    call("scream_render_depth_bwd", src, s_row0, s_len, n_pairs, max_s_len, src.shape[0], rot.reshape(V, 9), V, w, rho, dimgs, argmax,
+         workspace, workspace.numel(), dsrc)
     return dsrc
 
 
@@ -437,15 +465,13 @@ def voxel_down_sample_packed(xyz: torch.Tensor, row0: torch.Tensor, length: torc
     Returns (out_xyz [rows,3], out_len int32 [B], out_count int32 [rows] or None), all on the device: cloud c's voxels are rows
     row0[c] .. + out_len[c] of out_xyz (the rows behind are not written), out_len[c] = -1 for a refused cloud.  No host sync."""
     n_clouds, rows, dev = row0.shape[0], xyz.shape[0], xyz.device
-    workspace = _workspace(_lib.load().scream_voxel_workspace_bytes, "scream_voxel_workspace_bytes", rows, n_clouds, device=dev)
+    workspace = _workspace("scream_voxel_workspace_bytes", rows, n_clouds, device=dev)
     out_xyz = torch.empty(max(rows, 1), 3, device=dev, dtype=torch.float32)
     out_len = torch.empty(max(n_clouds, 1), device=dev, dtype=torch.int32)
     out_count = torch.empty(max(rows, 1), device=dev, dtype=torch.int32) if want_counts else None
-    xyz_p = _p(xyz) if rows else out_xyz.data_ptr()  # an all-empty batch still reports its lengths
-    check(_lib.load().scream_voxel_down_sample(xyz_p, _p(row0, torch.int32), _p(length, torch.int32), n_clouds, int(max_len),
-                                               _p(voxel, torch.float64), _p(out_xyz), _p(out_len, torch.int32),
-                                               _p(out_count, torch.int32), _p(workspace, torch.uint8), workspace.numel(), _stream()),
-          "scream_voxel_down_sample")
+    # (an all-empty batch still reports its lengths)
+    call("scream_voxel_down_sample", xyz if rows else out_xyz, row0, length, n_clouds, max_len, voxel, out_xyz, out_len, out_count,
+         workspace, workspace.numel())
     return out_xyz[:rows], out_len[:n_clouds], (out_count[:rows] if want_counts else None)
 
 
@@ -454,16 +480,12 @@ def dsm_extract_packed(patch: torch.Tensor, p_row0: torch.Tensor, p_len: torch.T
     """scream_dsm_extract on packed rows: patch [P,3] / dem [D,3] fp32, the four int32 [B] arrays on the device.  Returns
     (out_xyz [D,3], out_idx int32 [D]) on the device; rows of dem outside every cloud are not written.  No host sync."""
     n_clouds, P, D, dev = p_row0.shape[0], patch.shape[0], dem.shape[0], dem.device
-    lib = _lib.load()
-    workspace = _workspace(lib.scream_dsm_workspace_bytes, "scream_dsm_workspace_bytes", P, n_clouds, int(max_p_len), device=dev)
+    workspace = _workspace("scream_dsm_workspace_bytes", P, n_clouds, max_p_len, device=dev)
     out_xyz = torch.empty(max(D, 1), 3, device=dev, dtype=torch.float32)
     out_idx = torch.empty(max(D, 1), device=dev, dtype=torch.int32)
-    patch_p = _p(patch) if P else _p(workspace, torch.uint8)  # a batch of empty windows: nothing is read through it
-    dem_p = _p(dem) if D else out_xyz.data_ptr()
-    check(lib.scream_dsm_extract(patch_p, _p(p_row0, torch.int32), _p(p_len, torch.int32), int(max_p_len), P, dem_p,
-                                 _p(d_row0, torch.int32), _p(d_len, torch.int32), int(max_d_len), D, n_clouds, float(radius),
-                                 _p(out_xyz), _p(out_idx, torch.int32), _p(workspace, torch.uint8), workspace.numel(), _stream()),
-          "scream_dsm_extract")
+    patch_p = patch if P else workspace.data_ptr()  # a batch of empty windows: nothing is read through it
+    call("scream_dsm_extract", patch_p, p_row0, p_len, max_p_len, P, dem if D else out_xyz, d_row0, d_len, max_d_len, D, n_clouds,
+         radius, out_xyz, out_idx, workspace, workspace.numel())
     return out_xyz[:D], out_idx[:D]
 
 
@@ -473,9 +495,7 @@ def dsm_dem_assemble_packed(dsm: torch.Tensor, dem: torch.Tensor, row0: torch.Te
     n_clouds, rows, dev = row0.shape[0], dem.shape[0], dem.device
     out = torch.empty(max(rows, 1), 6, device=dev, dtype=torch.float32)
     centre = torch.empty(max(n_clouds, 1), 3, device=dev, dtype=torch.float32)
-    check(_lib.load().scream_dsm_dem_assemble(_p(dsm) if rows else out.data_ptr(), _p(dem) if rows else out.data_ptr(),
-                                              _p(row0, torch.int32), _p(length, torch.int32), n_clouds, int(max_len), rows,
-                                              _p(out), _p(centre), _stream()), "scream_dsm_dem_assemble")
+    call("scream_dsm_dem_assemble", dsm if rows else out, dem if rows else out, row0, length, n_clouds, max_len, rows, out, centre)
     return out[:rows], centre[:n_clouds]
 
 
@@ -485,8 +505,7 @@ def _radius_args(src, s_row0, s_len, max_s_len, tgt, t_row0, t_len, max_t_len, T
     n_pairs, S, N = s_row0.shape[0], src.shape[0], tgt.shape[0]
     if T.shape[0] != n_pairs or T.numel() != n_pairs * 16:
         raise _lib.ScreamHipError("expected %d 4x4 transforms, got %s" % (n_pairs, tuple(T.shape)))
-    return (_p(src) if S else dummy, _p(s_row0, torch.int32), _p(s_len, torch.int32), int(max_s_len), S, _p(tgt) if N else dummy,
-            _p(t_row0, torch.int32), _p(t_len, torch.int32), int(max_t_len), N, _p(T, torch.float64), n_pairs, float(radius))
+    return (src if S else dummy, s_row0, s_len, max_s_len, S, tgt if N else dummy, t_row0, t_len, max_t_len, N, T, n_pairs, radius)
 
 
 def radius_count_packed(src: torch.Tensor, s_row0: torch.Tensor, s_len: torch.Tensor, max_s_len: int, tgt: torch.Tensor,
@@ -496,12 +515,10 @@ def radius_count_packed(src: torch.Tensor, s_row0: torch.Tensor, s_len: torch.Te
     device.  Returns (count int32 [S], workspace): count[row] = the number of target rows of the row's pair with d2 < radius^2
     (0 for rows outside every pair); the workspace holds the targets' cell lists for radius_pairs_packed.  No host sync."""
     n_pairs, S, N, dev = s_row0.shape[0], src.shape[0], tgt.shape[0], src.device
-    lib = _lib.load()
-    workspace = _workspace(lib.scream_radius_workspace_bytes, "scream_radius_workspace_bytes", N, n_pairs, int(max_t_len), device=dev)
+    workspace = _workspace("scream_radius_workspace_bytes", N, n_pairs, max_t_len, device=dev)
     count = torch.zeros(max(S, 1), device=dev, dtype=torch.int32)
     args = _radius_args(src, s_row0, s_len, max_s_len, tgt, t_row0, t_len, max_t_len, T, radius, count.data_ptr())
-    check(lib.scream_radius_count(*args, _p(count, torch.int32), _p(workspace, torch.uint8), workspace.numel(), _stream()),
-          "scream_radius_count")
+    call("scream_radius_count", *args, count, workspace, workspace.numel())
     return count[:S], workspace
 
 
@@ -517,8 +534,7 @@ def radius_pairs_packed(src: torch.Tensor, s_row0: torch.Tensor, s_len: torch.Te
         raise _lib.ScreamHipError("offset: expected %d elements, got %d" % (S + 1, offset.shape[0]))
     pair_j = torch.empty(max(int(total), 1), device=dev, dtype=torch.int32)
     args = _radius_args(src, s_row0, s_len, max_s_len, tgt, t_row0, t_len, max_t_len, T, radius, pair_j.data_ptr())
-    check(_lib.load().scream_radius_pairs(*args, _p(workspace, torch.uint8), workspace.numel(), int(K), _p(offset, torch.int64),
-                                          _p(pair_j, torch.int32), _stream()), "scream_radius_pairs")
+    call("scream_radius_pairs", *args, workspace, workspace.numel(), K, offset, pair_j)
     return pair_j[:int(total)]
 
 
@@ -535,8 +551,7 @@ def prep_pairs_packed(raw: torch.Tensor, raw_row0: torch.Tensor, raw_len: torch.
     if B < 1 or raw_row0.shape[0] != 2 * B or raw_len.shape[0] != 2 * B or cloud_row0.shape[0] != 2 * B or T.numel() != 16 * B or \
             perturb.numel() != 16 * B or sample_id.shape[0] != B:
         raise _lib.ScreamHipError("prep_pairs_packed: the per-pair arrays do not describe %d pairs" % B)
-    lib = _lib.load()
-    workspace = _workspace(lib.scream_prep_pairs_workspace_bytes, "scream_prep_pairs_workspace_bytes", rows, B, int(max_len), device=dev)
+    workspace = _workspace("scream_prep_pairs_workspace_bytes", rows, B, max_len, device=dev)
     xyz = torch.empty(int(rows_total), 3, device=dev, dtype=torch.float32)
     center = torch.empty(2 * B, 3, device=dev, dtype=torch.float32)
     rot = torch.empty(B, 3, 3, device=dev, dtype=torch.float32)
@@ -544,12 +559,9 @@ def prep_pairs_packed(raw: torch.Tensor, raw_row0: torch.Tensor, raw_len: torch.
     s = torch.empty(B, device=dev, dtype=torch.float64)
     c = torch.empty(B, 3, device=dev, dtype=torch.float64)
     T_aug = torch.empty(B, 4, 4, device=dev, dtype=torch.float64)
-    check(lib.scream_prep_pairs(_p(raw, raw.dtype), int(raw.dtype == torch.float64), rows, _p(raw_row0, torch.int32),
-                                _p(raw_len, torch.int32), int(max_len), _p(T, torch.float64), _p(perturb, torch.float64),
-                                _p(side, torch.int32), float(noise_std), int(seed) & (2 ** 64 - 1), _p(sample_id, torch.int64), int(mode),
-                                int(center_rule), _p(cloud_row0, torch.int32), B, int(rows_total), _p(xyz), _p(center), _p(rot),
-                                _p(trans), _p(s, torch.float64), _p(c, torch.float64), _p(T_aug, torch.float64),
-                                _p(workspace, torch.uint8), workspace.numel(), _stream()), "scream_prep_pairs")
+    call("scream_prep_pairs", _p(raw, raw.dtype), raw.dtype == torch.float64, rows, raw_row0, raw_len, max_len, T, perturb, side,
+         noise_std, int(seed) & (2 ** 64 - 1), sample_id, mode, center_rule, cloud_row0, B, rows_total, xyz, center, rot, trans, s, c,
+         T_aug, workspace, workspace.numel())
     return xyz, center, rot, trans, s, c, T_aug
 
 
@@ -562,8 +574,7 @@ def _l1_args(pred, xyz, rot, trans, target, cloud_row0, cloud_len, n_pairs, max_
             raise _lib.ScreamHipError("the packed target must have the prediction's shape %s, got %s" % (tuple(pred.shape), tuple(target.shape)))
     elif xyz.shape[0] < rows_src or rot.numel() != 9 * n_pairs or trans.numel() != 3 * n_pairs:
         raise _lib.ScreamHipError("l1_pairs: xyz / rot / trans do not describe %d pairs over %d source rows" % (n_pairs, rows_src))
-    return (_p(pred), _p(xyz), _p(rot), _p(trans), _p(target), _p(cloud_row0, torch.int32), _p(cloud_len, torch.int32), int(n_pairs),
-            int(max_len), rows_src)
+    return pred, xyz, rot, trans, target, cloud_row0, cloud_len, n_pairs, max_len, rows_src
 
 
 def l1_pairs_fwd(pred: torch.Tensor, xyz: Optional[torch.Tensor], rot: Optional[torch.Tensor], trans: Optional[torch.Tensor],
@@ -571,13 +582,12 @@ def l1_pairs_fwd(pred: torch.Tensor, xyz: Optional[torch.Tensor], rot: Optional[
                  max_len: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """scream_l1_pairs_fwd: (loss fp32 scalar, loss_pair float64 [B]) of the packed prediction [rows_src,3] against rot / trans
     applied to the packed xyz, or against the packed `target` [rows_src,3] when it is given.  No host sync."""
-    lib, dev = _lib.load(), pred.device
-    workspace = _workspace(lib.scream_l1_pairs_workspace_bytes, "scream_l1_pairs_workspace_bytes", int(n_pairs), int(max_len), device=dev)
+    dev = pred.device
+    workspace = _workspace("scream_l1_pairs_workspace_bytes", n_pairs, max_len, device=dev)
     loss_pair = torch.empty(n_pairs, device=dev, dtype=torch.float64)
     loss = torch.empty((), device=dev, dtype=torch.float32)
-    check(lib.scream_l1_pairs_fwd(*_l1_args(pred, xyz, rot, trans, target, cloud_row0, cloud_len, n_pairs, max_len),
-                                  _p(loss_pair, torch.float64), _p(loss), _p(workspace, torch.uint8), workspace.numel(), _stream()),
-          "scream_l1_pairs_fwd")
+    call("scream_l1_pairs_fwd", *_l1_args(pred, xyz, rot, trans, target, cloud_row0, cloud_len, n_pairs, max_len), loss_pair, loss,
+         workspace, workspace.numel())
     return loss, loss_pair
 
 
@@ -585,8 +595,7 @@ def l1_pairs_bwd(dout: torch.Tensor, pred: torch.Tensor, xyz, rot, trans, target
                  n_pairs: int, max_len: int) -> torch.Tensor:
     """scream_l1_pairs_bwd: dpred fp32 [rows_src,3] for the upstream gradient `dout` (one fp32 on the device)."""
     dpred = torch.empty_like(pred)
-    check(_lib.load().scream_l1_pairs_bwd(_p(dout), *_l1_args(pred, xyz, rot, trans, target, cloud_row0, cloud_len, n_pairs, max_len),
-                                          _p(dpred), _stream()), "scream_l1_pairs_bwd")
+    call("scream_l1_pairs_bwd", dout, *_l1_args(pred, xyz, rot, trans, target, cloud_row0, cloud_len, n_pairs, max_len), dpred)
     return dpred
 
 
@@ -595,18 +604,14 @@ def kabsch_corr(src, ref, src_row0, src_len, ref_row0, idx, valid, s, c) -> Tupl
     n_pairs = s.shape[0]
     T = torch.empty(n_pairs, 4, 4, device=src.device, dtype=torch.float32)
     n_corr = torch.empty(n_pairs, device=src.device, dtype=torch.int32)
-    check(_lib.load().scream_kabsch_corr(_p(src), _p(ref), _p(src_row0, torch.int32), _p(src_len, torch.int32),
-                                         _p(ref_row0, torch.int32), _p(idx, torch.int32), _p(valid, torch.uint8),
-                                         _p(s), _p(c), n_pairs, _p(T), _p(n_corr, torch.int32), _stream()),
-          "scream_kabsch_corr")
+    call("scream_kabsch_corr", src, ref, src_row0, src_len, ref_row0, idx, valid, s, c, n_pairs, T, n_corr)
     return T, n_corr
 
 
 def rigid_transform_3d_dense(A: torch.Tensor, B: torch.Tensor, w: Optional[torch.Tensor], thr: float) -> torch.Tensor:
     bs, K = A.shape[0], A.shape[1]
     T = torch.empty(bs, 4, 4, device=A.device, dtype=torch.float32)
-    check(_lib.load().scream_rigid_transform_3d(_p(A) if K else None, _p(B) if K else None, _p(w), float(thr), bs, K,
-                                                _p(T), _stream()), "scream_rigid_transform_3d")
+    call("scream_rigid_transform_3d", A if K else None, B if K else None, w, thr, bs, K, T)
     return T
 
 
@@ -614,8 +619,7 @@ def transformation_error_batched(T_pred: torch.Tensor, T_gt: torch.Tensor) -> Tu
     n = T_pred.shape[0]
     re = torch.empty(n, device=T_pred.device, dtype=torch.float32)
     te = torch.empty(n, device=T_pred.device, dtype=torch.float32)
-    check(_lib.load().scream_transformation_error(_p(T_pred), _p(T_gt), n, _p(re), _p(te), _stream()),
-          "scream_transformation_error")
+    call("scream_transformation_error", T_pred, T_gt, n, re, te)
     return re, te
 
 
@@ -624,9 +628,7 @@ def point_loss(src_pred: torch.Tensor, src: torch.Tensor, src_row0, src_len, rot
     src_pred / src packed [rows,3]; rot [B,3,3]; trans [B,3,1] or [B,3]."""
     B = rot.shape[0]
     out = torch.empty(B, device=src_pred.device, dtype=torch.float32)
-    check(_lib.load().scream_point_loss(_p(src_pred), _p(src), _p(src_row0, torch.int32), _p(src_len, torch.int32),
-                                        _p(rot.reshape(B, 9).contiguous()), _p(trans.reshape(B, 3).contiguous()), B, _p(out), _stream()),
-          "scream_point_loss")
+    call("scream_point_loss", src_pred, src, src_row0, src_len, rot.reshape(B, 9).contiguous(), trans.reshape(B, 3).contiguous(), B, out)
     return out
 
 
@@ -634,40 +636,36 @@ def icp_p2p(src, ref, src_row0, src_len, ref_row0, ref_len, s, c, T_init, max_sr
             max_corr_dist: float, max_iter: int = 30, rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, search: str = "grid"):
     """Batched point-to-point ICP (scream_icp_p2p).  Returns (T [n,4,4], fitness_rmse [n,2], iters int32 [n]).
     search="brute": the yardstick of the tests and of tools/icp_bench.py (scream_icp_p2p_brute_range), the same bits, slower."""
-    lib = _lib.load()
-    range_fn, range_name = _icp_range_fn(lib, search)
+    range_name = _icp_range_name(search)
     n_pairs = s.shape[0]
     dev = src.device
     T = T_init.detach().clone().contiguous().float()
     fr = torch.empty(n_pairs, 2, device=dev, dtype=torch.float32)
     iters = torch.empty(n_pairs, device=dev, dtype=torch.int32)
-    ws = _icp_workspace(lib, src, ref, n_pairs)
-    args = (_p(src), _p(ref), _p(src_row0, torch.int32), _p(src_len, torch.int32), _p(ref_row0, torch.int32),
-            _p(ref_len, torch.int32), _p(s), _p(c), n_pairs, max_src_len, max_ref_len, src.shape[0], ref.shape[0],
-            float(max_corr_dist), int(max_iter), float(rel_fitness), float(rel_rmse), _p(T), _p(fr), _p(iters, torch.int32))
+    ws = _icp_workspace(src, ref, n_pairs)
+    args = (src, ref, src_row0, src_len, ref_row0, ref_len, s, c, n_pairs, max_src_len, max_ref_len, src.shape[0], ref.shape[0],
+            max_corr_dist, max_iter, rel_fitness, rel_rmse, T, fr, iters)
     if search == "grid":
-        check(lib.scream_icp_p2p(*args, ws.data_ptr(), ws.numel(), _stream()), "scream_icp_p2p")
+        call("scream_icp_p2p", *args, ws, ws.numel())
     else:  # the whole schedule, as scream_icp_p2p enqueues it
-        check(range_fn(*args, 0, int(max_iter) + 2, None, ws.data_ptr(), ws.numel(), _stream()), range_name)
+        call(range_name, *args, 0, int(max_iter) + 2, None, ws, ws.numel())
     return T, fr, iters
 
 
-def _icp_range_fn(lib, search: str):
-    """(C function, its name) that enqueues a piece of an ICP run with this search."""
+def _icp_range_name(search: str) -> str:
+    """The entry point that enqueues a piece of an ICP run with this search."""
     if search not in ("grid", "brute"):
         raise ValueError('search must be "grid" or "brute", not %r' % (search,))
-    name = "scream_icp_p2p_range" if search == "grid" else "scream_icp_p2p_brute_range"
-    return getattr(lib, name), name
+    return "scream_icp_p2p_range" if search == "grid" else "scream_icp_p2p_brute_range"
 
 
-def _icp_workspace(lib, src, ref, n_pairs: int) -> torch.Tensor:
-    return _workspace(lib.scream_icp_workspace_bytes, "scream_icp_workspace_bytes", src.shape[0], ref.shape[0], n_pairs, device=src.device)
+def _icp_workspace(src, ref, n_pairs: int) -> torch.Tensor:
+    return _workspace("scream_icp_workspace_bytes", src.shape[0], ref.shape[0], n_pairs, device=src.device)
 
 
 def icp_raw_workspace(src_rows: int, tgt_rows: int, n_pairs: int, device) -> torch.Tensor:
     """Scratch of scream_icp_raw_range / scream_icp_raw_nn (scream_amd/rawicp.py)."""
-    return _workspace(_lib.load().scream_icp_raw_workspace_bytes, "scream_icp_raw_workspace_bytes", src_rows, tgt_rows, n_pairs,
-                      device=device, floor=256)
+    return _workspace("scream_icp_raw_workspace_bytes", src_rows, tgt_rows, n_pairs, device=device, floor=256)
 
 
 ICP_ASYNC_ITERS = 64  # schedules up to this many iterations are enqueued whole (icp_p2p); longer ones in pieces (IcpRun)
@@ -727,8 +725,7 @@ class IcpRun(PiecewiseRun):
 
     def __init__(self, src, ref, src_row0, src_len, ref_row0, ref_len, s, c, T_init, max_src_len: int, max_ref_len: int,
                  max_corr_dist: float, max_iter: int, rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, search: str = "grid"):
-        self.lib = _lib.load()
-        self._fn, self._fn_name = _icp_range_fn(self.lib, search)  # one search for the whole run
+        self._entry = _icp_range_name(search)  # one search for the whole run
         n = s.shape[0]
         dev = src.device
         self.max_iter = int(max_iter)
@@ -736,18 +733,14 @@ class IcpRun(PiecewiseRun):
         self.T = T_init.detach().clone().contiguous().float()
         self.fr = torch.empty(n, 2, device=dev, dtype=torch.float32)
         self.iters = torch.empty(n, device=dev, dtype=torch.int32)
-        self.ws = _icp_workspace(self.lib, src, ref, n)
-        self._keep = (src, ref, src_row0, src_len, ref_row0, ref_len, s, c)
-        self._args = (_p(src), _p(ref), _p(src_row0, torch.int32), _p(src_len, torch.int32), _p(ref_row0, torch.int32),
-                      _p(ref_len, torch.int32), _p(s), _p(c), n, int(max_src_len), int(max_ref_len), src.shape[0], ref.shape[0],
-                      float(max_corr_dist), int(max_iter), float(rel_fitness), float(rel_rmse), _p(self.T), _p(self.fr),
-                      _p(self.iters, torch.int32))
+        self.ws = _icp_workspace(src, ref, n)
+        self._args = (src, ref, src_row0, src_len, ref_row0, ref_len, s, c, n, max_src_len, max_ref_len, src.shape[0], ref.shape[0],
+                      max_corr_dist, max_iter, rel_fitness, rel_rmse, self.T, self.fr, self.iters)
 
     launches_left = PiecewiseRun.steps_left
 
     def _enqueue(self, begin: int, end: int) -> None:
-        check(self._fn(*self._args, begin, end, _p(self.flags, torch.int32), self.ws.data_ptr(), self.ws.numel(), _stream()),
-              self._fn_name)
+        call(self._entry, *self._args, begin, end, self.flags, self.ws, self.ws.numel())
 
 
 # ---- the adversarial loss (csrc/gan.hip): contiguous NCHW fp32 tensors, torch's [Cout,Cin,4,4] weights
@@ -759,8 +752,7 @@ def _conv_out(h: int, w: int, stride: int) -> Tuple[int, int]:
 
 
 def _gan_conv_ws(mode: int, n, cin, cout, h, w, stride, device) -> torch.Tensor:
-    return _workspace(_lib.load().scream_gan_conv_workspace_bytes, "scream_gan_conv_workspace_bytes", mode, n, cin, cout, h, w, stride,
-                      device=device)
+    return _workspace("scream_gan_conv_workspace_bytes", mode, n, cin, cout, h, w, stride, device=device)
 
 
 def gan_conv_fwd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], stride: int, leaky: bool = False) -> torch.Tensor:
@@ -770,8 +762,7 @@ def gan_conv_fwd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
     ho, wo = _conv_out(h, w, stride)
     y = torch.empty(n, cout, ho, wo, device=x.device, dtype=torch.float32)
     ws = _gan_conv_ws(GAN_FWD, n, cin, cout, h, w, stride, x.device)
-    check(_lib.load().scream_gan_conv_fwd(_p(x), _p(weight), _p(bias), n, cin, cout, h, w, stride, int(leaky), _p(y), ws.data_ptr(),
-                                          ws.numel(), _stream()), "scream_gan_conv_fwd")
+    call("scream_gan_conv_fwd", x, weight, bias, n, cin, cout, h, w, stride, leaky, y, ws, ws.numel())
     return y
 
 
@@ -781,8 +772,7 @@ def gan_conv_dgrad(dy: torch.Tensor, weight: torch.Tensor, h: int, w: int, strid
     cin = weight.shape[1]
     dx = torch.empty(n, cin, h, w, device=dy.device, dtype=torch.float32)
     ws = _gan_conv_ws(GAN_DGRAD, n, cin, cout, h, w, stride, dy.device)
-    check(_lib.load().scream_gan_conv_dgrad(_p(dy), _p(weight), _p(mask), n, cin, cout, h, w, stride, _p(dx), ws.data_ptr(), ws.numel(),
-                                            _stream()), "scream_gan_conv_dgrad")
+    call("scream_gan_conv_dgrad", dy, weight, mask, n, cin, cout, h, w, stride, dx, ws, ws.numel())
     return dx
 
 
@@ -793,8 +783,7 @@ def gan_conv_wgrad(x: torch.Tensor, dy: torch.Tensor, stride: int, want_bias: bo
     dw = torch.empty(cout, cin, 4, 4, device=x.device, dtype=torch.float32)
     db = torch.empty(cout, device=x.device, dtype=torch.float32) if want_bias else None
     ws = _gan_conv_ws(GAN_WGRAD, n, cin, cout, h, w, stride, x.device)
-    check(_lib.load().scream_gan_conv_wgrad(_p(x), _p(dy), n, cin, cout, h, w, stride, _p(dw), _p(db), ws.data_ptr(), ws.numel(),
-                                            _stream()), "scream_gan_conv_wgrad")
+    call("scream_gan_conv_wgrad", x, dy, n, cin, cout, h, w, stride, dw, db, ws, ws.numel())
     return dw, db
 
 
@@ -808,9 +797,7 @@ def gan_bn_fwd(x: torch.Tensor, gamma, beta, running_mean, running_var, num_batc
     y = torch.empty_like(x)
     mean = torch.empty(c, device=x.device, dtype=torch.float32)
     invstd = torch.empty(c, device=x.device, dtype=torch.float32)
-    check(_lib.load().scream_gan_bn_fwd(_p(x), _p(gamma), _p(beta), _p(running_mean), _p(running_var),
-                                        _p(num_batches_tracked, torch.int64), n, c, hw, int(training), _p(y), _p(mean), _p(invstd),
-                                        _stream()), "scream_gan_bn_fwd")
+    call("scream_gan_bn_fwd", x, gamma, beta, running_mean, running_var, num_batches_tracked, n, c, hw, training, y, mean, invstd)
     return y, mean, invstd
 
 
@@ -820,33 +807,31 @@ def gan_bn_bwd(dy: torch.Tensor, y: torch.Tensor, x: torch.Tensor, gamma, mean, 
     dx = torch.empty_like(x)
     dgamma, dbeta = torch.empty_like(mean), torch.empty_like(mean)
     sums = torch.empty(2 * c, device=x.device, dtype=torch.float64)
-    check(_lib.load().scream_gan_bn_bwd(_p(dy), _p(y), _p(x), _p(gamma), _p(mean), _p(invstd), n, c, x.shape[2] * x.shape[3],
-                                        _p(sums, torch.float64), _p(dx), _p(dgamma), _p(dbeta), _stream()), "scream_gan_bn_bwd")
+    call("scream_gan_bn_bwd", dy, y, x, gamma, mean, invstd, n, c, x.shape[2] * x.shape[3], sums, dx, dgamma, dbeta)
     return dx, dgamma, dbeta
 
 
 def gan_loss_g(logits: torch.Tensor) -> torch.Tensor:
     loss = torch.empty((), device=logits.device, dtype=torch.float32)
-    check(_lib.load().scream_gan_loss_g(_p(logits), logits.numel(), _p(loss), _stream()), "scream_gan_loss_g")
+    call("scream_gan_loss_g", logits, logits.numel(), loss)
     return loss
 
 
 def gan_loss_g_bwd(dout: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
     d = torch.empty_like(like)
-    check(_lib.load().scream_gan_loss_g_bwd(_p(dout), d.numel(), _p(d), _stream()), "scream_gan_loss_g_bwd")
+    call("scream_gan_loss_g_bwd", dout, d.numel(), d)
     return d
 
 
 def gan_loss_d(real: torch.Tensor, fake: torch.Tensor) -> torch.Tensor:
     loss = torch.empty((), device=real.device, dtype=torch.float32)
-    check(_lib.load().scream_gan_loss_d(_p(real), real.numel(), _p(fake), fake.numel(), _p(loss), _stream()), "scream_gan_loss_d")
+    call("scream_gan_loss_d", real, real.numel(), fake, fake.numel(), loss)
     return loss
 
 
 def gan_loss_d_bwd(dout: torch.Tensor, real: torch.Tensor, fake: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     dr, df = torch.empty_like(real), torch.empty_like(fake)
-    check(_lib.load().scream_gan_loss_d_bwd(_p(dout), _p(real), real.numel(), _p(fake), fake.numel(), _p(dr), _p(df), _stream()),
-          "scream_gan_loss_d_bwd")
+    call("scream_gan_loss_d_bwd", dout, real, real.numel(), fake, fake.numel(), dr, df)
     return dr, df
 
 
@@ -854,9 +839,7 @@ def pairs_transform(xyz: torch.Tensor, rot: torch.Tensor, trans: torch.Tensor, t
                     rows_src: int) -> torch.Tensor:
     """scream_pairs_transform: R_p x + t_p on the packed source rows of every pair, one launch -> [rows_src,3]."""
     out = torch.empty(rows_src, 3, device=xyz.device, dtype=torch.float32)
-    check(_lib.load().scream_pairs_transform(_p(xyz), _p(rot.reshape(n_pairs, 9)), _p(trans.reshape(n_pairs, 3)),
-                                             _p(tile_cloud, torch.int32), int(n_pairs), int(rows_src), _p(out), _stream()),
-          "scream_pairs_transform")
+    call("scream_pairs_transform", xyz, rot.reshape(n_pairs, 9), trans.reshape(n_pairs, 3), tile_cloud, n_pairs, rows_src, out)
     return out
 
 
@@ -881,7 +864,7 @@ def gan_params(weights, b0, b4, gammas, betas, running_means, running_vars, nbts
 
 
 def gan_workspace(n: int, cin: int, ndf: int, h: int, w: int, device) -> torch.Tensor:
-    return _workspace(_lib.load().scream_gan_workspace_bytes, "scream_gan_workspace_bytes", n, cin, ndf, h, w, device=device)
+    return _workspace("scream_gan_workspace_bytes", n, cin, ndf, h, w, device=device)
 
 
 def gan_forward(x: torch.Tensor, params, ndf: int, training: bool, workspace: torch.Tensor) -> torch.Tensor:
@@ -890,8 +873,7 @@ def gan_forward(x: torch.Tensor, params, ndf: int, training: bool, workspace: to
     for s in (2, 2, 2, 1, 1):
         h, w = _conv_out(h, w, s)
     logits = torch.empty(n, 1, h, w, device=x.device, dtype=torch.float32)
-    check(_lib.load().scream_gan_forward(_p(x), C.byref(params), n, cin, int(ndf), x.shape[2], x.shape[3], int(training), _p(logits),
-                                         workspace.data_ptr(), workspace.numel(), _stream()), "scream_gan_forward")
+    call("scream_gan_forward", x, params, n, cin, ndf, x.shape[2], x.shape[3], training, logits, workspace, workspace.numel())
     return logits
 
 
@@ -902,8 +884,7 @@ def gan_backward(dlogits: torch.Tensor, x: torch.Tensor, params, ndf: int, works
     dx = torch.empty_like(x) if want_dx else None
     g = None
     if grads is not None:
-        g = C.byref(_gan_struct(_lib.GanGradsT, dict(w=[_p(t) for t in grads[0:5]], b0=_p(grads[5]), b4=_p(grads[6]),
-                                                     gamma=[_p(t) for t in grads[7:10]], beta=[_p(t) for t in grads[10:13]])))
-    check(_lib.load().scream_gan_backward(_p(dlogits), _p(x), C.byref(params), n, cin, int(ndf), h, w, workspace.data_ptr(),
-                                          workspace.numel(), _p(dx), g, _stream()), "scream_gan_backward")
+        g = _gan_struct(_lib.GanGradsT, dict(w=[_p(t) for t in grads[0:5]], b0=_p(grads[5]), b4=_p(grads[6]),
+                                             gamma=[_p(t) for t in grads[7:10]], beta=[_p(t) for t in grads[10:13]]))
+    call("scream_gan_backward", dlogits, x, params, n, cin, ndf, h, w, workspace, workspace.numel(), dx, g)
     return dx

@@ -25,7 +25,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 
 __all__ = ["FusedAdam", "ADAM_CHUNK"]
 
@@ -143,9 +143,9 @@ class _Group:
             if slot[2] is None:
                 slot[2] = torch.cuda.Event()
             slot[2].record(stream)
-            _lib.check(_lib.load().scream_adam_step(self.table.data_ptr(), T, chunks.data_ptr(), n_chunks, self.scalars.data_ptr(),
-                                                    _scalar_ptr(grad_scale, dev, "grad_scale"), _scalar_ptr(found_inf, dev, "found_inf"),
-                                                    lr, float(betas[0]), float(betas[1]), eps, stream.cuda_stream), "scream_adam_step")
+            # (the table is a row of int64 per tensor behind a `const void*`: it goes as an address)
+            ops.call("scream_adam_step", self.table.data_ptr(), T, chunks, n_chunks, self.scalars, _scalar_ptr(grad_scale, dev, "grad_scale"),
+                     _scalar_ptr(found_inf, dev, "found_inf"), lr, betas[0], betas[1], eps, stream.cuda_stream)
         return [params[i] for i in active]
 
 

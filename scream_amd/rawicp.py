@@ -19,10 +19,9 @@ from typing import Sequence
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import ScreamHipError, check
+from ._lib import ScreamHipError
 from .clouds import PackedPairs, check_clouds, pose_stack
-from .ops import PiecewiseRun, _p, _stream, icp_raw_workspace
+from .ops import PiecewiseRun, _p, call, icp_raw_workspace
 
 __all__ = ["icp_raw_batch", "raw_nn_batch", "RawIcpRun"]
 
@@ -85,7 +84,6 @@ class RawIcpRun(PiecewiseRun):
 
     def __init__(self, srcs, tgts, T_inits, max_corr_dist: float = 0.2, max_iter: int = 50000, rel_fitness: float = 1e-6,
                  rel_rmse: float = 1e-6):
-        self.lib = _lib.load()
         self.pk = _RawClouds(srcs, tgts)
         n, dev = self.pk.n, self.pk.dev
         self.max_iter, self.iterations = int(max_iter), 0
@@ -95,14 +93,12 @@ class RawIcpRun(PiecewiseRun):
         self.T = _poses(T_inits, n, dev)
         self.fitness_rmse = torch.zeros(max(n, 1), 2, device=dev, dtype=torch.float64)[:n]
         self.iters = torch.zeros(max(n, 1), device=dev, dtype=torch.int32)[:n]
-        self._tail = (float(max_corr_dist), self.max_iter, float(rel_fitness), float(rel_rmse), _p(self.T, torch.float64),
-                      _p(self.fitness_rmse, torch.float64), _p(self.iters, torch.int32))
+        self._tail = (max_corr_dist, self.max_iter, rel_fitness, rel_rmse, self.T, self.fitness_rmse, self.iters)
 
     iterations_left = PiecewiseRun.steps_left
 
     def _enqueue(self, begin: int, end: int) -> None:
-        check(self.lib.scream_icp_raw_range(*self.pk.head_args(), *self._tail, begin, end, _p(self.flags, torch.int32),
-                                            self.pk.ws.data_ptr(), self.pk.ws.numel(), _stream()), "scream_icp_raw_range")
+        call("scream_icp_raw_range", *self.pk.head_args(), *self._tail, begin, end, self.flags, self.pk.ws, self.pk.ws.numel())
         self.iterations += end - begin
 
 
@@ -133,8 +129,7 @@ def raw_nn_batch(srcs, tgts, Ts, radius: float, strict: bool = True):
     idx = torch.full((max(pk.s_rows, 1),), -1, device=dev, dtype=torch.int32)
     d2 = torch.full((max(pk.s_rows, 1),), float("inf"), device=dev, dtype=torch.float64)
     status = torch.zeros(n, device=dev, dtype=torch.int32)
-    check(_lib.load().scream_icp_raw_nn(*pk.head_args(), float(radius), _p(T, torch.float64), _p(idx, torch.int32), _p(d2, torch.float64),
-                                        _p(status, torch.int32), pk.ws.data_ptr(), pk.ws.numel(), _stream()), "scream_icp_raw_nn")
+    call("scream_icp_raw_nn", *pk.head_args(), radius, T, idx, d2, status, pk.ws, pk.ws.numel())
     status = status.cpu()
     out_i, out_d = pk.split_src(idx, clone=False), pk.split_src(d2, clone=False)
     if strict:

@@ -40,8 +40,8 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib, ops
-from ._lib import SPLIT_BF3, check
-from .ops import EPI_BIAS_RELU, EPI_ELU1, EPI_NONE, EPI_RELU, D_MODEL, _p, _stream, _workspace
+from ._lib import SPLIT_BF3
+from .ops import EPI_BIAS_RELU, EPI_ELU1, EPI_NONE, EPI_RELU, D_MODEL, _p, _workspace, call
 from .packing import PackedBatch
 
 
@@ -52,7 +52,7 @@ def _ptr(t: torch.Tensor, col: int = 0) -> int:
 def transpose(W: torch.Tensor) -> torch.Tensor:
     R, C_ = W.shape
     out = torch.empty(C_, R, device=W.device, dtype=torch.float32)
-    check(_lib.load().scream_transpose_f32(_p(W), R, C_, _p(out), _stream()), "scream_transpose_f32")
+    call("scream_transpose_f32", W, R, C_, out)
     return out
 
 
@@ -72,13 +72,11 @@ class Gemms:
         return self._wgrad(dY, X, dW, colsum, accumulate, ldy, ldx, rows)
 
     def _wgrad(self, dY, X, dW, colsum, accumulate, ldy, ldx, rows, *extra) -> torch.Tensor:
-        lib = _lib.load()
         rows = dY.shape[0] if rows is None else rows
         N, K = dY.shape[1], X.shape[1]
-        ws = _workspace(getattr(lib, self.wgrad_sizer), self.wgrad_sizer, rows, N, K, device=dY.device)
-        check(getattr(lib, self.wgrad_entry)(dY.data_ptr(), dY.stride(0) if ldy is None else ldy, X.data_ptr(),
-                                             X.stride(0) if ldx is None else ldx, rows, N, K, _p(dW), int(accumulate), _p(colsum),
-                                             *extra, ws.data_ptr(), ws.numel(), _stream()), self.wgrad_entry)
+        ws = _workspace(self.wgrad_sizer, rows, N, K, device=dY.device)
+        call(self.wgrad_entry, dY.data_ptr(), dY.stride(0) if ldy is None else ldy, X.data_ptr(), X.stride(0) if ldx is None else ldx,
+             rows, N, K, dW, accumulate, colsum, *extra, ws, ws.numel())
         return dW
 
 
@@ -144,44 +142,37 @@ def ln_fwd(a: torch.Tensor, b, gamma, beta, out: torch.Tensor = None):
     y = torch.empty(rows, D_MODEL, device=a.device, dtype=torch.float32) if out is None else out
     mean = torch.empty(rows, device=a.device, dtype=torch.float32)
     rstd = torch.empty(rows, device=a.device, dtype=torch.float32)
-    check(_lib.load().scream_ln_fwd(_p(a), _p(b), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), rows, _stream()), "scream_ln_fwd")
+    call("scream_ln_fwd", a, b, gamma, beta, y, mean, rstd, rows)
     return y, mean, rstd
 
 
 def ln_bwd(dy, a, b, mean, rstd, gamma, dz, dsum, dgamma, dbeta, accumulate: bool = False):
-    lib = _lib.load()
     rows = dy.shape[0]
-    ws = _workspace(lib.scream_ln_bwd_workspace_bytes, "scream_ln_bwd_workspace_bytes", rows, device=dy.device)
-    check(lib.scream_ln_bwd(_p(dy), _p(a), _p(b), _p(mean), _p(rstd), _p(gamma), _p(dz), _p(dsum), _p(dgamma), _p(dbeta),
-                            int(accumulate), rows, ws.data_ptr(), ws.numel(), _stream()), "scream_ln_bwd")
+    ws = _workspace("scream_ln_bwd_workspace_bytes", rows, device=dy.device)
+    call("scream_ln_bwd", dy, a, b, mean, rstd, gamma, dz, dsum, dgamma, dbeta, accumulate, rows, ws, ws.numel())
     return dz
 
 
 def attn_bwd(Qf, ldq, q_rows, q_row_base, O, dO, Kf, Vf, ldkv, kv_rows, kv_row_base, kv, batch: PackedBatch,
              q_cloud_begin, n_q, kv_cloud_offset, dq, lddq, dk, dv, lddkv):
     """Pointer-level wrapper of scream_attn_bwd: Qf / Kf / Vf / dq / dk / dv are device addresses (column offsets applied)."""
-    lib = _lib.load()
-    ws = _workspace(lib.scream_attn_bwd_workspace_bytes, "scream_attn_bwd_workspace_bytes", n_q, batch.max_chunks, device=O.device)
-    check(lib.scream_attn_bwd(Qf, ldq, q_rows, q_row_base, _p(O), _p(dO), Kf, Vf, ldkv, kv_rows, kv_row_base, _p(kv),
-                              _p(batch.tile_cloud, torch.int32), _p(batch.cloud_row0, torch.int32), _p(batch.cloud_len, torch.int32),
-                              q_cloud_begin, n_q, kv_cloud_offset, batch.max_chunks, dq, lddq, dk, dv, lddkv,
-                              ws.data_ptr(), ws.numel(), _stream()), "scream_attn_bwd")
+    ws = _workspace("scream_attn_bwd_workspace_bytes", n_q, batch.max_chunks, device=O.device)
+    call("scream_attn_bwd", Qf, ldq, q_rows, q_row_base, O, dO, Kf, Vf, ldkv, kv_rows, kv_row_base, kv, batch.tile_cloud, batch.cloud_row0,
+         batch.cloud_len, q_cloud_begin, n_q, kv_cloud_offset, batch.max_chunks, dq, lddq, dk, dv, lddkv, ws, ws.numel())
 
 
 def relu_bwd(dy, y):
-    check(_lib.load().scream_relu_bwd(_p(dy), _p(y), dy.numel(), _stream()), "scream_relu_bwd")
+    call("scream_relu_bwd", dy, y, dy.numel())
 
 
 def add_(y, x):
-    check(_lib.load().scream_add_f32(_p(y), _p(x), y.numel(), _stream()), "scream_add_f32")
+    call("scream_add_f32", y, x, y.numel())
 
 
 def grad3(w, s, dW, transpose_w: bool, col_w=None, col_s=None, center=None, tile_cloud=None):
-    lib = _lib.load()
     rows = w.shape[0]
-    ws = _workspace(lib.scream_grad3_workspace_bytes, "scream_grad3_workspace_bytes", rows, device=w.device)
-    check(lib.scream_grad3(_p(w), _p(s), _p(center), _p(tile_cloud, torch.int32), rows, _p(dW), int(transpose_w), _p(col_w),
-                           _p(col_s), 0, ws.data_ptr(), ws.numel(), _stream()), "scream_grad3")
+    ws = _workspace("scream_grad3_workspace_bytes", rows, device=w.device)
+    call("scream_grad3", w, s, center, tile_cloud, rows, dW, transpose_w, col_w, col_s, 0, ws, ws.numel())
 
 
 class _Layer:
@@ -308,8 +299,7 @@ def forward_saving(net, batch: PackedBatch):
     z0 = torch.empty(rt, D_MODEL, device=dev, dtype=torch.float32)
     emb_w = _w(P, "embedding.weight")[:, :, 0].contiguous()
     dim_t = pe_dim_t().to(dev)
-    check(_lib.load().scream_pe_embed(_p(batch.xyz), _p(batch.tile_cloud, torch.int32), _p(batch.center), _p(dim_t), _p(emb_w),
-                                      _p(_w(P, "embedding.bias")), _p(z0), rt, _stream()), "scream_pe_embed")
+    call("scream_pe_embed", batch.xyz, batch.tile_cloud, batch.center, dim_t, emb_w, _w(P, "embedding.bias"), z0, rt)
     f, *s0 = ln_fwd(z0, None, _w(P, "pre_norm.weight"), _w(P, "pre_norm.bias"))
     layers = []
     for passes in _stem_passes(net, batch):
@@ -342,7 +332,7 @@ def backward(net, batch: PackedBatch, saved, dout: torch.Tensor) -> List[torch.T
     h1, h2 = saved["h1"], saved["h2"]
     grad3(h2, dout, G["coor_mlp.4.weight"], False, col_s=G["coor_mlp.4.bias"])
     dh2 = torch.empty(rs, D_MODEL, device=dev, dtype=torch.float32)
-    check(_lib.load().scream_coor_head_bwd(_p(dout), _p(_coor_w(P, 4)), _p(h2), _p(dh2), rs, _stream()), "scream_coor_head_bwd")
+    call("scream_coor_head_bwd", dout, _coor_w(P, 4), h2, dh2, rs)
     mm.wgrad(dh2, h1, G["coor_mlp.2.weight"], G["coor_mlp.2.bias"])
     dh1 = mm.dgrad(dh2, _coor_w(P, 2))
     relu_bwd(dh1, h1)

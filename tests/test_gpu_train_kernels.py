@@ -119,7 +119,7 @@ def test_coor_head_bwd_against_float64(rows):
 # ------------------------------------------------------------------------------------- the 3-wide weight gradients
 def grad3(w, s, dW, transpose_w, col_w=None, col_s=None, center=None, tile_cloud=None, accumulate=False):
     lib, rows = _lib.load(), w.shape[0]
-    ws = ops._workspace(lib.scream_grad3_workspace_bytes, "scream_grad3_workspace_bytes", rows, device=w.device)
+    ws = ops._workspace("scream_grad3_workspace_bytes", rows, device=w.device)
     check(lib.scream_grad3(_p(w), _p(s), _p(center), _p(tile_cloud, torch.int32), rows, _p(dW), int(transpose_w), _p(col_w),
                            _p(col_s), int(accumulate), ws.data_ptr(), ws.numel(), _stream()), "scream_grad3")
 

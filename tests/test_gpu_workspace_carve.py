@@ -54,9 +54,9 @@ class Exact:
                     return fn(*args)
                 return call
 
-        def workspace(lib_fn, name, *args, device, floor=16):
+        def workspace(name, *args, device, floor=16):
             assert me.big is None, "one workspace per run"
-            me.need = lib_fn(*args) - me.short
+            me.need = getattr(me.lib, name)(*args) - me.short
             assert me.need >= floor, (name, args, me.need)
             me.big = torch.full((MARGIN + me.need + MARGIN,), me.fill, dtype=torch.uint8, device=device)
             return me.big[MARGIN:MARGIN + me.need]

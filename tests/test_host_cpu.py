@@ -37,6 +37,120 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.scream_version()
 
 
+def test_signatures_are_the_headers_prototypes():
+    """_lib.SIGNATURES is parsed from include/scream_hip.h: one entry per declared function, the odd return and argument types
+    pinned here, every pointer's pointee and every parameter's name kept beside it."""
+    import ctypes as C
+    S, P = _lib.SIGNATURES, _lib.PROTOTYPES
+    assert len(S) == len(P) == len(_header_functions())
+    assert S["scream_version"] == (C.c_char_p, []) and S["scream_abi_version"] == (C.c_int, [])
+    assert S["scream_trace_destroy"] == (None, [C.c_void_p]) and S["scream_trace_create"] == (C.c_void_p, [C.c_int32])
+    sizers = [n for n in S if n.endswith("_bytes")]
+    assert len(sizers) == 20 and all(S[n][0] is C.c_int64 for n in sizers)
+    assert sorted(n for n in S if S[n][0] is C.c_int64) == sorted(sizers)
+    prep = P["scream_prep_pairs"]
+    assert prep.argtypes[prep.params.index("seed")] is C.c_uint64 and prep.argtypes.count(C.c_uint64) == 1
+    adam = P["scream_adam_step"]
+    assert adam.params[7:11] == ("lr", "beta1", "beta2", "eps") and adam.argtypes[7:11] == (C.c_double,) * 4
+    assert adam.argtypes.count(C.c_double) == 4
+    for name, param, cls in (("scream_pack_tail", "exps", _lib.TailExpsT), ("scream_layer_tail_f32", "exps", _lib.TailExpsT),
+                             ("scream_forward", "model", _lib.ModelT), ("scream_forward", "batch", _lib.BatchT),
+                             ("scream_gan_forward", "params", _lib.GanParamsT), ("scream_gan_backward", "params", _lib.GanParamsT),
+                             ("scream_gan_backward", "grads", _lib.GanGradsT)):
+        i = P[name].params.index(param)
+        assert P[name].argtypes[i] is C.POINTER(cls) and P[name].pointees[i] is cls, (name, param)
+    assert sum(isinstance(t, type) and issubclass(t, C.Structure) for p in P.values() for t in p.pointees) == 7
+    nn = dict(zip(P["scream_nn_search"].params, P["scream_nn_search"].pointees))
+    assert [k for k, v in nn.items() if v == "int32_t"] == ["q_row0", "q_len", "r_row0", "r_len", "idx"]  # four inputs and idx
+    assert nn["keys"] == "uint64_t" and nn["valid"] == "uint8_t" and nn["thresh"] is None and nn["stream"] == "void"
+    radius = P["scream_radius_count"]
+    assert radius.pointees[radius.params.index("T")] == "double"
+    for name, p in P.items():
+        assert len(p.argtypes) == len(p.params) == len(p.pointees) == len(S[name][1]), name
+        assert all((t is C.c_void_p) == isinstance(pointee, str) for t, pointee in zip(p.argtypes, p.pointees)), name
+        if p.restype is C.c_int and name != "scream_abi_version" and not name.startswith("scream_trace_"):
+            assert p.stream and p.params[-1] == "stream" and p.argtypes[-1] is C.c_void_p, name
+        else:
+            assert not p.stream, name
+    assert sorted(n for n, p in P.items() if p.restype is C.c_int and not p.stream) == [
+        "scream_abi_version", "scream_trace_read", "scream_trace_read_starts", "scream_trace_reset"]
+
+
+def test_the_header_parser_refuses_what_it_cannot_read():
+    good = "int scream_a(const float* x, int64_t n, void* stream);\nint64_t scream_a_bytes(int32_t n);\n"
+    assert list(_lib.parse_header(good)) == ["scream_a", "scream_a_bytes"]
+    for bad in ("int scream_b(const float* x, int64_t n, void* stream)\nint scream_c(void);",  # a lost semicolon
+                "int scream_b(const float* x, long n);", "int scream_b(const float x[3]);", "unsigned scream_b(void);",
+                "int scream_b(float* const* x);", good + "int scream_a(void);",
+                "int scream_b(const scream_zzz_t* z, void* stream);"):
+        with pytest.raises(ValueError, match="scream_"):
+            _lib.parse_header(good + bad)
+
+
+class _RecordingLib:
+    """Stands in for the loaded library: every function records its arguments and answers `rc`."""
+
+    def __init__(self, rc=0):
+        self.rc, self.calls = rc, []
+
+    def __getattr__(self, name):
+        return lambda *args: (self.calls.append((name, args)), self.rc)[1]
+
+
+def test_call_marshals_by_the_header_without_a_gpu(monkeypatch):
+    """ops.call on the host: a CPU tensor is refused before the library is entered; a refused status and a refused size raise
+    with the function's name while the raw functions keep returning their codes; the argument count is checked against the
+    prototype; the current stream is appended only when it was left out; a structure goes by reference."""
+    import ctypes as C
+    from scream_amd import ops
+    lib = _lib.load()
+    rec = _RecordingLib()
+    monkeypatch.setattr(_lib, "load", lambda: rec)
+    monkeypatch.setattr(ops, "_stream", lambda: 1234)
+    x = torch.zeros(4)
+    with pytest.raises(_lib.ScreamHipError, match=r"scream_add_f32\(x\).*no CPU path"):
+        ops.call("scream_add_f32", None, x, 4)
+    assert rec.calls == []
+    ops.call("scream_add_f32", None, 4096, 4.0)
+    ops.call("scream_add_f32", None, None, True, None)
+    ops.call("scream_add_f32", None, None, 4, 77)
+    assert rec.calls == [("scream_add_f32", (None, 4096, 4, 1234)), ("scream_add_f32", (None, None, 1, None)),
+                         ("scream_add_f32", (None, None, 4, 77))]
+    assert type(rec.calls[0][1][2]) is int
+    for args in ((None,), (None, None), (None, None, 4, None, None)):
+        with pytest.raises(TypeError, match="scream_add_f32 takes 4 arguments"):
+            ops.call("scream_add_f32", *args)
+    with pytest.raises(TypeError, match="scream_tail_image_bytes takes 2 arguments"):
+        ops.call("scream_tail_image_bytes", 2)  # no stream to append
+    for raw_only in ("scream_version", "scream_abi_version", "scream_trace_create", "scream_trace_read"):
+        with pytest.raises(TypeError, match=raw_only):
+            ops.call(raw_only)
+    del rec.calls[:]
+    exps = ops.tail_exps(e_att=3)
+    ops.call("scream_pack_tail", 1, 2, 3, None, 2, exps, 4)
+    ops.call("scream_pack_tail", 1, 2, 3, None, 3, None, 4, None)
+    (_, a), (_, b) = rec.calls
+    assert a[:5] == (1, 2, 3, None, 2) and a[6:] == (4, 1234) and b == (1, 2, 3, None, 3, None, 4, None)
+    assert C.cast(a[5], C.POINTER(_lib.TailExpsT)).contents.e_att == 3
+    for wrong in (_lib.BatchT(), "exps", 1.5):
+        with pytest.raises(TypeError, match=r"scream_pack_tail\(exps\)"):
+            ops.call("scream_pack_tail", 1, 2, 3, None, 2, wrong, 4)
+    with pytest.raises(TypeError, match=r"scream_add_f32\(y\)"):
+        ops.call("scream_add_f32", 1.5, None, 4)
+    assert len(rec.calls) == 2
+    # the real library: refusals become exceptions through call, the raw functions still answer with their codes
+    monkeypatch.setattr(_lib, "load", lambda: lib)
+    null_gemm = (None, 256, None, None, 256, 128, 256, 256, 0, 0, None, None, 0, None, None, None)
+    with pytest.raises(_lib.ScreamHipError, match=r"scream_gemm_f32: .*SCREAM_EINVAL"):
+        ops.call("scream_gemm_f32", *null_gemm)
+    assert lib.scream_gemm_f32(*null_gemm) == -1
+    with pytest.raises(_lib.ScreamHipError, match=r"scream_wgrad_workspace_bytes\(-1, 256, 256\)"):
+        ops.call("scream_wgrad_workspace_bytes", -1, 256, 256)
+    assert lib.scream_wgrad_workspace_bytes(-1, 256, 256) == -1
+    assert ops.call("scream_wgrad_workspace_bytes", 300, 128, 128) == lib.scream_wgrad_workspace_bytes(300, 128, 128) > 0
+    assert ops.call("scream_kv_image_bytes") == lib.scream_kv_image_bytes()
+
+
 def test_host_side_argument_checks_need_no_gpu():
     lib = _lib.load()
     unfused, fused = lib.scream_forward_workspace_bytes(128, 256, 1, 1, 0, 0), lib.scream_forward_workspace_bytes(128, 256, 1, 1, 1, 0)
@@ -204,10 +318,9 @@ def test_train_wrappers_size_their_scratch_through_ops_workspace():
     from the size function, with the arguments in the message, before any tensor is touched."""
     from scream_amd import ops, train
     assert callable(train.wgrad_split) and train.wgrad_split is not train.wgrad
-    lib = _lib.load()
     for sizer in ("scream_wgrad_workspace_bytes", "scream_wgrad_split_workspace_bytes"):
         with pytest.raises(_lib.ScreamHipError, match=r"%s\(300, 200, 256\)" % sizer):
-            ops._workspace(getattr(lib, sizer), sizer, 300, 200, 256, device="cpu")
+            ops._workspace(sizer, 300, 200, 256, device="cpu")
     dY, X = torch.zeros(300, 200), torch.zeros(300, 256)
     for fn in (train.wgrad, train.wgrad_split):
         with pytest.raises(_lib.ScreamHipError, match=r"\(300, 200, 256\)"):
