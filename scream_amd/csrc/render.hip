@@ -374,6 +374,8 @@ extern "C" int scream_render_depth(const float* src, const int32_t* s_row0, cons
         SCREAM_LAUNCH_CHECK();
         // split each point range so that the launch has ~2 048 blocks when the images alone give fewer (B = 1: 48 blocks of
         // 1 024 pixels at w = 64), but never below 256 points per block; the merge makes the result independent of the split
+        // (restated line for line as split_plan() in tests/render_ref.py, by which the tests know that a shape reaches the
+        // mid-range scan of the splat block: change both together)
         const int64_t tiles = (int64_t)(w / TILE) * (w / TILE);
         const int64_t base = tiles * n_range;
         int64_t splits = (2048 + base - 1) / base;

@@ -70,6 +70,38 @@ def test_restatement_reassigned_eulers_follow_the_reference():
     assert torch.equal(RR.render(src, tgt, 24, 64, ref.eulers)[0], ref(src, tgt))
 
 
+def test_split_plan_restates_the_host_rule():
+    # the B = 32 training step at w = 64, six views: 4 tiles * 384 images = 1536 blocks -> ceil(2048 / 1536) = 2 splits
+    assert RR.split_plan(64, 32, 6, 5100) == (2, 2550)
+    # one pair: 48 blocks -> 43 splits wanted, ceil(5000 / 256) = 20 allowed
+    assert RR.split_plan(64, 1, 6, 5000) == (20, 250)
+    # the other calls of tests/test_gpu_render.py: none reaches 768 staged points before its range ends
+    assert RR.split_plan(128, 1, 6, 5000) == (11, 455)  # 192 blocks -> 11 splits
+    assert RR.split_plan(64, 5, 6, 5000) == (9, 556)    # 240 blocks -> 9 splits
+    assert RR.split_plan(64, 1, 1, 16000) == (63, 254)  # 8 blocks -> 256 wanted, 63 allowed; ceil(16000 / 63) = 254
+    # the shapes of tests/test_gpu_render_paths.py
+    assert RR.split_plan(64, 16, 6, 7500) == (3, 2500)  # 768 blocks
+    assert RR.split_plan(256, 16, 1, 3000) == (1, 3000)  # 2048 blocks: no split at all
+    assert RR.split_plan(256, 1, 6, 4000) == (3, 1334)  # 768 blocks; 3 * 1334 = 4002
+    assert RR.split_plan(192, 1, 1, 1500) == (6, 250)
+    assert RR.split_plan(64, 1, 6, 1) == (1, 1)
+    # per_split is rounded up: 576 blocks -> 4 splits of ceil(1025 / 4) = 257 (the last one holds 254 points)
+    assert RR.split_plan(64, 12, 6, 1025) == (4, 257)
+    assert RR.split_plan(64, 12, 6, 1030) == (4, 258)
+
+
+def test_restatement_in_point_chunks_changes_nothing(monkeypatch):
+    src, tgt = _clouds(120, 90, seed=5)
+    src = torch.cat([src, src[:20]])  # ties across chunks: the lower chunk keeps them, as one chunk's torch.max does here
+    want = RR.render(src, tgt, 24, 64, view_eulers("muti")[:2], top2=True)
+    monkeypatch.setattr(RR, "POINT_CHUNK", 37)
+    got = RR.render(src, tgt, 24, 64, view_eulers("muti")[:2], top2=True)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[3], want[3]) and got[2] == want[2]
+    assert torch.equal(got[1][:, 1], want[1][:, 1])  # the target has no duplicates
+    moved = got[1][:, 0] != want[1][:, 0]
+    assert torch.equal(src[got[1][:, 0][moved]], src[want[1][:, 0][moved]])  # a tie may name either copy of the point
+
+
 def test_view_matrices_equal_scipy_bitwise():
     Rotation = pytest.importorskip("scipy.spatial.transform").Rotation
     rng = np.random.default_rng(0)
