@@ -7,6 +7,7 @@ import argparse
 import torch
 
 from scream_amd import dist as _dist
+from scream_amd.chamfer import ChamferDistance  # noqa: F401  (evaluate_open_gf.py:25-41, on the HIP kernel)
 from scream_amd.evaluate_open_gf import OpenGFFiles, SyntheticDEM, evaluate_dem_generation  # noqa: F401
 
 

@@ -805,6 +805,50 @@ int scream_l1_pairs_bwd(const float* dout, const float* pred, const float* xyz, 
                         const float* target, const int32_t* cloud_row0, const int32_t* cloud_len, int32_t n_pairs, int32_t max_len,
                         int64_t rows_src, float* dpred, void* stream);
 
+/* ---- The Chamfer distance of packed cloud pairs (the ChamferDistance module of evaluate_open_gf.py:25-41: square_distance, two
+ * min, two means) and its gradient (csrc/chamfer.hip; scream_amd/chamfer.py is the host layer, tests/chamfer_ref.py the numpy
+ * restatement).  a [a_rows,3] and b [b_rows,3] fp32 packed; a_row0 / a_len / b_row0 / b_len [n_pairs] int32 on the DEVICE;
+ * max_a_len / max_b_len host bounds of every a_len / b_len.  For pair p, N = a_len[p], M = b_len[p]:
+ *
+ * Forward, every step ONE rounded fp32 operation, no fma:
+ *   d(n,m)     = ((dx*dx + dy*dy) + dz*dz),  dx = a_n.x - b_m.x, dy, dz likewise -- the DIFFERENCE form (the expansion
+ *                -2ab + |a|^2 + |b|^2 of scream_nn_search cancels: coordinates of size 5 leave 3e-6 of error on a 4e-4 distance);
+ *                d(n,m) has the same bits seen from a or from b
+ *   d_ab[n]    = min over m of d(n,m);  idx_ab[n] = the LOWEST m that attains it (strict < scanning m upwards, the tie rule of
+ *                scream_nn_search); d_ba[m], idx_ba[m] the same from the other side; indices count inside the pair's other cloud
+ *   rows outside every cloud (the padding of a PackedBatch), and the rows of a pair with an empty side: idx = -1, d = 0
+ *   S_ab       = float64 sum of the widened d_ab of the pair: 256-row chunks, inside a chunk s = v[0]; s += v[1]; ... in
+ *                ascending row order, then acc = chunk[0]; acc += chunk[1]; ... (the chunk and cloud sums of scream_l1_pairs_fwd);
+ *                S_ba likewise over d_ba
+ *   loss_pair[p] = S_ab / N + S_ba / M  in float64 (two divisions, one addition);  0 when N == 0 or M == 0
+ *   loss       = fp32((loss_pair[0] + loss_pair[1] + ...) / n_pairs)
+ * Backward, the gradient of loss for the upstream dout (one fp32 on the DEVICE); every step ONE float64 operation, no fma, on
+ * the fp32 coordinates widened (A, B); idx_ab / idx_ba are the forward's:
+ *   g = float64(dout) / n_pairs;  w_ab = (2 g) / N;  w_ba = (2 g) / M
+ *   da[n][k] = fp32((A_nk - B_jk) w_ab + acc w_ba),  j = idx_ab[n],
+ *              acc = 0.0; acc = acc + (A_nk - B_mk) for every m with idx_ba[m] == n, IN ASCENDING m, one after the other
+ *   db[m][k] = fp32((B_mk - A_ik) w_ba + acc w_ab),  i = idx_ba[m],  acc over the n with idx_ab[n] == m in ascending n
+ *   every other row of da / db (padding, the rows of a pair with an empty side) is exactly zero.  da or db NULL: that side is
+ *   skipped.
+ * Scratch, as typed arrays (there is no workspace sizer): keys_a uint64 [a_rows], keys_b uint64 [b_rows], part double
+ * [n_pairs * (ceil(max_a_len / 256) + ceil(max_b_len / 256))].  Outputs: idx_ab int32 / d_ab fp32 [a_rows], idx_ba / d_ba
+ * [b_rows], loss_pair double [n_pairs], loss one fp32.  The backward needs no scratch: the scatter term is a re-scan of the
+ * other side's indices in ascending order.  No float atomics (the blocks that share a long target cloud merge 64-bit
+ * (distance, index) keys with an integer minimum), no host synchronisation; the result of a pair is a pure function of that
+ * pair: bitwise repeatable, independent of the rest of the batch.  Non-finite coordinates are OUTSIDE the contract: values
+ * unspecified, no fault (every index is clamped into its cloud before it addresses anything).
+ * SCREAM_EINVAL: a null pointer (da / db excepted), n_pairs not positive, row totals outside 0 .. 2^31 - 1, max_a_len outside
+ * 0 .. a_rows or max_b_len outside 0 .. b_rows, keys / part / loss_pair not 8-byte aligned.  SCREAM_EUNSUPPORTED: n_pairs >
+ * 65535.  A pair whose rows leave a or b, or exceed the declared maxima, is found on the device and counts as empty. */
+int scream_chamfer_fwd(const float* a, const int32_t* a_row0, const int32_t* a_len, int64_t a_rows, int32_t max_a_len,
+                       const float* b, const int32_t* b_row0, const int32_t* b_len, int64_t b_rows, int32_t max_b_len,
+                       int32_t n_pairs, uint64_t* keys_a, uint64_t* keys_b, double* part, int32_t* idx_ab, float* d_ab,
+                       int32_t* idx_ba, float* d_ba, double* loss_pair, float* loss, void* stream);
+int scream_chamfer_bwd(const float* dout, const float* a, const int32_t* a_row0, const int32_t* a_len, int64_t a_rows,
+                       int32_t max_a_len, const float* b, const int32_t* b_row0, const int32_t* b_len, int64_t b_rows,
+                       int32_t max_b_len, int32_t n_pairs, const int32_t* idx_ab, const int32_t* idx_ba, float* da, float* db,
+                       void* stream);
+
 /* ---- The optimiser step: torch.optim.Adam (weight_decay = 0, amsgrad = False, maximize = False) over every parameter of a
  * model in one launch (csrc/optim.hip; scream_amd/optim.py is its host layer, tests/adam_ref.py its numpy restatement).
  * tensors: DEVICE work list of n_tensors rows of SCREAM_ADAM_TENSOR_BYTES bytes, { float* p; const float* grad; float* m;

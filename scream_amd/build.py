@@ -47,6 +47,9 @@ SOURCES = {
     "optim.hip": ["-ffp-contract=off"],
     # the discriminator's BatchNorm and loss steps are individually rounded operations restated by tests/gan_ref.py
     "gan.hip": ["-ffp-contract=off"],
+    # the Chamfer distance is one rounded fp32 operation per step forward, one float64 operation per step backward, restated by
+    # tests/chamfer_ref.py
+    "chamfer.hip": ["-ffp-contract=off"],
 }
 # The gate: what asm_check.gate() must pass on a file's generated code before the library is linked, as (asm loads, no scratch).
 # asm loads: the file requests operands with inline asm and waits for them with hand-counted s_waitcnt vmcnt(N); whether hipcc's
@@ -64,6 +67,8 @@ GATE = {
     "icp_raw.hip": (False, ("raw_search_kernel", "raw_nn_kernel")),
     # the bf16 training GEMMs hold a 32 x 256 accumulator tile and both operands' next k-tile in registers
     "gemm_bf16.hip": (False, ("gemm_bf16_kernel", "wgrad_split_partial_kernel")),
+    # the scan carries four queries' coordinates, minima and indices per thread in registers; the re-scan of the backward its sums
+    "chamfer.hip": (False, ("chamfer_scan_kernel", "chamfer_bwd_kernel")),
 }
 COMMON = ["-O3", "-std=c++17", "--offload-arch=" + ARCH, "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -110,10 +110,16 @@ class SyntheticDEM(torch.utils.data.Dataset):
 
 
 @torch.no_grad()
-def evaluate_samples(net, samples: Sequence[tuple], device: Optional[torch.device] = None, coarse: str = "host") -> np.ndarray:
+def evaluate_samples(net, samples: Sequence[tuple], device: Optional[torch.device] = None, coarse: str = "host",
+                     chamfer: str = "reference") -> np.ndarray:
     """One batch of samples -> [B, 3] (chamfer, height MAE, height MSE), each x 1000 (evaluate_open_gf.py:57-68).
     coarse="gpu": the samples come from a coarse="gpu" dataset (their second entry is the raw DEM) and the coarse DEMs of the
-    whole batch are built here, in one batched call."""
+    whole batch are built here, in one batched call.
+    chamfer="reference": the Chamfer column sample by sample from geometry.chamfer_distance, in the expansion arithmetic of
+    utils.square_distance (the default); "direct": the column of the whole batch from one chamfer_packed call (the difference
+    form, scream_amd/chamfer.py) and one copy to the host."""
+    if chamfer not in ("reference", "direct"):
+        raise ValueError("chamfer must be 'reference' or 'direct', got %r" % (chamfer,))
     device = device or next(net.parameters()).device
     dsms = [s[0].to(device) for s in samples]
     if _check_coarse(coarse) == "gpu":
@@ -125,22 +131,32 @@ def evaluate_samples(net, samples: Sequence[tuple], device: Optional[torch.devic
     rows = torch.zeros(len(samples), 3, dtype=torch.float64)
     for i, (p, d) in enumerate(zip(preds, dems)):
         dz = p[:, 2] - d[:, 2]
-        rows[i, 0] = chamfer_distance(p[None], d[None]).double().cpu()
+        if chamfer == "reference":
+            rows[i, 0] = chamfer_distance(p[None], d[None]).double().cpu()
         rows[i, 1] = dz.abs().mean().double().cpu()
         rows[i, 2] = (dz * dz).mean().double().cpu()
+    if chamfer == "direct":
+        from .chamfer import chamfer_packed
+        n_p, n_d = [int(p.shape[0]) for p in preds], [int(d.shape[0]) for d in dems]
+        start = lambda n: np.concatenate([[0], np.cumsum(n)[:-1]])
+        i32 = torch.from_numpy(np.concatenate([start(n_p), n_p, start(n_d), n_d]).astype(np.int32)).to(device)
+        B = len(samples)
+        _, pair = chamfer_packed(torch.cat(preds), i32[:B], i32[B:2 * B], torch.cat(dems), i32[2 * B:3 * B], i32[3 * B:], max(n_p),
+                                 max(n_d), return_pairs=True)
+        rows[:, 0] = pair.cpu()
     return rows.numpy() * METRIC_SCALE
 
 
-def evaluate_dem_generation(net, dataset, batch_samples: int = 8, verbose: bool = True):
+def evaluate_dem_generation(net, dataset, batch_samples: int = 8, verbose: bool = True, chamfer: str = "reference"):
     """evaluate_open_gf.py:46-73 -> (chamfer_loss, high_loss_mae, high_loss_mse).  With torch.distributed initialised the
-    samples are sharded round-robin over ranks and the per-sample rows are all-gathered once at the end."""
+    samples are sharded round-robin over ranks and the per-sample rows are all-gathered once at the end.  chamfer: evaluate_samples'."""
     n = len(dataset)
     rank, world = sdist.rank_world()
     mine = sdist.shard_indices(n, rank, world)
     rows: List[np.ndarray] = []
     for lo in range(0, len(mine), batch_samples):
         ids = mine[lo:lo + batch_samples]
-        r = evaluate_samples(net, [dataset[i] for i in ids], coarse=getattr(dataset, "coarse", "host"))
+        r = evaluate_samples(net, [dataset[i] for i in ids], coarse=getattr(dataset, "coarse", "host"), chamfer=chamfer)
         full = np.zeros((len(ids), sdist.ROW_WIDTH))
         full[:, sdist.COL_PAIR] = ids
         full[:, 1:4] = r

@@ -79,6 +79,17 @@ def _batch_of(prepared) -> PackedBatch:
     return prepared.batch if isinstance(prepared, PreparedPairs) else prepared[0]
 
 
+def _point_loss(net, pred, prepared, chamfer_weight: float, chamfer_rows: Optional[Callable]):
+    """The point loss of a step: loss_packed, plus chamfer_weight times the Chamfer distance of the prediction against
+    chamfer_rows(prepared) when the weight is positive (with weight 0 nothing of it is entered)."""
+    loss = _loss(net, pred, prepared)
+    if chamfer_weight > 0:
+        if chamfer_rows is None:
+            raise ValueError("chamfer_weight > 0 needs chamfer_rows (pair_real_rows or dem_real_rows)")
+        loss = loss + chamfer_weight * net.chamfer_packed_loss(pred, _batch_of(prepared), chamfer_rows(prepared))
+    return loss
+
+
 def _step(loss, opt, scaler):
     """zero_grad, backward, step; through `scaler` (scale, step, update) when one is given."""
     opt.zero_grad()
@@ -91,28 +102,33 @@ def _step(loss, opt, scaler):
         scaler.update()
 
 
-def train_epoch(net, opt, batches: Iterable, prepare: Callable, scaler=None) -> Tuple[float, np.ndarray]:
+def train_epoch(net, opt, batches: Iterable, prepare: Callable, scaler=None, chamfer_weight: float = 0.0,
+                chamfer_rows: Optional[Callable] = None) -> Tuple[float, np.ndarray]:
     """One pass over `batches`: prepare, forward_packed_train, loss_packed, zero_grad, backward, step (through `scaler`, a
-    torch.amp.GradScaler, when one is given).  Returns (the float64 mean of the per-step losses, the fp32 losses)."""
+    torch.amp.GradScaler, when one is given).  chamfer_weight > 0: the loss of a step is loss_packed + chamfer_weight *
+    net.chamfer_packed_loss(pred, batch, chamfer_rows(prepared)), chamfer_rows being pair_real_rows or dem_real_rows (or any
+    packed [rows_src,3] ground truth, row-paired or not).  Returns (the float64 mean of the per-step losses, the fp32 losses)."""
     net.train()
     log = _LossLog(batches)
     for raw in batches:
         prepared = prepare(raw)
-        loss = _loss(net, net.forward_packed_train(_batch_of(prepared)), prepared)
+        loss = _point_loss(net, net.forward_packed_train(_batch_of(prepared)), prepared, chamfer_weight, chamfer_rows)
         _step(loss, opt, scaler)
         log.add(loss)
     losses = log.host()
     return _mean(losses), losses
 
 
-def val_loss(net, batches: Iterable, prepare: Callable) -> Tuple[float, np.ndarray]:
-    """The same loss on the inference forward, in eval() under no_grad.  Returns (float64 mean, the fp32 per-batch losses)."""
+def val_loss(net, batches: Iterable, prepare: Callable, chamfer_weight: float = 0.0,
+             chamfer_rows: Optional[Callable] = None) -> Tuple[float, np.ndarray]:
+    """The same loss (train_epoch's, chamfer_weight included) on the inference forward, in eval() under no_grad.  Returns
+    (float64 mean, the fp32 per-batch losses)."""
     net.eval()
     log = _LossLog(batches)
     with torch.no_grad():
         for raw in batches:
             prepared = prepare(raw)
-            log.add(_loss(net, net.forward_packed(_batch_of(prepared)), prepared))
+            log.add(_point_loss(net, net.forward_packed(_batch_of(prepared)), prepared, chamfer_weight, chamfer_rows))
     losses = log.host()
     return _mean(losses), losses
 
@@ -159,11 +175,11 @@ def gan_training(device, real_rows: Callable, lr_d: float = 1e-4, betas=(0.5, 0.
 
 
 def train_epoch_gan(net, gan_loss, opt_g, opt_d, batches: Iterable, prepare: Callable, real_rows: Callable, scaler=None,
-                    g_weight: float = 0.1) -> Tuple[float, np.ndarray]:
+                    g_weight: float = 0.1, chamfer_weight: float = 0.0, chamfer_rows: Optional[Callable] = None) -> Tuple[float, np.ndarray]:
     """train_epoch with the adversarial loss, in the reference's order (train_3d_match.py:171-205), every step:
       1. forward_packed_train;
       2. the prediction's images through render_rows;
-      3. loss = point_loss + g_weight * g_loss, g_loss = gan_loss(imgs, None, 0); opt_g.zero_grad(), backward, opt_g.step();
+      3. loss = point_loss + g_weight * g_loss (point_loss: train_epoch's, chamfer_weight included), g_loss = gan_loss(imgs, None, 0); opt_g.zero_grad(), backward, opt_g.step();
       4. real = the images of real_rows(prepared), the ground-truth source rows, rendered under no_grad;
       5. d_loss = gan_loss(imgs.detach(), real, 1); opt_d.zero_grad(), backward, opt_d.step().
     With a `scaler` both updates go scale(loss).backward(), step(opt), update(), as train_kitti.py:185-204 writes them.
@@ -179,7 +195,7 @@ def train_epoch_gan(net, gan_loss, opt_g, opt_d, batches: Iterable, prepare: Cal
         pred = net.forward_packed_train(_batch_of(prepared))
         imgs = render_rows(net, pred, prepared)
         g = gan_loss(imgs, None, 0)
-        loss = _loss(net, pred, prepared) + g_weight * g
+        loss = _point_loss(net, pred, prepared, chamfer_weight, chamfer_rows) + g_weight * g
         _step(loss, opt_g, scaler)
         with torch.no_grad():
             real = render_rows(net, real_rows(prepared), prepared)
@@ -193,23 +209,24 @@ def train_epoch_gan(net, gan_loss, opt_g, opt_d, batches: Iterable, prepare: Cal
 
 def fit(net, opt, train_batches: Iterable, val_batches: Iterable, prepare_train: Callable, prepare_val: Callable, epochs: int,
         save_path: str, scaler=None, gamma: float = 0.5, every: int = 15, floor: float = 1e-5, log: Optional[Callable] = print,
-        gan: Optional[GanTraining] = None) -> List[dict]:
+        gan: Optional[GanTraining] = None, chamfer_weight: float = 0.0, chamfer_rows: Optional[Callable] = None) -> List[dict]:
     """The reference's train(): for epoch in range(1, epochs) -- as it writes it, epochs - 1 passes -- a training epoch, the
     validation loss, a checkpoint (net.state_dict(), what the reference's models load) whenever that loss improves on the best so
     far, then the learning-rate rule.  Returns one dict per epoch: epoch, train_loss, val_loss, saved, lr (the rate after the
     epoch).  gan: a GanTraining turns the epoch into train_epoch_gan (the reference's use_GAN = True); the dicts then also carry
     g_loss and d_loss (epoch means), the discriminator is saved with the generator, and its rate is left alone, as the reference
-    only ever updates optimizer_G's."""
+    only ever updates optimizer_G's.  chamfer_weight / chamfer_rows: train_epoch's, for the training and the validation loss alike."""
     best = 1e8  # train_3d_match.py:157
     history = []
     for epoch in range(1, epochs):
         extra = {}
         if gan is None:
-            train_loss, _ = train_epoch(net, opt, train_batches, prepare_train, scaler)
+            train_loss, _ = train_epoch(net, opt, train_batches, prepare_train, scaler, chamfer_weight, chamfer_rows)
         else:
-            train_loss, steps = train_epoch_gan(net, gan.loss, opt, gan.opt, train_batches, prepare_train, gan.real_rows, scaler, gan.g_weight)
+            train_loss, steps = train_epoch_gan(net, gan.loss, opt, gan.opt, train_batches, prepare_train, gan.real_rows, scaler, gan.g_weight,
+                                                chamfer_weight, chamfer_rows)
             extra = dict(g_loss=_mean(steps[:, 1]), d_loss=_mean(steps[:, 2]))
-        v, _ = val_loss(net, val_batches, prepare_val)
+        v, _ = val_loss(net, val_batches, prepare_val, chamfer_weight, chamfer_rows)
         saved = v < best
         if saved:
             best = v
@@ -254,10 +271,12 @@ class Driver:
         return gan_training(device, self.real_rows, lr_d=self.mod.lr_d, save_path=self.mod.discriminator_save_path)
 
     def train(self, model, datasets: Callable, preparers: Callable, synthetic=0, batch=1, train_backend=None, layers=(6, 6),
-              n_epochs=None, save_path=None, device=None, log=print, scaler=None, gan=None) -> List[dict]:
+              n_epochs=None, save_path=None, device=None, log=print, scaler=None, gan=None, chamfer_weight=None) -> List[dict]:
         """The body of the reference's train(): `model` (a class) on `device`, FusedAdam at lr_g, loaders over
         datasets(synthetic) -> (train_set, val_set), preparers(device) -> (prepare_train, prepare_val), then fit().  The torch
-        global generator is consumed in this order: the model, the loaders, the GAN loss.  Returns fit()'s history."""
+        global generator is consumed in this order: the model, the loaders, the GAN loss.  chamfer_weight: the weight of the
+        Chamfer term against the driver's real_rows (None: the module's chamfer_weight, which --chamfer sets; 0 without one).
+        Returns fit()'s history."""
         from .optim import FusedAdam
         m = self.mod
         device = torch.device(device if device is not None else "cuda:0")
@@ -272,7 +291,9 @@ class Driver:
         prepare_train, prepare_val = preparers(device)
         return fit(net, optimizer_G, train_loader, val_loader, prepare_train, prepare_val, m.epochs if n_epochs is None else n_epochs,
                    save_path or m.generator_save_path, scaler=scaler, gamma=m.learning_rate_decay_gamma, every=m.lr_update_epoch,
-                   floor=m.min_learning_rate, log=log, gan=m._gan(device) if (m.use_GAN if gan is None else gan) else None)
+                   floor=m.min_learning_rate, log=log, gan=m._gan(device) if (m.use_GAN if gan is None else gan) else None,
+                   chamfer_weight=float(getattr(m, "chamfer_weight", 0.0) if chamfer_weight is None else chamfer_weight),
+                   chamfer_rows=self.real_rows)
 
     def main(self, argv=None):
         from .model import PointTransformer
@@ -283,8 +304,13 @@ class Driver:
         ap.add_argument("--train-backend", choices=PointTransformer.TRAIN_BACKENDS, default=None)
         ap.add_argument("--epochs", type=int, default=m.epochs)
         ap.add_argument("--gan", action="store_true", help="train with the adversarial loss (use_GAN)")
+        ap.add_argument("--chamfer", type=float, default=0.0, metavar="W",
+                        help="add W times the HIP Chamfer distance against the ground-truth rows to the point loss (default 0: off)")
         a = ap.parse_args(argv)
+        if a.chamfer < 0:
+            ap.error("--chamfer must not be negative")
         m.use_GAN = m.use_GAN or a.gan
+        m.chamfer_weight = a.chamfer
         m.train(a.synthetic, a.batch, a.train_backend, n_epochs=a.epochs)
 
 

@@ -404,6 +404,17 @@ class PointTransformer(nn.Module):
         from .prep import packed_l1_loss
         return packed_l1_loss(pred, prepared)
 
+    def chamfer_packed_loss(self, pred, batch, rows):
+        """The Chamfer distance (scream_amd/chamfer.py) of the packed prediction [rows_src,3] against the packed clouds `rows`
+        [rows_src,3], pair by pair over the batch's source rows; `rows` need not be row-paired with the prediction.  An fp32
+        scalar with a grad_fn into `pred`."""
+        from .chamfer import chamfer_packed
+        if tuple(pred.shape) != (batch.rows_src, 3) or tuple(rows.shape) != (batch.rows_src, 3):
+            raise _lib.ScreamHipError("chamfer_packed_loss takes two packed [%d,3] tensors, got %s and %s"
+                                      % (batch.rows_src, tuple(pred.shape), tuple(rows.shape)))
+        n = max(batch.src_len)
+        return chamfer_packed(pred, batch.src_row0, batch.src_len_dev, rows.detach().to(torch.float32), batch.src_row0, batch.src_len_dev, n, n)
+
 
 class DEMTransformer(PointTransformer):
     """models/pointnet.py:103-167 (ground generation on OpenGF): the same blocks with separate stem weights for the

@@ -599,6 +599,47 @@ def l1_pairs_bwd(dout: torch.Tensor, pred: torch.Tensor, xyz, rot, trans, target
     return dpred
 
 
+def _chamfer_args(a, a_row0, a_len, max_a_len, b, b_row0, b_len, max_b_len):
+    for name, t in (("a", a), ("b", b)):
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise _lib.ScreamHipError("chamfer: %s is packed [rows,3], got %s" % (name, tuple(t.shape)))
+    n_pairs = a_row0.shape[0]
+    if not (a_len.shape[0] == b_row0.shape[0] == b_len.shape[0] == n_pairs):
+        raise _lib.ScreamHipError("chamfer: row0 / len of a and b must have one entry per pair")
+    # (an empty tensor has no address; the library is told 0 rows and reads none)
+    one = lambda t: t if t.shape[0] else t.new_zeros(1, 3)
+    return one(a), a_row0, a_len, a.shape[0], max_a_len, one(b), b_row0, b_len, b.shape[0], max_b_len, n_pairs
+
+
+def chamfer_fwd(a: torch.Tensor, a_row0, a_len, max_a_len: int, b: torch.Tensor, b_row0, b_len, max_b_len: int):
+    """scream_chamfer_fwd over packed clouds: (loss fp32 scalar, loss_pair float64 [B], idx_ab int32 [a_rows], d_ab fp32 [a_rows],
+    idx_ba [b_rows], d_ba [b_rows]).  No host sync."""
+    dev = a.device
+    args = _chamfer_args(a, a_row0, a_len, max_a_len, b, b_row0, b_len, max_b_len)
+    ar, br, n_pairs = a.shape[0], b.shape[0], args[-1]
+    chunk = lambda n: (n + 255) // 256
+    keys_a = torch.empty(max(ar, 1), device=dev, dtype=torch.int64)
+    keys_b = torch.empty(max(br, 1), device=dev, dtype=torch.int64)
+    part = torch.empty(max(n_pairs * (chunk(max_a_len) + chunk(max_b_len)), 1), device=dev, dtype=torch.float64)
+    idx_ab, d_ab = torch.empty(max(ar, 1), device=dev, dtype=torch.int32), torch.empty(max(ar, 1), device=dev, dtype=torch.float32)
+    idx_ba, d_ba = torch.empty(max(br, 1), device=dev, dtype=torch.int32), torch.empty(max(br, 1), device=dev, dtype=torch.float32)
+    loss_pair = torch.empty(n_pairs, device=dev, dtype=torch.float64)
+    loss = torch.empty((), device=dev, dtype=torch.float32)
+    call("scream_chamfer_fwd", *args, keys_a, keys_b, part, idx_ab, d_ab, idx_ba, d_ba, loss_pair, loss)
+    return loss, loss_pair, idx_ab[:ar], d_ab[:ar], idx_ba[:br], d_ba[:br]
+
+
+def chamfer_bwd(dout: torch.Tensor, a: torch.Tensor, a_row0, a_len, max_a_len: int, b: torch.Tensor, b_row0, b_len, max_b_len: int,
+                idx_ab: torch.Tensor, idx_ba: torch.Tensor, need_a: bool = True, need_b: bool = True):
+    """scream_chamfer_bwd: (da, db) fp32 like a and b for the upstream gradient `dout` (one fp32 on the device); None for a side
+    that is not needed."""
+    args = _chamfer_args(a, a_row0, a_len, max_a_len, b, b_row0, b_len, max_b_len)
+    da, db = torch.empty_like(a) if need_a else None, torch.empty_like(b) if need_b else None
+    one = lambda t: t if t.shape[0] else t.new_zeros(1)
+    call("scream_chamfer_bwd", dout, *args, one(idx_ab), one(idx_ba), da if a.shape[0] else None, db if b.shape[0] else None)
+    return da, db
+
+
 def kabsch_corr(src, ref, src_row0, src_len, ref_row0, idx, valid, s, c) -> Tuple[torch.Tensor, torch.Tensor]:
     """Returns (T [n_pairs,4,4], n_corr int32 [n_pairs])."""
     n_pairs = s.shape[0]

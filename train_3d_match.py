@@ -1,7 +1,7 @@
 """Drop-in for the reference's ``train_3d_match.py``: the same names (update_lr, evaluate, train), paths and hyper-parameters,
 over the loops of scream_amd/fit.py -- batches prepared on the GPU, the HIP forward / backward, FusedAdam.
 
-    python train_3d_match.py [--batch 1] [--synthetic N] [--train-backend f32|split|bf16] [--gan] [--epochs 45]
+    python train_3d_match.py [--batch 1] [--synthetic N] [--train-backend f32|split|bf16] [--gan] [--chamfer W] [--epochs 45]
 
 With the reference's on-disk splits present (``3DMatch_train/`` and ``3DMatch_val/``: src%d.npy, tgt%d.npy, T%d.npy, raw metric
 clouds) it trains on them; ``--synthetic N`` trains on N seeded synthetic pairs and validates on N / 4 others (no dataset ships

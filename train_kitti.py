@@ -1,7 +1,7 @@
 """Drop-in for the reference's ``train_kitti.py``: the same names (update_lr, evaluate, train), path and hyper-parameters, over
 the loops of scream_amd/fit.py -- batches prepared on the GPU, the HIP forward / backward, FusedAdam under a GradScaler.
 
-    python train_kitti.py [--batch 1] [--synthetic N] [--train-backend f32|split|bf16] [--gan] [--epochs 120]
+    python train_kitti.py [--batch 1] [--synthetic N] [--train-backend f32|split|bf16] [--gan] [--chamfer W] [--epochs 120]
 
 With the reference's on-disk splits present (``KITTI_train/`` and ``KITTI_val/``: src%d.npy, tgt%d.npy, T%d.npy, raw metric
 clouds) it trains on them; ``--synthetic N`` trains on N seeded synthetic pairs and validates on N / 4 others.  Nothing runs at

@@ -1,12 +1,13 @@
 """Drop-in for the reference's ``train_open_gf.py``: the same names (update_lr, evaluate, train), path and hyper-parameters, over
 the loops of scream_amd/fit.py -- DEMTransformer on packed batches, the HIP forward / backward, FusedAdam.
 
-    python train_open_gf.py [--batch 1] [--synthetic N] [--train-backend f32|split|bf16] [--gan] [--epochs 45]
+    python train_open_gf.py [--batch 1] [--synthetic N] [--train-backend f32|split|bf16] [--gan] [--chamfer W] [--epochs 45]
 
 With the reference's on-disk splits present (``OpenGF_train/`` and ``OpenGF_val/``: 1.npy, 2.npy, ... [N,6] DSM | DEM) it trains
 on them; ``--synthetic N`` trains on N seeded synthetic terrain patches and validates on N / 4 others.  Nothing runs at import.
 evaluate() returns the validation loss (the reference's "chamfer loss" is this L1 loss); its height-loss progress column is
-evaluate_open_gf.py's.  ``--gan`` turns on use_GAN: the adversarial loss of
+evaluate_open_gf.py's.  ``--chamfer W`` adds W times the Chamfer distance of scream_amd/chamfer.py against the ground-truth DEM to
+the L1 loss of every step (fit(chamfer_weight=W)); that term needs no row pairing between prediction and ground truth.  ``--gan`` turns on use_GAN: the adversarial loss of
 scream_amd/gan.py (a 2-channel HIP discriminator, FusedAdam at lr_d with betas (0.5, 0.999)) through fit(gan=...); the
 discriminator is saved to discriminator_save_path whenever the generator is.
 """
